@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE metric: attention forward TFLOPS at head_dim=128, seqlen=8K (+ speedup vs FA2-ROCm).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|ring]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|ring] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the whole hot path (K mean -> INT8 Q/K quantizers -> fused attention kernel) over one
 batch of synthetic (q,k,v) already resident in HBM.  TFLOPS = 4*B*H*M*N*D / t (/2 causal), the reference's own
@@ -9,6 +9,11 @@ formula (bench/bench_baseline.py:31).  N=1 default workload: C3 = qk_int8_pv_fp1
 configuration the metric is quoted on.  N>1: ring sequence-parallel `sageattn` over RCCL on (1,32,65536,128)
 (BASELINE configs[4]; at 64K keys the dispatcher's choice is the INT8-QK / FP8-PV operator), strong scaling.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline figure.  --full adds the context: the attention
+kernel alone (roofline), the quantizer pre-pass, bf16 inputs, FA2-ROCm, the CPU baselines and, for N>1, the check against
+the one-GPU result.  --dump-outputs DIR writes the output of the last timed step to DIR/o.npy as float32 (a fixed,
+seeded sample of DUMP_MAX_ELEMS elements of a larger tensor), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,8 +39,23 @@ WORKLOADS = {
 }
 
 
+DUMP_MAX_ELEMS = 1 << 23  # --dump-outputs: 32 MB of float32 over all ranks
+
+
 def flops(B, H, M, N, D, causal):
     return 4.0 * B * H * M * N * D / (2.0 if causal else 1.0)
+
+
+def dump_output(o, path, max_elems):
+    """Write the output tensor `o` to `path` (.npy, float32).  Beyond `max_elems` elements, a sample at flat indices
+    drawn from a generator seeded with the element count: two runs with the same arguments write the same elements."""
+    import numpy as np
+    flat = o.detach().reshape(-1)
+    if flat.numel() > max_elems:
+        g = torch.Generator().manual_seed(flat.numel())
+        idx = torch.randint(flat.numel(), (max_elems,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(path, flat.float().cpu().numpy())
 
 
 def time_events(fn, steps, warmup):
@@ -83,9 +103,9 @@ def cpu_baseline(D, causal):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="default 20 (200 for c2, whose step is 0.17 ms: a 4 ms timed "
-                    "region is over before the clocks have settled and reads 15-20 %% low)")
-    ap.add_argument("--warmup", type=int, default=None, help="default 5 (20 for c2)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps; default 100 (20 for ring; 200 for c2, whose step "
+                    "is 0.17 ms: a 4 ms timed region is over before the clocks have settled and reads 15-20 %% low)")
+    ap.add_argument("--warmup", type=int, default=None, help="default 20 (5 for ring)")
     ap.add_argument("--workload", default=None, choices=list(WORKLOADS))
     ap.add_argument("--gran", default="per_thread", choices=["per_warp", "per_thread"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -102,7 +122,13 @@ def main():
                     "rehearse the multi-process path with several ranks on ONE GPU")
     ap.add_argument("--seq", type=int, default=None, help="override the workload's sequence length (rehearsals)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even at world size 1")
+    ap.add_argument("--full", action="store_true", help="also measure the context of the headline figure: kernel alone "
+                    "(roofline), quantizer pre-pass, bf16 inputs, FA2-ROCm, CPU baselines; N>1: check against one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/o.npy (float32; N>1: DIR/o_rank<r>.npy)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -184,8 +210,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()  # kept for --dump-outputs; earlier outputs are freed at once, as a caller's would be
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -209,8 +236,13 @@ def main():
                                f"qk_quant_gran={args.gran}", "global_batch": B, "seq_len": N, "head_dim": D,
                    "heads": H, "parallelism": parallelism},
     }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "o.npy" if world == 1 else f"o_rank{rank}.npy"
+        dump_output(last, os.path.join(args.dump_outputs, name), DUMP_MAX_ELEMS // world)
+    del last
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # ---- dominant kernel alone (pre-quantized inputs), HIP events on the launch stream
         with torch.cuda.device(dev):
             km = sa.quant.k_mean(k)
@@ -278,7 +310,7 @@ def main():
             port, sdpa = cpu_baseline(D, causal)
             out["cpu_baseline"] = port
             out["cpu_sdpa"] = sdpa
-    if use_dist and world > 1 and wl == "ring":
+    if args.full and use_dist and world > 1 and wl == "ring":
         # context for the driver's scaling table (N = 1 runs C3, a different workload): the SAME problem -- the very tensors
         # of the timed run, gathered on rank 0 -- on ONE GPU through the single-GPU operator, a few launches after the timed
         # region (the other ranks wait at the barrier).  The first real multi-GPU run thereby VALIDATES itself: rank 0's rows
