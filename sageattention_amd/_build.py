@@ -110,31 +110,6 @@ def _write_stamp(target, key):
         f.write(key + "\n")
 
 
-def build_variant(out: str, extra_flags, verbose: bool = False, only=None) -> str:
-    """Timing-only variant build (ablations, A/B): separate objects, separate output library.  `only`: the sources the
-    flags apply to -- the others are linked from the product objects (build() first)."""
-    import tempfile
-    tmp = tempfile.mkdtemp(prefix="sage_variant_")
-    objs, procs = [], []
-    for src, extra in SOURCES:
-        if only is not None and src not in only:
-            objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
-            continue
-        o = os.path.join(tmp, src.replace(".hip", ".o"))
-        objs.append(o)
-        cmd = [HIPCC] + COMMON + extra + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", o]
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for src, pr in procs:
-        o_, _ = pr.communicate()
-        if pr.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {src}:\n{o_}")
-    r = subprocess.run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out] + objs,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stdout)
-    return out
-
-
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile what is out of date and link.  The library's stamp covers every source, header and flag, so a snapshot
     that carries the built .so and its stamp but no objects (the GPU box: *.o stay behind, .gpurunignore) builds nothing."""

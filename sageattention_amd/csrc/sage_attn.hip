@@ -19,7 +19,6 @@
 // Roofline: MFMA (4*M*N*D flop per (b,h); half int8 at 2x the fp16 rate), VALU/exp2 co-limited.
 // Algorithmic HBM bytes per (b,h): M*D (Q) + N*D (K) + 2*N*D (V fp16) + 2*M*D (O) + scales.
 #include "sage_attn_common.h"
-#include "sage_attn_ablate.h"
 
 namespace sage {
 
@@ -34,7 +33,7 @@ constexpr int attn_ring_slots(int D, int nwaves, bool pv_fp8) { return (pv_fp8 &
 template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8, bool HAS_MASK>
 // (head_dim 64 FP8 PV in its dispatched 4-wave geometry is told to stay within 168 registers = three waves per SIMD: it fits
 //  without scratch, but left alone hipcc settles a few registers above the line)
-__global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4 && SAGE_MINWAVES < 3) ? 3 : SAGE_MINWAVES)
+__global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kernel(const AttnParams p) {
   static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
   static_assert(!HAS_MASK || (!CAUSAL && !PV_FP8), "attn_mask: non-causal 16-bit-PV operator");
@@ -76,9 +75,8 @@ void attn_i8_kernel(const AttnParams p) {
   // Causal: heaviest q-blocks of a head first (load balance at the end of the grid).  An XCD holds fewer workgroups than
   // a long head has q-blocks, so a head runs in two generations and the second starts again at key 0 (C4 reads 2.06x its
   // K/V + Q bytes from the HBM side, 1.72x with 8-wave workgroups: profiles/r03_ab/fetch_by_geometry.md; at 0.35 TB/s).
-  // The opposite order, meant to let the second generation find the first one's tiles in L2, was measured: 1-2 % slower
-  // on every causal shape and FETCH_SIZE went UP (742 vs 604 MB at C4).
-  if constexpr (CAUSAL && !abl::kLightFirst) qb = p.nqb - 1 - qb;
+  // Lightest first measured 1-2 % slower on every causal shape, with more HBM-side reads.
+  if constexpr (CAUSAL) qb = p.nqb - 1 - qb;
   const int hk = h / (p.Hq / p.Hk);
   int M_ = p.M, N_ = p.N;
   int64_t q_boff = b * p.qsb, k_boff = b * p.ksb, v_boff = b * p.vsb, o_boff = b * p.osb;
@@ -250,8 +248,6 @@ void attn_i8_kernel(const AttnParams p) {
   // LDS chunk position c of a tile holds global chunk (row(c), pos(c) ^ swizzle(row)).  No VGPR staging, no
   // ds_write, and the copy has a whole iteration to land (it is drained by the vmcnt(0) of the next barrier).
   // bf16 V is staged like fp16 V (16-bit elements; the transposing LDS read does not care) and multiplied as bf16.
-  // History: rounds 1-2 converted the tile to fp16 on the way (head_dim 128: through registers, head_dim 64: in place in
-  // LDS by the wave that copied the slice), which cost 5-8 % at head_dim 128 and 15-18 % at head_dim 64 against fp16 V.
   int k_voff[KC], v_voff[VC];
 #pragma unroll
   for (int i = 0; i < KC; ++i) {
@@ -269,16 +265,14 @@ void attn_i8_kernel(const AttnParams p) {
     }
   }
   // K(j) -> K buffer `buf`
-  auto dma_k = [&](int j, const int buf) __attribute__((always_inline)) {
-    if constexpr (abl::kSameTile) j = 0;
+  auto dma_k = [&](const int j, const int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < KC; ++i)
       if (KC * T == 64 * KCH || wave * 64 + i * T < 64 * KCH)
         lds_dma16(k_rsrc, (unsigned)(buf * KBYTES + (wave * 64 + i * T) * 16), k_voff[i], j * k_tile_stride);
   };
   // V(j) -> V buffer `buf`
-  auto load_v = [&](int j, const int buf) __attribute__((always_inline)) {
-    if constexpr (abl::kSameTile) j = 0;
+  auto load_v = [&](const int j, const int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < VC; ++i) {
       if (!(VC * T == VROWS * VCH || wave * 64 + i * T < VROWS * VCH)) continue;
@@ -311,10 +305,7 @@ void attn_i8_kernel(const AttnParams p) {
   float m_run = -1e30f;
   // per-lane partial row sum of the UNROUNDED p in fp32 on the VALU (the lane's 32 of the row's 64 keys per tile;
   // the two lane halves are added once in the epilogue), as the reference's Triton kernels and its fp8 CUDA kernel
-  // (attn_qk_int8_per_block.py:55-60; ComputeUnit::kCudaCore, sm89_*.cu:148).  A ones-row MFMA that sums the
-  // rounded P (the reference's fp16 CUDA trick, attn_utils.cuh:543-547) was measured slower in every configuration
-  // (head_dim 128 fp16 -3 %, fp8 -0.7 %; head_dim 64 fp16 -9 %, fp8 -7 %): the chip is power limited and an extra MFMA
-  // per P operand costs more clock than the 32 v_add_f32 it replaces.
+  // (attn_qk_int8_per_block.py:55-60; ComputeUnit::kCudaCore, sm89_*.cu:148).
   float l_run = 0.f;
   // FP16 PV at head_dim 64: the row sum runs on the matrix pipe instead -- one v_mfma_f32_16x16x32_f16 per 16-key quarter.
   // B = the quarter's 8 packed fp16 p of the lane (MFMA column l%16, k group l/16: lanes l and l+32 are the two halves of
@@ -325,11 +316,11 @@ void attn_i8_kernel(const AttnParams p) {
   // ROUNDED P -- exactly what the reference's fp16 CUDA kernel does (ComputeUnit::kTensorCore: mma::rowsum_f16f16f32 on the
   // packed half P, attn_utils.cuh:528-548, qk_int_sv_f16_cuda_sm80.cu:318-320,814), where its Triton twin sums the fp32 p.
   // At head_dim 64 the loop is bound by vector issue and the matrix pipe is a third busy: steady state C2 +2.7 %, C2-causal
-  // +3.1 %, (4,32,8192,64) +3.0 % against the VALU sums (a first form on v_mfma_f32_4x4x4_16b_f16, 8 per tile, gave +1.5 /
-  // +2.3 / +1.4 %), and the unrounded p are dead after the convert (153-156 registers instead of 162-168).  At head_dim 128
-  // every gap already holds a P.V MFMA: 4x4x4 -1.5 %, this form +0.2 ... +0.8 % -- not worth giving up the exact fp32 sums there.
+  // +3.1 %, (4,32,8192,64) +3.0 % against the VALU sums, and the unrounded p are dead after the convert (153-156 registers
+  // instead of 162-168).  At head_dim 128 every gap already holds a P.V MFMA: +0.2 ... +0.8 % -- not worth giving up the
+  // exact fp32 sums there.
   // (bf16 PV keeps the VALU sums of the unrounded p: a sum of bf16-rounded P would cost the LSE three more bits)
-  constexpr bool MROW = !PV_FP8 && !V_BF16 && (D == 64 ? !abl::kValuRowSum64 : abl::kMfmaRowSum128);
+  constexpr bool MROW = !PV_FP8 && !V_BF16 && D == 64;
   v4f l4 = {0.f, 0.f, 0.f, 0.f};
   v8h sel8;
   {
@@ -355,23 +346,15 @@ void attn_i8_kernel(const AttnParams p) {
   for (int e = 0; e < 16; ++e) bias[e] = kBiasI;
   // keep the 16 bias registers resident: as a known constant the compiler re-materialises them with 8 v_mov_b64 per
   // tile (or, in the in-place form below, 16 moves per S chain), and the kernel is bound by the vector issue port (every
-  // VALU instruction costs 4 cycles of it).  Not in the attn_mask instantiation, which has no registers to spare.
-  // History: until the end of round 2 the head_dim-64 FP8-PV and causal variants gave the pin up to stay within the 168
-  // registers of three waves per SIMD (worth more than the moves: fp8 +5 %, causal +7 %).  Since the register diet, the MFMA
-  // row sums and the bf16-native P.V every dispatched head_dim-64 variant fits WITH the pin (153-168 registers, no scratch;
-  // the build fails otherwise): C2-causal +3.7 % (fp16), +3.1 % (bf16), +4.9 % (FP8 PV); C2-fp8 +3.9 %, (4,32,8192,64)-fp8
-  // +4.0 %; bit-identical.
+  // VALU instruction costs 4 cycles of it).  Not in the attn_mask instantiation, which has no registers to spare.  Every
+  // dispatched head_dim-64 variant fits WITH the pin (153-168 registers, no scratch; the build fails otherwise): C2-causal
+  // +3.1 ... +4.9 %, C2-fp8 +3.9 %, (4,32,8192,64)-fp8 +4.0 %.
   constexpr bool BIAS_RESIDENT = !HAS_MASK;
   if constexpr (BIAS_RESIDENT) asm volatile("" : "+v"(bias));
   // First k-step of an S^T chain: acc = bias + K.Q^T.  C is either the resident bias tuple or the MFMA's own destination
   // registers initialised in place (C = D), so the chain never needs a second 16-register tuple.
-  // History: round 1 blamed nondeterministic rows at head_dim 64 / causal on hipcc re-using a temporary C tuple too early
-  // and introduced this form as the fix.  That diagnosis was wrong: the cause was the missing barrier between the
-  // prologue S(0) and the first K(2) copy (below; profiles/r02_race_evidence.md).  With the barrier in place the old
-  // form (-DSAGE_EXP_CTEMP) is bit-stable too (0 of 100 + 0 of 1000 stressed launches); this form stays because it is
-  // what every test and profile of the kernel ran on.
   auto mfma_s_first = [&](const v4i a, const v4i b) __attribute__((always_inline)) -> v16i {
-    if constexpr (BIAS_RESIDENT || abl::kCTemp) {
+    if constexpr (BIAS_RESIDENT) {
       return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, bias, 0, 0, 0);
     } else {
       v16i acc = bias;
@@ -386,12 +369,8 @@ void attn_i8_kernel(const AttnParams p) {
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        if constexpr (abl::kNoQK) {
-          s[mt] = bias; s[mt][0] += kbuf + ks;
-        } else {
-          const v4i a = *reinterpret_cast<const v4i*>(k_rd[ks] + (kbuf * KBYTES + mt * 32 * D));
-          s[mt] = ks == 0 ? mfma_s_first(a, qf[ks]) : __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qf[ks], s[mt], 0, 0, 0);
-        }
+        const v4i a = *reinterpret_cast<const v4i*>(k_rd[ks] + (kbuf * KBYTES + mt * 32 * D));
+        s[mt] = ks == 0 ? mfma_s_first(a, qf[ks]) : __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qf[ks], s[mt], 0, 0, 0);
       }
   };
   // dequantisation scales of tile j: …sm80.cu:131, 4 per 64 keys, index (c%8)/2 = 2*hh + ((reg&3)>>1)
@@ -568,8 +547,7 @@ void attn_i8_kernel(const AttnParams p) {
       if (MASKED && fmask) {
         pv = __builtin_amdgcn_exp2f(__int_as_float(s[mt][e]) - m_run + kPOff);  // registers hold fp32 logits
       } else {
-        pv = __builtin_fmaf(__int_as_float(s[mt][e]), g1 ? sc1 : sc0, g1 ? c1 : c0);
-        if constexpr (!abl::kNoExp) pv = __builtin_amdgcn_exp2f(pv);
+        pv = __builtin_amdgcn_exp2f(__builtin_fmaf(__int_as_float(s[mt][e]), g1 ? sc1 : sc0, g1 ? c1 : c0));
       }
       return pv;
     };
@@ -601,8 +579,7 @@ void attn_i8_kernel(const AttnParams p) {
             v8h a;
             a.s0123 = __builtin_bit_cast(v4h, lo);
             a.s4567 = __builtin_bit_cast(v4h, hi);
-            if constexpr (abl::kNoPV) asm volatile("" ::"v"(a), "v"(pf));
-            else acc_o[dt] = pv_mfma(a, pf, acc_o[dt]);
+            acc_o[dt] = pv_mfma(a, pf, acc_o[dt]);
           }
         }
     } else {
@@ -645,11 +622,8 @@ void attn_i8_kernel(const AttnParams p) {
   int n_plain = wave_tiles;
   if (N_ & 63) n_plain = min(n_plain, N_ >> 6);
   if constexpr (CAUSAL) n_plain = min(n_plain, max(0, (q0 + 1) >> 6));  // tile j needs no mask iff 64*j+63 <= q0
-  const int n_fast = (abl::kAllGeneric || (CAN_MASK && p.mask)) ? 0 : max(0, min(n_plain - 1, wave_tiles - 1));  // attn_mask: all tiles generic
+  const int n_fast = (CAN_MASK && p.mask) ? 0 : max(0, min(n_plain - 1, wave_tiles - 1));  // attn_mask: all tiles generic
 
-  if constexpr (abl::kPrio >= 0) {  // static priority for the second-dispatched half of the workgroup: measured 0 %
-    if (wave >= NWAVES / 2) __builtin_amdgcn_s_setprio(abl::kPrio >= 0 ? abl::kPrio : 0);
-  }
   // tile copies a wave issues per iteration (full tiles): the unit of the counted waits of the four-slot ring
   constexpr int NDMA = KC + VC;
   static_assert(RING == 2 || (KC * T == 64 * KCH && VC * T == VROWS * VCH), "four-slot ring: every wave copies full shares");
@@ -706,16 +680,14 @@ void attn_i8_kernel(const AttnParams p) {
   } else {
   v16i s_cur[2], s_nxt[2];
   float sc0, sc1, mx_cur;
-  if constexpr (abl::kDelayWave) {  // mechanism probe: force the interleaving that the missing barrier below allowed
-    if (wave == 1) { __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127); }
-  }
   qk(0, s_cur);
   // Every wave reads ALL 64 rows of K buffer 0 for S(0) above, and iteration 0 below re-fills that buffer with K(2)
   // (each wave DMA-writes its own 1 KiB slice).  Later iterations are ordered by the barrier that closes the previous
   // one; this first re-fill needs its own: without it a wave that is held back between the prologue barrier and its
   // K(0) fragment reads (three waves per SIMD: the youngest wave can starve for longer than an L2 round trip) computes
-  // S(0) from a mix of K(0) and K(2) rows -- one wrong 32-row wave, the same wrong value every time.
-  if constexpr (!abl::kNoPrologueBarrier) __syncthreads();
+  // S(0) from a mix of K(0) and K(2) rows -- one wrong 32-row wave, the same wrong value every time
+  // (profiles/r02_race_evidence.md).
+  __syncthreads();
   tile_scales(0, sc0, sc1);
   // a plain tile 0 needs no mask (64 compare + select instructions per wave); the causal head_dim-64 variants keep it
   // unconditional -- under the branch they need 170 registers, two over the three-waves-per-SIMD line
@@ -729,7 +701,7 @@ void attn_i8_kernel(const AttnParams p) {
   //   0  a plain tile: the fast loops.  Ring slots are compile-time (R = j % RING), every LDS offset an immediate.
   //   1  a tile that may need masking (sequence end, causal diagonal), 2  nothing (the wave's last tile): the remaining
   //      tiles of a wave run through the SAME hand-placed stream with run-time ring slots (a few address adds) -- the
-  //      compiler-scheduled body they used before was 1.6x slower per tile, 5-7 % of a short causal sequence.
+  //      compiler-scheduled body is 1.6x slower per tile, 5-7 % of a short causal sequence.
   auto fast_iter = [&](auto par_tag, auto next_tag, const int j, v16i (&sa)[2], v16i (&sb)[2], float& a0, float& a1, float& b0,
                        float& b1) __attribute__((always_inline)) {
     constexpr int R = decltype(par_tag)::value;  // j % RING, static so every LDS offset is an immediate
@@ -764,26 +736,18 @@ void attn_i8_kernel(const AttnParams p) {
     if constexpr (NEXT != 2) {
       scales_from(kk_nxt, b0, b1);
       kk_nxt = load_kscales(min(j + 2, ntiles - 1));
-      if constexpr (!abl::kNoLdsK) kf_early = *reinterpret_cast<const v4i*>(k_rd[0] + (DYN ? 0 : K_RD * KBYTES));
+      kf_early = *reinterpret_cast<const v4i*>(k_rd[0] + (DYN ? 0 : K_RD * KBYTES));
     }
     __builtin_amdgcn_sched_barrier(0);
     maybe_rescale(mx_cur);
-    if constexpr (!abl::kNoStage) {
-      if constexpr (RING == 2) {
-        if (j + 2 < ntiles && !(abl::kHalfCopies && (j & 1))) dma_k(j + 2, K_WR);
-        if ((!DYN || j + 1 < ntiles) && !(abl::kHalfCopies && (j & 1))) load_v(j + 1, V_WR);
-      } else {
-        dma_k(min(j + RING, last_tile), K_WR);
-        load_v(min(j + RING - 1, last_tile), V_WR);
-      }
+    if constexpr (RING == 2) {
+      if (j + 2 < ntiles) dma_k(j + 2, K_WR);
+      if (!DYN || j + 1 < ntiles) load_v(j + 1, V_WR);
+    } else {
+      dma_k(min(j + RING, last_tile), K_WR);
+      load_v(min(j + RING - 1, last_tile), V_WR);
     }
-    constexpr int HAND_PLACED = PV_FP8 ? abl::kHandPlacedF8 : abl::kHandPlacedF16;
-    if constexpr (HAND_PLACED == 0) {
-      if constexpr (NEXT != 2) qk(DYN ? 0 : K_RD, sb);
-      if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(j + 1, sb); }
-      softmax_pv(j, DYN ? 0 : V_RD, sa, a0, a1, std::false_type{});
-      if constexpr (NEXT != 2) mx_cur = row_max(sb, b0, b1);
-    } else if constexpr (HAND_PLACED == 2) {
+    if constexpr (PV_FP8) {
       // Hand-placed stream, FP8 PV.  The K = 64 MFMA consumes the P of the whole tile, so all of P(j) precedes the P.V
       // MFMAs; left alone hipcc emits ~110 softmax VALU instructions with the matrix pipe idle and then the 12 MFMAs in
       // one cluster.  Here: the S(j+1) MFMAs are spread through the computation of the eight P words (4 keys each:
@@ -825,8 +789,7 @@ void attn_i8_kernel(const AttnParams p) {
         pb[w] = pk;
       };
       auto p_sum = [&]() __attribute__((always_inline)) {
-        psum += pend[0];
-        if constexpr (!abl::kNoRowSumF8) { psum += pend[1]; psum += pend[2]; psum += pend[3]; }
+        psum += pend[0]; psum += pend[1]; psum += pend[2]; psum += pend[3];
       };
 #define SAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
       v4i kf = kf_early;
@@ -884,25 +847,15 @@ void attn_i8_kernel(const AttnParams p) {
       const int kb = DYN ? 0 : K_RD * KBYTES, vb = DYN ? 0 : V_RD * VBYTES;  // slot offsets (DYN: the pointers were moved)
       const float c0 = __builtin_fmaf(-kBiasF, a0, kPOff - m_run), c1 = __builtin_fmaf(-kBiasF, a1, kPOff - m_run);
       auto k_frag = [&](const int i) __attribute__((always_inline)) -> v4i {
-        if constexpr (abl::kNoLdsK) return qf[i % KS];
-        else if constexpr (abl::kHalfReads) { if (i & 1) return qf[i % KS]; else return *reinterpret_cast<const v4i*>(k_rd[i % KS] + (kb + (i / KS) * 32 * D)); }
-        else if constexpr (abl::kConstOdd) {
-          const v4i f = *reinterpret_cast<const v4i*>(k_rd[i % KS] + (kb + (i / KS) * 32 * D));
-          if (i & 1) { asm volatile("" :: "v"(f)); return qf[i % KS]; }
-          return f;
-        }
-        else return *reinterpret_cast<const v4i*>(k_rd[i % KS] + (kb + (i / KS) * 32 * D));
+        return *reinterpret_cast<const v4i*>(k_rd[i % KS] + (kb + (i / KS) * 32 * D));
       };
       auto v_frag = [&](const int q, const int dt) __attribute__((always_inline)) -> v8h {
-        if constexpr (abl::kNoLdsV) return __builtin_bit_cast(v8h, qf[(q + dt) % KS]);
-        if constexpr (abl::kHalfReads) { if ((q + dt) & 1) return __builtin_bit_cast(v8h, qf[(q + dt) % KS]); }
         const char* base = v_rd[dt] + (vb + 16 * q * (2 * D));
         const v4s_vs lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_vs*)(base));
         const v4s_vs hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_vs*)(base + 8 * (2 * D)));
         v8h a;
         a.s0123 = __builtin_bit_cast(v4h, lo);
         a.s4567 = __builtin_bit_cast(v4h, hi);
-        if constexpr (abl::kConstOdd) { if ((q + dt) & 1) { asm volatile("" :: "v"(a)); return __builtin_bit_cast(v8h, qf[(q + dt) % KS]); } }
         return a;
       };
       auto s_step = [&](const int i, const v4i a) __attribute__((always_inline)) {
@@ -936,8 +889,7 @@ void attn_i8_kernel(const AttnParams p) {
 #define SAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
       v4i kf = kf_early;
       // head_dim 64: K fragments are read TWO S MFMAs ahead (two registers in flight; four S MFMAs per tile, one per region,
-      // so one-ahead left the read ~70 cycles).  Round 3, long windows, bit-identical: C2 +0.75 %, (4,32,8192,64) +0.8 %,
-      // C2-causal +0.3 %; head_dim 128 (eight S MFMAs, two per region): -0.3 % -> not there.
+      // so one-ahead left the read ~70 cycles): C2 +0.75 %; head_dim 128 (eight S MFMAs, two per region): -0.3 % -> not there.
       constexpr bool KPREF2 = D == 64;
       v4i kfq[2] = {kf_early, kf_early};
       if constexpr (KPREF2 && NEXT != 2) kfq[1] = k_frag(1);
@@ -1020,18 +972,16 @@ void attn_i8_kernel(const AttnParams p) {
     }
     // keep the cross-lane end of the row max (a dependent chain of ~8 instructions with hazard nops) in FRONT of the
     // tile's wait and barrier, where a wave idles anyway: hipcc sank it below the barrier in one of the two unrolled
-    // bodies, i.e. in front of the next tile's first MFMA (round 3, bit-identical: C3 +1.1 %, C3-causal +0.5 %, C2 +0.2 %)
+    // bodies, i.e. in front of the next tile's first MFMA (C3 +1.1 %)
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!abl::kNoStage) {
-      if constexpr (RING == 2) {
-        dma_wait_all();  // two-slot ring: every copy of this wave has landed before the barrier publishes the tiles
-      } else if constexpr (DYN) {
-        dma_wait_all();  // the last tiles of a wave drain every copy (the counts of the four-slot ring stay constant)
-      } else {
-        dma_wait_keep<2 * NDMA>();  // K(j+2), V(j+1) and everything older have landed; the last two iterations' copies fly on
-      }
+    if constexpr (RING == 2) {
+      dma_wait_all();  // two-slot ring: every copy of this wave has landed before the barrier publishes the tiles
+    } else if constexpr (DYN) {
+      dma_wait_all();  // the last tiles of a wave drain every copy (the counts of the four-slot ring stay constant)
+    } else {
+      dma_wait_keep<2 * NDMA>();  // K(j+2), V(j+1) and everything older have landed; the last two iterations' copies fly on
     }
-    if constexpr (!abl::kNoBar) __syncthreads();
+    __syncthreads();
   };
   float nsc0 = 0.f, nsc1 = 0.f;
   int j = 0;
@@ -1069,13 +1019,11 @@ void attn_i8_kernel(const AttnParams p) {
   }
   // an odd fast tile left (j is even here): one more fast iteration instead of a generic one (+11 % at C2, where the
   // generic body otherwise takes 2 of 32 tiles).
-  if constexpr (!abl::kNoOddFast) {
-    if (j < n_fast) {
-      fast_iter(std::integral_constant<int, 0>{}, kPlainNext, j, s_cur, s_nxt, sc0, sc1, nsc0, nsc1);
-      s_cur[0] = s_nxt[0]; s_cur[1] = s_nxt[1];
-      sc0 = nsc0; sc1 = nsc1;
-      ++j;
-    }
+  if (j < n_fast) {
+    fast_iter(std::integral_constant<int, 0>{}, kPlainNext, j, s_cur, s_nxt, sc0, sc1, nsc0, nsc1);
+    s_cur[0] = s_nxt[0]; s_cur[1] = s_nxt[1];
+    sc0 = nsc0; sc1 = nsc1;
+    ++j;
   }
   }
   {
@@ -1165,7 +1113,7 @@ void attn_i8_kernel(const AttnParams p) {
         }
         // o = round16(round32(acc * inv ...)): the fp32 value is made opaque, otherwise hipcc folds the last multiply and the
         // convert into v_fma_mixlo_f16 (one rounding) in SOME instantiations -- more exact by up to one fp16 ulp in ~5e-5 of
-        // the elements, but not the arithmetic of the reference epilogue (…sm80.cu:600-640) nor of this library's earlier builds
+        // the elements, but not the arithmetic of the reference epilogue (…sm80.cu:600-640)
 #pragma unroll
         for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(x[e]));
         uint2 w;  // packed converts (round to nearest even, as the scalar ones): v_cvt_pk_{f16,bf16}_f32
@@ -1219,43 +1167,45 @@ static bool allow_lds(const void* kern, size_t bytes) {
          hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-template <int D, int NWAVES, bool PV_FP8>
-static int launch_attn(const AttnParams& p, bool causal, bool kthread, bool v_bf16, hipStream_t st) {
-  if constexpr (!PV_FP8) {
-    if (p.mask) {  // attn_mask variant (non-causal, fp16 V: checked by run_attn)
-      const size_t smem_m = 2 * 64 * D + 2 * 64 * D * 2;
-      const dim3 grid_m(p.nqb * p.Hq * p.B), block_m(NWAVES * 64);
-#define SAGE_LAUNCH_MASKED(K, V)                                                                                   \
-  do {                                                                                                             \
-    auto kern = attn_i8_kernel<D, NWAVES, false, K, V, false, true>;                                                \
-    if (!allow_lds((const void*)kern, smem_m)) return SAGE_ERR_LAUNCH;                                             \
-    hipLaunchKernelGGL(kern, grid_m, block_m, smem_m, st, p);                                                      \
-  } while (0)
-      if (kthread) { if (v_bf16) SAGE_LAUNCH_MASKED(true, true); else SAGE_LAUNCH_MASKED(true, false); }
-      else { if (v_bf16) SAGE_LAUNCH_MASKED(false, true); else SAGE_LAUNCH_MASKED(false, false); }
-#undef SAGE_LAUNCH_MASKED
-      return launch_status();
-    }
-  }
-  const size_t smem = (size_t)attn_ring_slots(D, NWAVES, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));  // RING x (K tile + V tile)
-  const dim3 grid(p.nqb * p.Hq * p.B), block(NWAVES * 64);
-#define SAGE_LAUNCH(C, K, V)                                                                                       \
-  do {                                                                                                             \
-    auto kern = attn_i8_kernel<D, NWAVES, C, K, V, PV_FP8, false>;                                                      \
-    if (!allow_lds((const void*)kern, smem)) return SAGE_ERR_LAUNCH;                                                   \
-    hipLaunchKernelGGL(kern, grid, block, smem, st, p);                                                            \
-  } while (0)
-#define SAGE_BY_V(C, K)                                                                                            \
-  do {                                                                                                             \
-    if constexpr (PV_FP8) SAGE_LAUNCH(C, K, false);                                                                \
-    else { if (v_bf16) SAGE_LAUNCH(C, K, true); else SAGE_LAUNCH(C, K, false); }                                   \
-  } while (0)
-#define SAGE_BY_K(C) do { if (kthread) SAGE_BY_V(C, true); else SAGE_BY_V(C, false); } while (0)
-  if (causal) SAGE_BY_K(true); else SAGE_BY_K(false);
-#undef SAGE_BY_K
-#undef SAGE_BY_V
-#undef SAGE_LAUNCH
+// a run-time flag as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static int by_flag(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8, bool HAS_MASK>
+static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
+  auto kern = attn_i8_kernel<D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK>;
+  if (!allow_lds((const void*)kern, smem)) return SAGE_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, dim3(p.nqb * p.Hq * p.B), dim3(NWAVES * 64), smem, st, p);
   return launch_status();
+}
+
+template <int D, int NWAVES>
+static int launch_attn(const AttnParams& p, bool pv_fp8, bool causal, bool kthread, bool v_bf16, hipStream_t st) {
+  return by_flag(pv_fp8, [&](auto fp8) {
+    constexpr bool PV_FP8 = decltype(fp8)::value;
+    // V element type: fp8 V has no bf16 flavour
+    auto by_v = [&](auto f) { if constexpr (PV_FP8) return f(std::false_type{}); else return by_flag(v_bf16, f); };
+    if constexpr (!PV_FP8) {
+      if (p.mask) {  // attn_mask variant (non-causal, fp16 V: checked by run_attn)
+        const size_t smem = 2 * 64 * D + 2 * 64 * D * 2;
+        return by_flag(kthread, [&](auto k) {
+          return by_v([&](auto v) {
+            return launch_kernel<D, NWAVES, false, decltype(k)::value, decltype(v)::value, false, true>(p, smem, st);
+          });
+        });
+      }
+    }
+    const size_t smem = (size_t)attn_ring_slots(D, NWAVES, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));  // RING x (K tile + V tile)
+    return by_flag(causal, [&](auto c) {
+      return by_flag(kthread, [&](auto k) {
+        return by_v([&](auto v) {
+          return launch_kernel<D, NWAVES, decltype(c)::value, decltype(k)::value, decltype(v)::value, PV_FP8, false>(p, smem, st);
+        });
+      });
+    });
+  });
 }
 
 static bool t_ok(const sage_tensor* t, int align_elems) {
@@ -1267,16 +1217,31 @@ static bool t_ok(const sage_tensor* t, int align_elems) {
 // the launches of another thread; 0 = the measured default below
 static thread_local int g_nwaves_override = 0;
 
+// the inputs of run_attn that only some entry points have
+struct AttnOptions {
+  const int* cu_q = nullptr;  // packed sequences: cumulative query / key lengths
+  const int* cu_k = nullptr;
+  int q_dtype = -1;           // >= 0: q8 is the fp16 / bf16 query tensor, quantized in the kernel's prologue
+  const void* km = nullptr;   // fused Q: k_mean of the LSE correction
+  const void* mask = nullptr; // attn_mask, its kind and its four strides
+  int mask_kind = 0;
+  const int64_t* mask_strides = nullptr;
+  const sage_kv_layout* kvl = nullptr;  // tile-major K / V buffers
+};
 
-// shared argument handling of the two attention entry points
+// shared argument handling of the attention entry points
 static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
                     const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
                     const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
                     int blkq, int warpq, float sm_scale, int logit_mult_is_one, hipStream_t st,
-                    const int* cu_q = nullptr, const int* cu_k = nullptr, int q_dtype = -1, const void* km = nullptr,
-                    const void* mask = nullptr, int mask_kind = 0, const int64_t* mask_strides = nullptr,
-                    const sage_kv_layout* kvl = nullptr) {
-  if (mask && (mask_kind < 1 || mask_kind > 3 || !mask_strides || is_causal || pv_fp8 || cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
+                    const AttnOptions& opt = AttnOptions()) {
+  const int* const cu_q = opt.cu_q;
+  const int* const cu_k = opt.cu_k;
+  const int q_dtype = opt.q_dtype;
+  const void* const km = opt.km;
+  const void* const mask = opt.mask;
+  const sage_kv_layout* const kvl = opt.kvl;
+  if (mask && (opt.mask_kind < 1 || opt.mask_kind > 3 || !opt.mask_strides || is_causal || pv_fp8 || cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
   const bool fusedq = q_dtype >= 0;  // q8 is then the fp16/bf16 query tensor
   if ((cu_q == nullptr) != (cu_k == nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
   if (fusedq) {
@@ -1335,8 +1300,9 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   p.logit_mult = logit_mult_is_one ? 1.0f : sm_scale * kLog2e;
   p.out_bf16 = o_dtype == SAGE_BF16;
   p.cu_q = cu_q; p.cu_k = cu_k;
-  p.mask = (const uint8_t*)mask; p.mask_kind = mask ? mask_kind : 0;
-  p.msb = mask ? mask_strides[0] : 0; p.msh = mask ? mask_strides[1] : 0; p.msm = mask ? mask_strides[2] : 0; p.msn = mask ? mask_strides[3] : 0;
+  p.mask = (const uint8_t*)mask; p.mask_kind = mask ? opt.mask_kind : 0;
+  const int64_t* const ms = opt.mask_strides;
+  p.msb = mask ? ms[0] : 0; p.msh = mask ? ms[1] : 0; p.msm = mask ? ms[2] : 0; p.msn = mask ? ms[3] : 0;
   p.k_tile_bytes = (int)k_tile; p.v_tile_bytes = (int)v_tile; p.ks_b = ks_b; p.ks_h = ks_h; p.ks_t = (int)ks_t;
   p.kv_tiled = tiled ? 1 : 0;
   p.o_vec16 = (o->stride_b % 8 == 0 && o->stride_h % 8 == 0 && o->stride_n % 8 == 0) ? 1 : 0;  // 16-byte aligned output rows
@@ -1346,25 +1312,20 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   // measured on MI355X: D=128 fp16 PV -> one 8-wave workgroup per CU (4-wave: -3 %); D=128 fp8 PV -> two 4-wave
   // workgroups per CU (+3.6 % non-causal, +5.7 % causal); D=64 (<= 168 VGPRs) -> 4-wave workgroups, 3 per CU
   // ... except for short key sequences (few tiles per workgroup, so prologue and epilogue weigh more and two smaller
-  // workgroups per CU overlap them better).  Re-measured at the end of round 2 (the prologue now issues its tile copies
-  // first): 4-wave +10 % at 1024 keys, +7 % at 1536, +6 % at 2048, 0 % at 3072-4096, -2 % from 6144; causal (a row attends
-  // half the keys on average) +21 % at 2048, +13 % at 4096, 0 % at 8192, -1 % at 16384 -> 4 waves up to 2048 keys per row.
-  // Round 3, end to end with the Q quantizer in the prologue (tools/nw_e2e.py, profiles/r03_ab/geometry_end_to_end.log): the
-  // heavier prologue moves the crossover out -- 4-wave 0.959x the 8-wave time at 2048 keys, 0.979x at 3072, 0.998x at 4096,
-  // 1.02x from 6144; causal 0.993x at 8192 (4096 keys per row on average) -> 4 waves up to 3072 keys per row.
+  // workgroups per CU overlap them better): end to end, 4-wave 0.959x the 8-wave time at 2048 keys, 0.979x at 3072, 0.998x
+  // at 4096, 1.02x from 6144; causal 0.993x at 8192 (4096 keys per row on average) -> 4 waves up to 3072 keys per row
+  // (profiles/r03_ab/geometry_end_to_end.log).
   const int keys_per_row = is_causal ? N / 2 : N;
-  // FP8 PV at head_dim 128, end of round 3 (tools/ab_bench.py --pv fp8 lib@4 lib@8, non-causal): 4-wave workgroups +2.2 % at 8K
-  // keys, +0.7 % at 16K, -1.1 % at 32K, -1.3 % at 64K.  The two co-resident 4-wave workgroups of a CU drift apart on a long
-  // stream (the older one wins the issue arbitration) until they no longer share K/V tiles in L2: FETCH_SIZE of one rank's launch
-  // of the 64K-key gather schedule (8192 rows x 65536 keys) is 1.90x the algorithmic bytes with 4 waves and 1.00x with 8
-  // (profiles/r03_ab/fetch_by_geometry.md) -> 8 waves beyond 24K keys per row.
+  // FP8 PV at head_dim 128: 4-wave workgroups +2.2 % at 8K keys, +0.7 % at 16K, -1.1 % at 32K, -1.3 % at 64K.  The two
+  // co-resident 4-wave workgroups of a CU drift apart on a long stream until they no longer share K/V tiles in L2 (1.90x the
+  // algorithmic HBM-side bytes with 4 waves, 1.00x with 8: profiles/r03_ab/fetch_by_geometry.md) -> 8 waves beyond 24K keys per row.
   const int nw = g_nwaves_override ? g_nwaves_override
                                    : ((D == 64 || (pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
   p.nqb = (M + nw * 32 - 1) / (nw * 32);
-#define SAGE_GO(DD, NW) (pv_fp8 ? launch_attn<DD, NW, true>(p, is_causal, kthread, false, st) : launch_attn<DD, NW, false>(p, is_causal, kthread, vb, st))
-  if (nw == 8) return D == 64 ? SAGE_GO(64, 8) : SAGE_GO(128, 8);
-  return D == 64 ? SAGE_GO(64, 4) : SAGE_GO(128, 4);
-#undef SAGE_GO
+  if (nw == 8) return D == 64 ? launch_attn<64, 8>(p, pv_fp8, is_causal, kthread, vb, st)
+                              : launch_attn<128, 8>(p, pv_fp8, is_causal, kthread, vb, st);
+  return D == 64 ? launch_attn<64, 4>(p, pv_fp8, is_causal, kthread, vb, st)
+                 : launch_attn<128, 4>(p, pv_fp8, is_causal, kthread, vb, st);
 }
 
 }  // namespace sage
@@ -1410,9 +1371,12 @@ extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage
                                                int max_seqlen_q, int max_seqlen_k, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!cu_seqlens_q || !cu_seqlens_k) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.cu_q = cu_seqlens_q;
+  opt.cu_k = cu_seqlens_k;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, nullptr, num_seqs, Hq, Hk,
                   max_seqlen_q, max_seqlen_k, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one,
-                  (hipStream_t)stream, cu_seqlens_q, cu_seqlens_k);
+                  (hipStream_t)stream, opt);
 }
 
 extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1420,8 +1384,11 @@ extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const 
                                        const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                        int is_causal, int qk_gran, int warpq, float sm_scale, sage_stream_t stream) {
   if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.q_dtype = q_dtype;
+  opt.km = km;
   return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, nullptr, nullptr, q_dtype, km);
+                  qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, opt);
 }
 
 extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -1430,8 +1397,11 @@ extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const s
                                       int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                       sage_stream_t stream) {
   if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.q_dtype = q_dtype;
+  opt.km = km;
   return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, nullptr, nullptr, q_dtype, km);
+                  is_causal, qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1440,9 +1410,12 @@ extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage
                                                int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
                                                float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!attn_mask) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.mask = attn_mask;
+  opt.mask_kind = mask_kind;
+  opt.mask_strides = mask_strides;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, 0, qk_gran,
-                  blkq, warpq, sm_scale, logit_mult_is_one, (hipStream_t)stream, nullptr, nullptr, -1, nullptr, attn_mask,
-                  mask_kind, mask_strides);
+                  blkq, warpq, sm_scale, logit_mult_is_one, (hipStream_t)stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1451,9 +1424,10 @@ extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sag
                                                 int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                                 sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.kvl = kv_layout;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, nullptr, nullptr, -1, nullptr, nullptr, 0, nullptr,
-                  kv_layout);
+                  qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -1462,7 +1436,8 @@ extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage
                                                int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt;
+  opt.kvl = kv_layout;
   return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, nullptr, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, nullptr, nullptr, -1, nullptr, nullptr, 0,
-                  nullptr, kv_layout);
+                  is_causal, qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, opt);
 }

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void merge_many_kernel(const MergeMany m, uint
   // every lse and every o row of this thread is requested up front (slots unrolled; a slot past `count` repeats the last
   // one and is not used): as a run-time loop with the o load under `if (l != -inf)` each block cost two dependent round
   // trips -- hipcc sinks a load into the branch that uses it.  The uses below are selects, not branches, for that reason.
-  // The combination runs in slot order as before: deterministic, bit-identical.
+  // The combination runs in slot order: deterministic, bit-identical.
   float l[MAXC];
   uint4 raw[MAXC];
 #pragma unroll

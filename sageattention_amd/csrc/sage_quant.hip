@@ -13,10 +13,6 @@
 #include "sage_common.h"
 #include "sage_fp8_kernels.h"
 
-#ifndef SAGE_KV_UNITS_CAP  // blocks / units one workgroup of the streaming K + V quantizer walks at most (variant builds sweep it)
-#define SAGE_KV_UNITS_CAP 32
-#endif
-
 namespace sage {
 
 // ------------------------------------------------------------------------------------------------
@@ -25,8 +21,8 @@ namespace sage {
 constexpr int KMEAN_ROWS = 256;  // granule of the pass-1 chunks (rows)
 // Rows per pass-1 chunk: a multiple of KMEAN_ROWS chosen so that a sequence never has more than 16 chunks -- the quantizers
 // then ALWAYS finish the statistics themselves (16 partial rows per head out of L2), i.e. the K pre-pass is two launches
-// and the FP8 operator's K + V pre-pass is two launches at every length (round 3; up to 4096 rows the chunks are the 256
-// rows of rounds 1-2, so nothing changes there bit for bit; beyond, the partial sums are taken over longer chunks).
+// and the FP8 operator's K + V pre-pass is two launches at every length (up to 4096 rows the chunks are KMEAN_ROWS rows;
+// beyond, the partial sums are taken over longer chunks).
 __host__ __device__ __forceinline__ int kmean_chunk_rows(int N) {
   const int c256 = (N + KMEAN_ROWS - 1) / KMEAN_ROWS;
   return KMEAN_ROWS * ((c256 + 15) / 16 > 0 ? (c256 + 15) / 16 : 1);
@@ -546,11 +542,11 @@ __global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(const Qu
   v_quant_store_image<D>(q.out, q.ob, q.oh, q.od, q.o_tile, p.N, bx, h, b, tile);
 }
 
-// Launch B as a STREAMING kernel for long sequences (round 3; sage_kv_prepare_fp8 picks by the units a workgroup would walk): workgroups [0, nwg_k) walk per_k consecutive K blocks
+// Launch B as a STREAMING kernel for long sequences (sage_kv_prepare_fp8 picks by the units a workgroup would walk): workgroups [0, nwg_k) walk per_k consecutive K blocks
 // of their head (k_quant_stream_body), the others per_v consecutive V units (BLKS x 64 tokens), the next unit's rows
 // requested while this one is transposed, the image double-buffered in LDS (one barrier per unit), and the per-channel
 // scale -- S maxima and two IEEE divisions per channel -- finished ONCE per workgroup by its first token group instead of by
-// every thread for every unit (that was three quarters of the V half's vector work).  Same arithmetic: bit-identical.
+// every thread for every unit (three quarters of the V half's vector work otherwise).  Same arithmetic: bit-identical.
 template <int D, bool BF16, bool TRITON>
 __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(const QuantParams p, const VPrepParams q, const int per_k,
                                                                                const int nwg_k, const int per_v) {
@@ -854,8 +850,9 @@ extern "C" int sage_kv_prepare_fp8(const sage_tensor* k, const sage_tensor* v, i
   const int nunit_v = (nblk_k + vq_blks - 1) / vq_blks;
   // K blocks / V units per workgroup: each half gets about half of the workgroups the chip holds at once (k_quant_blocks_per_wg)
   const int64_t target = 128 * (D == 64 ? 5 : 4);
-  // (at most SAGE_KV_UNITS_CAP units per workgroup: beyond, more generations of workgroups measured better than longer walks)
-  auto per_wg = [&](int units) { int64_t per = ((int64_t)B * H * units + target - 1) / target; per = per > SAGE_KV_UNITS_CAP ? SAGE_KV_UNITS_CAP : per; return (int)(per < 1 ? 1 : per > units ? units : per); };
+  // (at most kUnitsCap units per workgroup: beyond, more generations of workgroups measured better than longer walks)
+  constexpr int64_t kUnitsCap = 32;
+  auto per_wg = [&](int units) { int64_t per = ((int64_t)B * H * units + target - 1) / target; per = per > kUnitsCap ? kUnitsCap : per; return (int)(per < 1 ? 1 : per > units ? units : per); };
   const int per_k = per_wg(nblk_k), per_v = per_wg(nunit_v);
   const int nwg_k = (nblk_k + per_k - 1) / per_k, nwg_v = (nunit_v + per_v - 1) / per_v;
   hipStream_t st = (hipStream_t)stream;

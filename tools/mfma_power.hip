@@ -1,6 +1,6 @@
 // Power-limited MFMA throughput by instruction shape (all CUs busy, random operands in registers, wall clock):
 // which shapes should the attention kernel use when the chip, not the schedule, sets the clock?
-//   hipcc --offload-arch=gfx950 -O2 tools/mfma_power.hip -o ab_libs/mfma_power && ab_libs/mfma_power
+//   hipcc --offload-arch=gfx950 -O2 tools/mfma_power.hip -o mfma_power && ./mfma_power
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
