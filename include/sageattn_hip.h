@@ -18,6 +18,8 @@
  *    keeps no state; work is enqueued on `stream` and never synchronised.
  *  - every function returns SAGE_OK (0) or a negative sage_status; nothing is printed, nothing
  *    aborts (the reference raises through TORCH_CHECK / std::invalid_argument, utils.cuh:20-38).
+ *  - a call that returns an argument status (SAGE_ERR_INVALID_ARGUMENT, _UNSUPPORTED_HEAD_DIM,
+ *    _UNSUPPORTED, _TOO_LARGE) has enqueued no work: every argument is checked before the first launch.
  */
 #ifndef SAGEATTN_HIP_H
 #define SAGEATTN_HIP_H

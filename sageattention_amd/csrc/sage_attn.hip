@@ -18,7 +18,7 @@
 //
 // Roofline: MFMA (4*M*N*D flop per (b,h); half int8 at 2x the fp16 rate), VALU/exp2 co-limited.
 // Algorithmic HBM bytes per (b,h): M*D (Q) + N*D (K) + 2*N*D (V fp16) + 2*M*D (O) + scales.
-#include "sage_attn_common.h"
+#include "sage_entry.h"
 
 namespace sage {
 
@@ -1167,12 +1167,6 @@ static bool allow_lds(const void* kern, size_t bytes) {
          hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
-// a run-time flag as a compile-time one: f(std::true_type{}) or f(std::false_type{})
-template <class F>
-static int by_flag(bool flag, F&& f) {
-  return flag ? f(std::true_type{}) : f(std::false_type{});
-}
-
 template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8, bool HAS_MASK>
 static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
   auto kern = attn_i8_kernel<D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK>;
@@ -1182,15 +1176,16 @@ static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
 }
 
 template <int D, int NWAVES>
-static int launch_attn(const AttnParams& p, bool pv_fp8, bool causal, bool kthread, bool v_bf16, hipStream_t st) {
-  return by_flag(pv_fp8, [&](auto fp8) {
+static int launch_attn(const AttnCall& c, hipStream_t st) {
+  const AttnParams& p = c.p;
+  return by_flag(c.pv_fp8, [&](auto fp8) {
     constexpr bool PV_FP8 = decltype(fp8)::value;
     // V element type: fp8 V has no bf16 flavour
-    auto by_v = [&](auto f) { if constexpr (PV_FP8) return f(std::false_type{}); else return by_flag(v_bf16, f); };
+    auto by_v = [&](auto f) { if constexpr (PV_FP8) return f(std::false_type{}); else return by_flag(c.v_bf16, f); };
     if constexpr (!PV_FP8) {
-      if (p.mask) {  // attn_mask variant (non-causal, fp16 V: checked by run_attn)
+      if (p.mask) {  // attn_mask variant (non-causal, fp16 V: checked by attn_check)
         const size_t smem = 2 * 64 * D + 2 * 64 * D * 2;
-        return by_flag(kthread, [&](auto k) {
+        return by_flag(c.kthread, [&](auto k) {
           return by_v([&](auto v) {
             return launch_kernel<D, NWAVES, false, decltype(k)::value, decltype(v)::value, false, true>(p, smem, st);
           });
@@ -1198,43 +1193,25 @@ static int launch_attn(const AttnParams& p, bool pv_fp8, bool causal, bool kthre
       }
     }
     const size_t smem = (size_t)attn_ring_slots(D, NWAVES, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));  // RING x (K tile + V tile)
-    return by_flag(causal, [&](auto c) {
-      return by_flag(kthread, [&](auto k) {
+    return by_flag(c.causal, [&](auto ca) {
+      return by_flag(c.kthread, [&](auto k) {
         return by_v([&](auto v) {
-          return launch_kernel<D, NWAVES, decltype(c)::value, decltype(k)::value, decltype(v)::value, PV_FP8, false>(p, smem, st);
+          return launch_kernel<D, NWAVES, decltype(ca)::value, decltype(k)::value, decltype(v)::value, PV_FP8, false>(p, smem, st);
         });
       });
     });
   });
 }
 
-static bool t_ok(const sage_tensor* t, int align_elems) {
-  return t && t->data && aligned16(t->data) && t->stride_b % align_elems == 0 && t->stride_h % align_elems == 0 &&
-         t->stride_n % align_elems == 0;
-}
-
 // tuning hook (sage_set_tuning): per host thread, so a test or tool that pins the geometry for its own calls cannot change
 // the launches of another thread; 0 = the measured default below
 static thread_local int g_nwaves_override = 0;
 
-// the inputs of run_attn that only some entry points have
-struct AttnOptions {
-  const int* cu_q = nullptr;  // packed sequences: cumulative query / key lengths
-  const int* cu_k = nullptr;
-  int q_dtype = -1;           // >= 0: q8 is the fp16 / bf16 query tensor, quantized in the kernel's prologue
-  const void* km = nullptr;   // fused Q: k_mean of the LSE correction
-  const void* mask = nullptr; // attn_mask, its kind and its four strides
-  int mask_kind = 0;
-  const int64_t* mask_strides = nullptr;
-  const sage_kv_layout* kvl = nullptr;  // tile-major K / V buffers
-};
-
-// shared argument handling of the attention entry points
-static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
-                    const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
-                    const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
-                    int blkq, int warpq, float sm_scale, int logit_mult_is_one, hipStream_t st,
-                    const AttnOptions& opt = AttnOptions()) {
+// argument checks of the attention entry points; fills the kernel parameters and the geometry
+int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
+               const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
+               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+               int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt) {
   const int* const cu_q = opt.cu_q;
   const int* const cu_k = opt.cu_k;
   const int q_dtype = opt.q_dtype;
@@ -1247,17 +1224,19 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   if (fusedq) {
     if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
     if (qk_gran == SAGE_GRAN_PER_BLOCK || cu_q || (km && !aligned16(km))) return SAGE_ERR_UNSUPPORTED;
-    if (!t_ok(q8, 8) || !k_scale) return SAGE_ERR_INVALID_ARGUMENT;
+    if (!tensor_ok(q8, 8) || !k_scale) return SAGE_ERR_INVALID_ARGUMENT;
     q_scale = k_scale;  // unused placeholder so the shared checks below pass
   }
   if (cu_q && (pv_fp8 || lse)) return SAGE_ERR_UNSUPPORTED;  // packed sequences: fp16 PV, no LSE (as the reference)
-  if (!t_ok(q8, fusedq ? 8 : 16) || !t_ok(k8, 16) || !t_ok(v, pv_fp8 ? 16 : 8) || !t_ok(o, 4) || !q_scale || !k_scale) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(q8, fusedq ? 8 : 16) || !tensor_ok(k8, 16) || !tensor_ok(v, pv_fp8 ? 16 : 8) || !tensor_ok(o, 4) || !q_scale ||
+      !k_scale)
+    return SAGE_ERR_INVALID_ARGUMENT;
   if (pv_fp8 && !v_scale) return SAGE_ERR_INVALID_ARGUMENT;
   if (B <= 0 || Hq <= 0 || Hk <= 0 || M <= 0 || N <= 0 || Hq % Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
   // the integer row max and the -inf mask pattern rely on a positive, finite dequantisation scale
   if (!logit_mult_is_one && !(sm_scale > 0.f && sm_scale < 1.0e30f)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if ((v_dtype != SAGE_F16 && v_dtype != SAGE_BF16) || (o_dtype != SAGE_F16 && o_dtype != SAGE_BF16)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, v_dtype)) return s;
+  if (o_dtype != SAGE_F16 && o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
   if (qk_gran < SAGE_GRAN_PER_BLOCK || qk_gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
   if (blkq != 64 && blkq != 128) return SAGE_ERR_INVALID_ARGUMENT;
   if (qk_gran == SAGE_GRAN_PER_BLOCK) warpq = blkq;
@@ -1285,7 +1264,7 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   if (ntile * k_tile + 64 * k8->stride_n + D >= lim) return SAGE_ERR_TOO_LARGE;
   if (pv_fp8 ? (ntile * v_tile + (int64_t)D * v->stride_n + 64 >= lim) : (ntile * v_tile + (64 * v->stride_n + D) * 2 >= lim)) return SAGE_ERR_TOO_LARGE;
   if (ks_t * ntile >= lim) return SAGE_ERR_TOO_LARGE;
-  AttnParams p;
+  AttnParams& p = c.p;
   p.q = (const int8_t*)q8->data; p.qsb = q8->stride_b; p.qsh = q8->stride_h; p.qsn = q8->stride_n;
   p.k = (const int8_t*)k8->data; p.ksb = k8->stride_b; p.ksh = k8->stride_h; p.ksn = k8->stride_n;
   p.v = (const uint8_t*)v->data; p.vsb = v->stride_b; p.vsh = v->stride_h; p.vsn = v->stride_n;
@@ -1308,7 +1287,6 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   p.o_vec16 = (o->stride_b % 8 == 0 && o->stride_h % 8 == 0 && o->stride_n % 8 == 0) ? 1 : 0;  // 16-byte aligned output rows
   p.q_f16 = fusedq ? (const uint16_t*)q8->data : nullptr;
   p.km = (const uint16_t*)km; p.q_bf16 = q_dtype == SAGE_BF16; p.sm_scale = sm_scale;
-  const bool kthread = qk_gran == SAGE_GRAN_PER_THREAD, vb = v_dtype == SAGE_BF16;
   // measured on MI355X: D=128 fp16 PV -> one 8-wave workgroup per CU (4-wave: -3 %); D=128 fp8 PV -> two 4-wave
   // workgroups per CU (+3.6 % non-causal, +5.7 % causal); D=64 (<= 168 VGPRs) -> 4-wave workgroups, 3 per CU
   // ... except for short key sequences (few tiles per workgroup, so prologue and epilogue weigh more and two smaller
@@ -1319,13 +1297,32 @@ static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_ten
   // FP8 PV at head_dim 128: 4-wave workgroups +2.2 % at 8K keys, +0.7 % at 16K, -1.1 % at 32K, -1.3 % at 64K.  The two
   // co-resident 4-wave workgroups of a CU drift apart on a long stream until they no longer share K/V tiles in L2 (1.90x the
   // algorithmic HBM-side bytes with 4 waves, 1.00x with 8: profiles/r03_ab/fetch_by_geometry.md) -> 8 waves beyond 24K keys per row.
-  const int nw = g_nwaves_override ? g_nwaves_override
-                                   : ((D == 64 || (pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
+  const int nw = opt.nwaves            ? opt.nwaves
+                 : g_nwaves_override ? g_nwaves_override
+                                     : ((D == 64 || (pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
   p.nqb = (M + nw * 32 - 1) / (nw * 32);
-  if (nw == 8) return D == 64 ? launch_attn<64, 8>(p, pv_fp8, is_causal, kthread, vb, st)
-                              : launch_attn<128, 8>(p, pv_fp8, is_causal, kthread, vb, st);
-  return D == 64 ? launch_attn<64, 4>(p, pv_fp8, is_causal, kthread, vb, st)
-                 : launch_attn<128, 4>(p, pv_fp8, is_causal, kthread, vb, st);
+  c.D = D; c.nwaves = nw;
+  c.pv_fp8 = pv_fp8; c.causal = is_causal != 0; c.kthread = qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = v_dtype == SAGE_BF16;
+  return SAGE_OK;
+}
+
+int attn_launch(const AttnCall& c, hipStream_t st) {
+  return by_dim(c.D, [&](auto d) {
+    return c.nwaves == 8 ? launch_attn<decltype(d)::value, 8>(c, st) : launch_attn<decltype(d)::value, 4>(c, st);
+  });
+}
+
+// the public entry points: check, then launch
+static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
+                    const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
+                    const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+                    int blkq, int warpq, float sm_scale, int logit_mult_is_one, sage_stream_t stream,
+                    const AttnOptions& opt = AttnOptions()) {
+  AttnCall c;
+  if (const int s = attn_check(c, q8, k8, v, pv_fp8, v_dtype, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M,
+                               N, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, opt))
+    return s;
+  return attn_launch(c, (hipStream_t)stream);
 }
 
 }  // namespace sage
@@ -1353,7 +1350,7 @@ extern "C" int sage_attn_qk_int8_pv_f16(const sage_tensor* q8, const sage_tensor
                                         int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                         int logit_mult_is_one, sage_stream_t stream) {
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, (hipStream_t)stream);
+                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -1362,7 +1359,7 @@ extern "C" int sage_attn_qk_int8_pv_f8(const sage_tensor* q8, const sage_tensor*
                                        int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                        int logit_mult_is_one, sage_stream_t stream) {
   return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, (hipStream_t)stream);
+                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1376,7 +1373,7 @@ extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage
   opt.cu_k = cu_seqlens_k;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, nullptr, num_seqs, Hq, Hk,
                   max_seqlen_q, max_seqlen_k, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one,
-                  (hipStream_t)stream, opt);
+                  stream, opt);
 }
 
 extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1388,7 +1385,7 @@ extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const 
   opt.q_dtype = q_dtype;
   opt.km = km;
   return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, opt);
+                  qk_gran, 128, warpq, sm_scale, 0, stream, opt);
 }
 
 extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -1401,7 +1398,7 @@ extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const s
   opt.q_dtype = q_dtype;
   opt.km = km;
   return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, 128, warpq, sm_scale, 0, (hipStream_t)stream, opt);
+                  is_causal, qk_gran, 128, warpq, sm_scale, 0, stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1415,7 +1412,7 @@ extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage
   opt.mask_kind = mask_kind;
   opt.mask_strides = mask_strides;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, 0, qk_gran,
-                  blkq, warpq, sm_scale, logit_mult_is_one, (hipStream_t)stream, opt);
+                  blkq, warpq, sm_scale, logit_mult_is_one, stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -1427,7 +1424,7 @@ extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sag
   AttnOptions opt;
   opt.kvl = kv_layout;
   return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, opt);
+                  qk_gran, blkq, warpq, sm_scale, 0, stream, opt);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -1439,5 +1436,5 @@ extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage
   AttnOptions opt;
   opt.kvl = kv_layout;
   return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, nullptr, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, 0, (hipStream_t)stream, opt);
+                  is_causal, qk_gran, blkq, warpq, sm_scale, 0, stream, opt);
 }

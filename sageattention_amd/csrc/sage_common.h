@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/sageattn_hip.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -87,5 +88,30 @@ __host__ inline int launch_status() {
 }
 
 __host__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// a [B,H,N,D] tensor argument: data present and 16-byte aligned, every stride a multiple of align_elems
+__host__ inline bool tensor_ok(const sage_tensor* t, int align_elems) {
+  return t && t->data && aligned16(t->data) && t->stride_b % align_elems == 0 && t->stride_h % align_elems == 0 &&
+         t->stride_n % align_elems == 0;
+}
+
+// head_dim, then the fp16 / bf16 dtype: the statuses of every entry point for them, in this order
+__host__ inline int dim_dtype_status(int D, int dtype) {
+  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
+  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  return SAGE_OK;
+}
+
+// a run-time flag as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+__host__ inline decltype(auto) by_flag(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// a checked head_dim as a compile-time one: f(std::integral_constant<int, 64>{}) or f(std::integral_constant<int, 128>{})
+template <class F>
+__host__ inline decltype(auto) by_dim(int D, F&& f) {
+  return D == 64 ? f(std::integral_constant<int, 64>{}) : f(std::integral_constant<int, 128>{});
+}
 
 }  // namespace sage

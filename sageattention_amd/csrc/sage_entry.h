@@ -1,0 +1,133 @@
+// The check and launch halves of the entry points that the one-call operators (sage_op.hip) chain.  Every C-ABI entry point
+// checks all its arguments and fills its kernel parameters, with no HIP call, before its first launch, and then launches
+// with no further check: a call that returns an argument status has enqueued nothing.  sage_op.hip checks every step of a
+// call with these functions before it launches the first step.
+#pragma once
+#include "sage_attn_common.h"  // AttnParams
+
+namespace sage {
+
+// ---- INT8 quantizer (sage_quant.hip) ----------------------------------------------------------------------------------
+struct QuantParams {
+  const uint16_t* x;
+  int64_t xsb, xsh, xsn;
+  const uint16_t* mean;  // [B,H,D] or null
+  int8_t* out;
+  int64_t osb, osh, osn;
+  float* scale;  // [B,H,G]
+  const uint16_t* dot_vec;  // [B,H/dot_group,D] or null
+  float* dot_out;           // [B,H,N]
+  int dot_group;
+  int N, G;          // rows, scales per (b,h)
+  int gran, is_key;  // sage_qk_gran, K-side grouping of per_thread
+  int warp;          // rows per warp group (16, 32, 64 or 128)
+  int warp_shift;    // log2(warp): the group maps run per row and must not cost an integer division
+  float mult;
+  int rounding;
+  const int* cu;  // varlen: sequence b = rows [cu[b], cu[b+1]) of the packed tensor (stride_b unused); N = max length
+  // result layout: rows of block `blk` start at blk * o_blk (elements; dense: BLK * osn); scales of (b, h, blk) at
+  // b*ss_b + h*ss_h + blk*ss_blk (floats; dense: [B,H,G])
+  int64_t o_blk, ss_b, ss_h, ss_blk;
+  // mean given as the per-chunk column sums of k_mean_partial_kernel ([B*H][S][D] fp32) instead of `mean`: the kernel
+  // finishes the reduction itself (S <= 16: a few KB per workgroup out of L2) and block 0 stores km -- one launch less
+  const float* mean_part;
+  int S;
+  uint16_t* km_out;
+};
+
+// V half of the fused K/V pre-pass (sage_quant.hip, kv_quant_kernel / kv_quant_stream_kernel)
+struct VPrepParams {
+  const uint16_t* v;
+  int64_t sb, sh, sn;
+  uint8_t* out;
+  int64_t ob, oh, od, o_tile;
+  float* v_scale;      // [B,H,D]
+  const float* part;   // [B,H,S,D] max|v| per chunk
+  float scale_max;
+};
+
+// the inputs of quant_check that only some entry points have
+struct QuantOptions {
+  const int* cu = nullptr;                 // packed sequences (sage_quant_qk_int8_varlen)
+  int64_t out_blk_stride = 0;              // tile-major output (sage_quant_k_int8_kvtiles): elements between 64-row blocks,
+  const int64_t* scale_strides = nullptr;  // and the scale strides per batch, head and block; 0 / null = dense
+  const float* mean_part = nullptr;        // the mean as S chunk sums of k, finished by the quantizer, which stores it to km_out
+  int S = 0;
+  void* km_out = nullptr;
+};
+
+// one launch of quant_qk_int8_kernel
+struct QuantCall {
+  QuantParams p;
+  int B, H, D, blk;
+  bool bf16;
+};
+int quant_check(QuantCall& c, const sage_tensor* x, int dtype, int B, int H, int N, int D, const void* mean,
+                const sage_tensor* out, float* scale, int gran, int is_key, int blk, int warp, float mult, int rounding,
+                const void* lse_dot_vec, int dot_group, float* lse_dot, const QuantOptions& opt = QuantOptions());
+int quant_launch(const QuantCall& c, hipStream_t st);
+
+// sage_k_smooth_quant: chunk sums of k into the workspace (q.p.mean_part), then the streaming quantizer
+struct KSmoothCall {
+  QuantCall q;
+  sage_tensor k;
+  float* part;
+  int per_wg;  // 64-row blocks per workgroup of the quantizer
+};
+int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
+                         float* scale, void* km, int gran, int rounding, void* workspace);
+int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st);
+
+// sage_kv_prepare_fp8: K and V chunk statistics, then both quantizers in one launch
+struct KVPrepCall {
+  QuantCall k;
+  VPrepParams v;
+  float* kpart;
+  float* vpart;
+  int nblk_k, nunit_v;  // K blocks, V units (VQuantGeom<D>::BLKS blocks each)
+  int per_k, per_v;     // ... per workgroup of the streaming kernel
+  bool streaming;       // kv_quant_stream_kernel, else kv_quant_kernel (one block / unit per workgroup)
+};
+int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                     const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding, const sage_tensor* v_fp8,
+                     float* v_scale, float scale_max, void* workspace);
+int kv_prepare_launch(const KVPrepCall& c, hipStream_t st);
+
+// ---- attention (sage_attn.hip) ----------------------------------------------------------------------------------------
+// the inputs of attn_check that only some entry points have
+struct AttnOptions {
+  const int* cu_q = nullptr;  // packed sequences: cumulative query / key lengths
+  const int* cu_k = nullptr;
+  int q_dtype = -1;           // >= 0: q8 is the fp16 / bf16 query tensor, quantized in the kernel's prologue
+  const void* km = nullptr;   // fused Q: k_mean of the LSE correction
+  const void* mask = nullptr; // attn_mask, its kind and its four strides
+  int mask_kind = 0;
+  const int64_t* mask_strides = nullptr;
+  const sage_kv_layout* kvl = nullptr;  // tile-major K / V buffers
+  int nwaves = 0;             // waves per workgroup (4 or 8); 0 = the thread's SAGE_TUNE_NWAVES if set, else the measured choice
+};
+
+// one launch of attn_i8_kernel: its parameters and the template arguments they select
+struct AttnCall {
+  AttnParams p;
+  int D, nwaves;
+  bool pv_fp8, causal, kthread, v_bf16;
+};
+int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
+               const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
+               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+               int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt = AttnOptions());
+int attn_launch(const AttnCall& c, hipStream_t st);
+
+// ---- sage_finish_lse (sage_misc.hip) ------------------------------------------------------------------------------------
+struct FinishLseCall {
+  const float* lse2;
+  const float* corr;
+  float sm_scale;
+  float* out;
+  int64_t n;
+};
+int finish_lse_check(FinishLseCall& c, const float* lse2, const float* corr, float sm_scale, float* lse_out, int64_t n);
+int finish_lse_launch(const FinishLseCall& c, hipStream_t st);
+
+}  // namespace sage

@@ -168,33 +168,45 @@ extern "C" size_t sage_quant_v_fp8_workspace_bytes(int B, int H, int N, int D) {
   return ((size_t)B * H * S * 3 * D + (size_t)B * H * 2 * D) * sizeof(float);
 }
 
+// pass 1 of x [B,H,N,D] into part (S chunks of VQ_ROWS rows)
+static void launch_v_stats_partial(const sage_tensor* x, bool bf16, int B, int H, int N, int D, float* part, int S,
+                                   hipStream_t st) {
+  by_dim(D, [&](auto d) {
+    by_flag(bf16, [&](auto bf) {
+      hipLaunchKernelGGL((v_stats_partial_kernel<decltype(d)::value, decltype(bf)::value>), dim3(S, H, B), dim3(256), 0, st,
+                         (const uint16_t*)x->data, x->stride_b, x->stride_h, x->stride_n, N, part, S);
+    });
+  });
+}
+
+// pass 2: v -> v_fp8 with the coefficients coef [B,H,2,D]; 64-token block t at t * o_tile bytes
+static void launch_v_quant_transpose(const sage_tensor* v, bool bf16, int B, int H, int N, int D, const float* coef,
+                                     const sage_tensor* v_fp8, int64_t o_tile, hipStream_t st) {
+  by_dim(D, [&](auto d) {
+    by_flag(bf16, [&](auto bf) {
+      constexpr int DD = decltype(d)::value, BLKS = VQuantGeom<DD>::BLKS;  // 64-token blocks per workgroup
+      hipLaunchKernelGGL((v_quant_transpose_kernel<DD, decltype(bf)::value>), dim3(((N + 63) / 64 + BLKS - 1) / BLKS, H, B),
+                         dim3(256), 0, st, (const uint16_t*)v->data, v->stride_b, v->stride_h, v->stride_n, N, coef,
+                         (uint8_t*)v_fp8->data, v_fp8->stride_b, v_fp8->stride_h, v_fp8->stride_n, o_tile);
+    });
+  });
+}
+
 extern "C" int sage_quant_v_fp8(const sage_tensor* v, int dtype, int B, int H, int N, int D, const sage_tensor* v_fp8,
                                 float* v_scale, float* v_mean, float scale_max, void* workspace, sage_stream_t stream) {
-  if (!v || !v->data || !aligned16(v->data) || v->stride_b % 8 || v->stride_h % 8 || v->stride_n % 8) return SAGE_ERR_INVALID_ARGUMENT;
-  if (!v_fp8 || !v_fp8->data || !aligned16(v_fp8->data) || v_fp8->stride_b % 16 || v_fp8->stride_h % 16 || v_fp8->stride_n % 16)
-    return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v, 8) || !tensor_ok(v_fp8, 16)) return SAGE_ERR_INVALID_ARGUMENT;
   if (!v_scale || !workspace || B <= 0 || H <= 0 || N <= 0 || !(scale_max > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
   const int S = (N + VQ_ROWS - 1) / VQ_ROWS;
   float* part = (float*)workspace;
   float* coef = part + (size_t)B * H * S * 3 * D;
+  const bool bf16 = dtype == SAGE_BF16;
   hipStream_t st = (hipStream_t)stream;
   launch_begin();
-  const uint16_t* vp = (const uint16_t*)v->data;
-  const int vq_blks = D == 128 ? 1 : 2;  // 64-token blocks per workgroup of v_quant_transpose_kernel
-  const dim3 g1(S, H, B), g2(((N + 63) / 64 + vq_blks - 1) / vq_blks, H, B);
-#define L1(DD, BF) hipLaunchKernelGGL((v_stats_partial_kernel<DD, BF>), g1, dim3(256), 0, st, vp, v->stride_b, v->stride_h, v->stride_n, N, part, S)
-#define L2(DD, BF)                                                                                                    \
-  hipLaunchKernelGGL((v_quant_transpose_kernel<DD, BF>), g2, dim3(256), 0, st, vp, v->stride_b, v->stride_h, v->stride_n, N, \
-                     coef, (uint8_t*)v_fp8->data, v_fp8->stride_b, v_fp8->stride_h, v_fp8->stride_n, (int64_t)64)
-  const bool bf = dtype == SAGE_BF16;
-  if (D == 64) { if (bf) L1(64, true); else L1(64, false); } else { if (bf) L1(128, true); else L1(128, false); }
+  launch_v_stats_partial(v, bf16, B, H, N, D, part, S, st);
   hipLaunchKernelGGL(v_stats_final_kernel, dim3(B * H), dim3(128), 0, st, part, S, D, N, scale_max, v_mean ? 1 : 0, v_scale,
                      v_mean, coef);
-  if (D == 64) { if (bf) L2(64, true); else L2(64, false); } else { if (bf) L2(128, true); else L2(128, false); }
-#undef L1
-#undef L2
+  launch_v_quant_transpose(v, bf16, B, H, N, D, coef, v_fp8, 64, st);
   return launch_status();
 }
 
@@ -205,22 +217,15 @@ extern "C" size_t sage_seq_stats_workspace_bytes(int B, int H, int N, int D) {
 
 extern "C" int sage_seq_stats(const sage_tensor* x, int dtype, int B, int H, int N, int D, float* stats, void* workspace,
                               sage_stream_t stream) {
-  if (!x || !x->data || !aligned16(x->data) || x->stride_b % 8 || x->stride_h % 8 || x->stride_n % 8) return SAGE_ERR_INVALID_ARGUMENT;
-  if (!stats || !workspace || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(x, 8) || !stats || !workspace || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
   const int S = (N + VQ_ROWS - 1) / VQ_ROWS;
   float* part = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   launch_begin();
-  const uint16_t* xp = (const uint16_t*)x->data;
-  const dim3 g1(S, H, B);
   // rows in [N, ceil16(N)) would count as zeros in v_stats_partial_kernel (the reference's padded amax, fused.cu:335):
   // harmless for max|x| and for the sum
-#define L1(DD, BF) hipLaunchKernelGGL((v_stats_partial_kernel<DD, BF>), g1, dim3(256), 0, st, xp, x->stride_b, x->stride_h, x->stride_n, N, part, S)
-  const bool bf = dtype == SAGE_BF16;
-  if (D == 64) { if (bf) L1(64, true); else L1(64, false); } else { if (bf) L1(128, true); else L1(128, false); }
-#undef L1
+  launch_v_stats_partial(x, dtype == SAGE_BF16, B, H, N, D, part, S, st);
   hipLaunchKernelGGL(seq_stats_final_kernel, dim3(B * H), dim3(128), 0, st, part, S, D, stats);
   return launch_status();
 }
@@ -230,37 +235,22 @@ extern "C" int sage_kv_stats_reduce(const float* k_stats, const float* v_stats, 
   if ((!k_stats && !v_stats) || parts <= 0 || BH <= 0 || n_total <= 0 || part_stride < (int64_t)BH * 3 * D) return SAGE_ERR_INVALID_ARGUMENT;
   if ((k_stats != nullptr) != (km != nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
   if (v_stats && (!v_scale || !v_coef || !(scale_max > 0.f))) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
   launch_begin();
-  if (dtype == SAGE_BF16)
-    hipLaunchKernelGGL((kv_stats_reduce_kernel<true>), dim3(BH), dim3(128), 0, (hipStream_t)stream, k_stats, v_stats, parts, part_stride, BH,
-                       D, (float)n_total, scale_max, (uint16_t*)km, v_scale, v_coef);
-  else
-    hipLaunchKernelGGL((kv_stats_reduce_kernel<false>), dim3(BH), dim3(128), 0, (hipStream_t)stream, k_stats, v_stats, parts, part_stride, BH,
-                       D, (float)n_total, scale_max, (uint16_t*)km, v_scale, v_coef);
+  by_flag(dtype == SAGE_BF16, [&](auto bf) {
+    hipLaunchKernelGGL((kv_stats_reduce_kernel<decltype(bf)::value>), dim3(BH), dim3(128), 0, (hipStream_t)stream, k_stats,
+                       v_stats, parts, part_stride, BH, D, (float)n_total, scale_max, (uint16_t*)km, v_scale, v_coef);
+  });
   return launch_status();
 }
 
 extern "C" int sage_quant_v_fp8_apply(const sage_tensor* v, int dtype, int B, int H, int N, int D, const sage_tensor* v_fp8,
                                       int64_t out_tile_stride, const float* v_coef, sage_stream_t stream) {
-  if (!v || !v->data || !aligned16(v->data) || v->stride_b % 8 || v->stride_h % 8 || v->stride_n % 8) return SAGE_ERR_INVALID_ARGUMENT;
-  if (!v_fp8 || !v_fp8->data || !aligned16(v_fp8->data) || v_fp8->stride_b % 16 || v_fp8->stride_h % 16 || v_fp8->stride_n % 16)
-    return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v, 8) || !tensor_ok(v_fp8, 16)) return SAGE_ERR_INVALID_ARGUMENT;
   if (!v_coef || B <= 0 || H <= 0 || N <= 0 || out_tile_stride < 0 || (out_tile_stride & 15)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  const int64_t o_tile = out_tile_stride ? out_tile_stride : 64;
-  hipStream_t st = (hipStream_t)stream;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
   launch_begin();
-  const uint16_t* vp = (const uint16_t*)v->data;
-  const int vq_blks = D == 128 ? 1 : 2;
-  const dim3 g2(((N + 63) / 64 + vq_blks - 1) / vq_blks, H, B);
-#define L2(DD, BF)                                                                                                    \
-  hipLaunchKernelGGL((v_quant_transpose_kernel<DD, BF>), g2, dim3(256), 0, st, vp, v->stride_b, v->stride_h, v->stride_n, N, \
-                     v_coef, (uint8_t*)v_fp8->data, v_fp8->stride_b, v_fp8->stride_h, v_fp8->stride_n, o_tile)
-  const bool bf = dtype == SAGE_BF16;
-  if (D == 64) { if (bf) L2(64, true); else L2(64, false); } else { if (bf) L2(128, true); else L2(128, false); }
-#undef L2
+  launch_v_quant_transpose(v, dtype == SAGE_BF16, B, H, N, D, v_coef, v_fp8, out_tile_stride ? out_tile_stride : 64,
+                           (hipStream_t)stream);
   return launch_status();
 }

@@ -1,6 +1,6 @@
 // Small helpers of the hot path: library info, LSE finishing (core.py:651) and the ring-attention
 // state merge (new component; rule in SURVEY.md section 5).  Elementwise, HBM-bound.
-#include "sage_common.h"
+#include "sage_entry.h"
 
 namespace sage {
 
@@ -96,6 +96,19 @@ __global__ __launch_bounds__(256) void finish_lse_kernel(const float* __restrict
   out[i] = v;
 }
 
+int finish_lse_check(FinishLseCall& c, const float* lse2, const float* corr, float sm_scale, float* lse_out, int64_t n) {
+  if (!lse2 || !lse_out || n <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  c = FinishLseCall{lse2, corr, sm_scale, lse_out, n};
+  return SAGE_OK;
+}
+
+int finish_lse_launch(const FinishLseCall& c, hipStream_t st) {
+  launch_begin();
+  hipLaunchKernelGGL(finish_lse_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, st, c.lse2, c.corr, c.sm_scale,
+                     c.out, c.n);
+  return launch_status();
+}
+
 }  // namespace sage
 
 using namespace sage;
@@ -117,16 +130,23 @@ extern "C" const char* sage_status_string(int status) {
 extern "C" int sage_merge_attn_states(float* o_acc, float* lse_acc, const void* o_blk, int o_dtype, const float* lse_blk,
                                       int64_t rows, int D, sage_stream_t stream) {
   if (!o_acc || !lse_acc || !o_blk || !lse_blk || rows <= 0 || !aligned16(o_acc) || !aligned16(o_blk)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (o_dtype != SAGE_F16 && o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, o_dtype)) return s;
   const int64_t threads = rows * (D / 8);
-  const dim3 grid((unsigned)((threads + 255) / 256));
   launch_begin();
-  if (o_dtype == SAGE_BF16)
-    hipLaunchKernelGGL((merge_states_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, o_acc, lse_acc, (const uint16_t*)o_blk, lse_blk, rows, D);
-  else
-    hipLaunchKernelGGL((merge_states_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, o_acc, lse_acc, (const uint16_t*)o_blk, lse_blk, rows, D);
+  by_flag(o_dtype == SAGE_BF16, [&](auto bf) {
+    hipLaunchKernelGGL((merge_states_kernel<decltype(bf)::value>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, o_acc, lse_acc, (const uint16_t*)o_blk, lse_blk, rows, D);
+  });
   return launch_status();
+}
+
+// merge_many_kernel's slot count as a compile-time constant: the first of 2, 4, 8, 16 that holds `count`
+template <class F>
+static void by_slots(int count, F&& f) {
+  if (count <= 2) f(std::integral_constant<int, 2>{});
+  else if (count <= 4) f(std::integral_constant<int, 4>{});
+  else if (count <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
 }
 
 extern "C" int sage_merge_attn_states_multi_ex(const void* const* o_blks, const float* const* lse_blks, int count, int o_dtype,
@@ -134,8 +154,7 @@ extern "C" int sage_merge_attn_states_multi_ex(const void* const* o_blks, const 
                                                const float* corr, float corr_mult, sage_stream_t stream) {
   if (!(lse_in_mult > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
   if (!o_blks || !lse_blks || !o_out || count <= 0 || count > SAGE_MERGE_MAX || rows <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (o_dtype != SAGE_F16 && o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, o_dtype)) return s;
   MergeMany m;
   m.count = count;
   for (int i = 0; i < count; ++i) {
@@ -146,18 +165,13 @@ extern "C" int sage_merge_attn_states_multi_ex(const void* const* o_blks, const 
   for (int i = count; i < SAGE_MERGE_MAX; ++i) { m.o[i] = nullptr; m.lse[i] = nullptr; }
   if (!aligned16(o_out)) return SAGE_ERR_INVALID_ARGUMENT;
   const int64_t threads = rows * (D / 8);
-  const dim3 grid((unsigned)((threads + 255) / 256));
   launch_begin();
-#define LAUNCH(BF, MC)                                                                                                  \
-  hipLaunchKernelGGL((merge_many_kernel<BF, MC>), grid, dim3(256), 0, (hipStream_t)stream, m, (uint16_t*)o_out, lse_out, rows, D, \
-                     lse_in_mult, corr, corr_mult)
-#define BY_COUNT(BF)                                                                                                    \
-  do {                                                                                                                  \
-    if (count <= 2) LAUNCH(BF, 2); else if (count <= 4) LAUNCH(BF, 4); else if (count <= 8) LAUNCH(BF, 8); else LAUNCH(BF, 16); \
-  } while (0)
-  if (o_dtype == SAGE_BF16) BY_COUNT(true); else BY_COUNT(false);
-#undef BY_COUNT
-#undef LAUNCH
+  by_flag(o_dtype == SAGE_BF16, [&](auto bf) {
+    by_slots(count, [&](auto slots) {
+      hipLaunchKernelGGL((merge_many_kernel<decltype(bf)::value, decltype(slots)::value>), dim3((unsigned)((threads + 255) / 256)),
+                         dim3(256), 0, (hipStream_t)stream, m, (uint16_t*)o_out, lse_out, rows, D, lse_in_mult, corr, corr_mult);
+    });
+  });
   return launch_status();
 }
 
@@ -168,8 +182,7 @@ extern "C" int sage_merge_attn_states_multi(const void* const* o_blks, const flo
 
 extern "C" int sage_finish_lse(const float* lse2, const float* corr, float sm_scale, float* lse_out, int64_t n,
                                sage_stream_t stream) {
-  if (!lse2 || !lse_out || n <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  launch_begin();
-  hipLaunchKernelGGL(finish_lse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lse2, corr, sm_scale, lse_out, n);
-  return launch_status();
+  FinishLseCall c;
+  if (const int s = finish_lse_check(c, lse2, corr, sm_scale, lse_out, n)) return s;
+  return finish_lse_launch(c, (hipStream_t)stream);
 }

@@ -1,10 +1,11 @@
 // One-call operators: everything sageattn_qk_int8_pv_fp16_cuda / sageattn_qk_int8_pv_fp8_cuda do below their argument
 // checks (core.py:604-651, 786-905) behind ONE C-ABI crossing and ONE caller-provided workspace -- K mean + INT8 K
 // (sage_k_smooth_quant / sage_kv_prepare_fp8), FP8 V, Q quantizer (folded into the attention kernel's prologue unless
-// fuse_q = 0), attention, LSE fix.  Host code only: it sequences the library's own entry points on the caller's stream, so the
-// results are bit-identical to calling them one by one (what the Python mirror did until round 3: 3-4 crossings and 6-9
-// allocations per call, 46 us of host time against a 64 us GPU step at (4,32,1024,64)).
-#include "sage_common.h"
+// fuse_q = 0), attention, LSE fix.  Host code only: it checks every step with the entry points' own checks (sage_entry.h)
+// and then launches them on the caller's stream, so the results are bit-identical to calling them one by one (what the
+// Python mirror did until round 3: 3-4 crossings and 6-9 allocations per call, 46 us of host time against a 64 us GPU step
+// at (4,32,1024,64)).
+#include "sage_entry.h"
 
 namespace {
 
@@ -56,8 +57,7 @@ int run(int pv_fp8, const sage_tensor* q, const sage_tensor* k, const sage_tenso
         int B, int Hq, int Hk, int M, int N, int D, int is_causal, float sm_scale, float scale_max, const sage_op_opts* opts,
         void* workspace, size_t workspace_bytes, sage_stream_t stream) {
   if (!q || !k || !v || !o || !opts || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = sage::dim_dtype_status(D, dtype)) return s;
   if (Hk <= 0 || Hq % Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (!opts->smooth_k) return SAGE_ERR_UNSUPPORTED;  // the un-smoothed variant goes through the separate entry points
   if (opts->nwaves != 0 && opts->nwaves != 4 && opts->nwaves != 8) return SAGE_ERR_INVALID_ARGUMENT;
@@ -73,40 +73,49 @@ int run(int pv_fp8, const sage_tensor* q, const sage_tensor* k, const sage_tenso
   const sage_tensor k8{ws + pl.k8, (int64_t)Hk * N * D, (int64_t)N * D, D};
   float* const ks = reinterpret_cast<float*>(ws + pl.ks);
   void* const km = ws + pl.km;
-  int st;
   sage_tensor v8{nullptr, 0, 0, 0};
   float* v_scale = nullptr;
+  // every step is checked before the first launch: K (+ V) pre-pass, Q quantizer (fuse_q = 0), attention, LSE fix
+  sage::KSmoothCall kc;
+  sage::KVPrepCall kvc;
+  int st;
   if (pv_fp8) {
     v8 = sage_tensor{ws + pl.v8, (int64_t)Hk * D * pl.npad, (int64_t)D * pl.npad, pl.npad};
     v_scale = reinterpret_cast<float*>(ws + pl.v_scale);
-    st = sage_kv_prepare_fp8(k, v, dtype, B, Hk, N, D, &k8, ks, km, k_gran, rounding, &v8, v_scale, scale_max, ws + pl.pre_ws, stream);
+    st = sage::kv_prepare_check(kvc, k, v, dtype, B, Hk, N, D, &k8, ks, km, k_gran, rounding, &v8, v_scale, scale_max,
+                                ws + pl.pre_ws);
   } else {
-    st = sage_k_smooth_quant(k, dtype, B, Hk, N, D, &k8, ks, km, k_gran, rounding, ws + pl.pre_ws, stream);
+    st = sage::k_smooth_quant_check(kc, k, dtype, B, Hk, N, D, &k8, ks, km, k_gran, rounding, ws + pl.pre_ws);
   }
   if (st != SAGE_OK) return st;
-  // per-call workgroup geometry: the calling thread's tuning value is set for this call's launches and restored
-  const int prev_nw = sage_get_tuning(SAGE_TUNE_NWAVES);
-  if (opts->nwaves) sage_set_tuning(SAGE_TUNE_NWAVES, opts->nwaves);
+  sage::AttnOptions ao;
+  ao.nwaves = opts->nwaves;
+  sage::AttnCall ac;
+  sage::QuantCall qc;
+  sage::FinishLseCall fc;
   if (pl.fuse_q) {
-    st = pv_fp8 ? sage_attn_fusedq_pv_f8(q, dtype, &k8, &v8, o, dtype, ks, km, v_scale, nullptr, lse, B, Hq, Hk, M, N, D, is_causal,
-                                         gran, warpq, sm_scale, stream)
-                : sage_attn_fusedq_pv_f16(q, dtype, &k8, v, dtype, o, dtype, ks, km, nullptr, lse, B, Hq, Hk, M, N, D, is_causal,
-                                          gran, warpq, sm_scale, stream);
+    ao.q_dtype = dtype;
+    ao.km = km;
+    st = sage::attn_check(ac, q, &k8, pv_fp8 ? &v8 : v, pv_fp8, pv_fp8 ? SAGE_F16 : dtype, o, dtype, nullptr, ks, v_scale, nullptr,
+                          lse, B, Hq, Hk, M, N, D, is_causal, gran, 128, warpq, sm_scale, 0, ao);
   } else {
     const sage_tensor q8{ws + pl.q8, (int64_t)Hq * M * D, (int64_t)M * D, D};
     float* const qs = reinterpret_cast<float*>(ws + pl.qs);
     float* const corr = lse ? reinterpret_cast<float*>(ws + pl.corr) : nullptr;
     float* const lse2 = lse ? reinterpret_cast<float*>(ws + pl.lse2) : nullptr;
-    st = sage_quant_qk_int8(q, dtype, B, Hq, M, D, nullptr, &q8, qs, gran, 0, 128, warpq, 1.0f, rounding, lse ? km : nullptr,
-                            Hq / Hk, corr, stream);
+    st = sage::quant_check(qc, q, dtype, B, Hq, M, D, nullptr, &q8, qs, gran, 0, 128, warpq, 1.0f, rounding, lse ? km : nullptr,
+                           Hq / Hk, corr);
     if (st == SAGE_OK)
-      st = pv_fp8 ? sage_attn_qk_int8_pv_f8(&q8, &k8, &v8, o, dtype, qs, ks, v_scale, nullptr, lse2, B, Hq, Hk, M, N, D, is_causal,
-                                            gran, 128, warpq, sm_scale, 0, stream)
-                  : sage_attn_qk_int8_pv_f16(&q8, &k8, v, dtype, o, dtype, qs, ks, nullptr, lse2, B, Hq, Hk, M, N, D, is_causal,
-                                             gran, 128, warpq, sm_scale, 0, stream);
-    if (st == SAGE_OK && lse) st = sage_finish_lse(lse2, corr, sm_scale, lse, (int64_t)B * Hq * M, stream);
+      st = sage::attn_check(ac, &q8, &k8, pv_fp8 ? &v8 : v, pv_fp8, pv_fp8 ? SAGE_F16 : dtype, o, dtype, qs, ks, v_scale, nullptr,
+                            lse2, B, Hq, Hk, M, N, D, is_causal, gran, 128, warpq, sm_scale, 0, ao);
+    if (st == SAGE_OK && lse) st = sage::finish_lse_check(fc, lse2, corr, sm_scale, lse, (int64_t)B * Hq * M);
   }
-  if (opts->nwaves) sage_set_tuning(SAGE_TUNE_NWAVES, prev_nw);
+  if (st != SAGE_OK) return st;
+  const hipStream_t s = (hipStream_t)stream;
+  st = pv_fp8 ? sage::kv_prepare_launch(kvc, s) : sage::k_smooth_quant_launch(kc, s);
+  if (st == SAGE_OK && !pl.fuse_q) st = sage::quant_launch(qc, s);
+  if (st == SAGE_OK) st = sage::attn_launch(ac, s);
+  if (st == SAGE_OK && !pl.fuse_q && lse) st = sage::finish_lse_launch(fc, s);
   return st;
 }
 

@@ -9,8 +9,7 @@
 // Roofline: HBM. Algorithmic traffic per element: 2 B read + 1 B written (K1), 2 B read (K0).
 // Every thread moves 16 B per load (8 fp16/bf16), the widest coalesced access on CDNA4.
 // Compiled with -ffp-contract=off: the integer outputs must match the oracle bit for bit.
-#include <type_traits>
-#include "sage_common.h"
+#include "sage_entry.h"
 #include "sage_fp8_kernels.h"
 
 namespace sage {
@@ -103,32 +102,7 @@ __global__ void k_mean_final_kernel(const float* __restrict__ part, int S, int D
 // ------------------------------------------------------------------------------------------------
 // K1: INT8 quantizer, all granularities
 // ------------------------------------------------------------------------------------------------
-struct QuantParams {
-  const uint16_t* x;
-  int64_t xsb, xsh, xsn;
-  const uint16_t* mean;  // [B,H,D] or null
-  int8_t* out;
-  int64_t osb, osh, osn;
-  float* scale;  // [B,H,G]
-  const uint16_t* dot_vec;  // [B,H/dot_group,D] or null
-  float* dot_out;           // [B,H,N]
-  int dot_group;
-  int N, G;          // rows, scales per (b,h)
-  int gran, is_key;  // sage_qk_gran, K-side grouping of per_thread
-  int warp;          // rows per warp group (16, 32, 64 or 128)
-  int warp_shift;    // log2(warp): the group maps run per row and must not cost an integer division
-  float mult;
-  int rounding;
-  const int* cu;  // varlen: sequence b = rows [cu[b], cu[b+1]) of the packed tensor (stride_b unused); N = max length
-  // result layout: rows of block `blk` start at blk * o_blk (elements; dense: BLK * osn); scales of (b, h, blk) at
-  // b*ss_b + h*ss_h + blk*ss_blk (floats; dense: [B,H,G])
-  int64_t o_blk, ss_b, ss_h, ss_blk;
-  // mean given as the per-chunk column sums of k_mean_partial_kernel ([B*H][S][D] fp32) instead of `mean`: the kernel
-  // finishes the reduction itself (S <= 16: a few KB per workgroup out of L2) and block 0 stores km -- one launch less
-  const float* mean_part;
-  int S;
-  uint16_t* km_out;
-};
+// (QuantParams, the kernels' parameter block: sage_entry.h)
 
 // max over the TPR (8 or 16) consecutive lanes that hold one row, on DPP (quad swaps, then the mirrored half rows / rows): every
 // lane ends with the row's maximum; 3-4 v_max_f32_dpp instead of as many ds_bpermute round trips.  (A maximum does not depend
@@ -432,15 +406,7 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kernel(co
 // Without V smoothing only max|v| is needed, which does not depend on the order of the reduction: bit-identical to
 // sage_k_smooth_quant + sage_quant_v_fp8(v_mean = null).
 // ------------------------------------------------------------------------------------------------
-struct VPrepParams {
-  const uint16_t* v;
-  int64_t sb, sh, sn;
-  uint8_t* out;
-  int64_t ob, oh, od, o_tile;
-  float* v_scale;      // [B,H,D]
-  const float* part;   // [B,H,S,D] max|v| per chunk
-  float scale_max;
-};
+// (VPrepParams, the V half's parameter block: sage_entry.h)
 
 template <int D, bool BF16>
 __device__ __forceinline__ void v_amax_partial_body(const uint16_t* __restrict__ v, int64_t sb, int64_t sh, int64_t sn, int N,
@@ -631,9 +597,188 @@ __global__ __launch_bounds__(256) void sub_mean_f16_kernel(const uint16_t* __res
   *reinterpret_cast<uint4*>(out + b * ob + h * oh + (int64_t)row * on + tc * 8) = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-static bool tensor_ok(const sage_tensor* t, int align_elems) {
-  return t && t->data && aligned16(t->data) && t->stride_b % align_elems == 0 && t->stride_h % align_elems == 0 &&
-         t->stride_n % align_elems == 0;
+// ---- host side (sage_entry.h): checks that fill the parameters, then the launches -----------------------------------------
+
+// chunks of pass 1 (kmean_chunk_rows): at most 16
+static int kmean_chunks(int N) {
+  const int rows = kmean_chunk_rows(N);
+  return (N + rows - 1) / rows;
+}
+
+// Units (64-row K blocks, V units) per workgroup of a streaming quantizer: as many as leave about `target` workgroups for
+// all B*H heads, at most `cap`, and at least one.
+static int units_per_wg(int64_t BH, int units, int64_t target, int64_t cap) {
+  int64_t per = (BH * units + target - 1) / target;
+  per = per > cap ? cap : per;
+  return (int)(per < 1 ? 1 : per > units ? units : per);
+}
+
+static void launch_k_mean_partial(const sage_tensor& k, int B, int H, int N, int D, bool bf16, float* part, int S,
+                                  hipStream_t st) {
+  by_dim(D, [&](auto d) {
+    by_flag(bf16, [&](auto bf) {
+      hipLaunchKernelGGL((k_mean_partial_kernel<decltype(d)::value, decltype(bf)::value>), dim3(S, H, B), dim3(256), 0, st,
+                         (const uint16_t*)k.data, k.stride_b, k.stride_h, k.stride_n, N, part, S);
+    });
+  });
+}
+
+int quant_check(QuantCall& c, const sage_tensor* x, int dtype, int B, int H, int N, int D, const void* mean,
+                const sage_tensor* out, float* scale, int gran, int is_key, int blk, int warp, float mult, int rounding,
+                const void* lse_dot_vec, int dot_group, float* lse_dot, const QuantOptions& opt) {
+  if (!tensor_ok(x, 8) || !tensor_ok(out, 8) || !scale || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
+  if (gran < SAGE_GRAN_PER_BLOCK || gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
+  if (rounding != SAGE_ROUND_TRITON && rounding != SAGE_ROUND_CUDA) return SAGE_ERR_INVALID_ARGUMENT;
+  if (blk != 64 && blk != 128) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran == SAGE_GRAN_PER_BLOCK) warp = blk;
+  if ((warp != 16 && warp != 32 && warp != 64 && warp != 128) || blk % warp != 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (mean && !aligned16(mean)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (opt.mean_part && (opt.S < 1 || opt.S > 16 || !aligned16(opt.mean_part))) return SAGE_ERR_INVALID_ARGUMENT;  // mpart[16][D] in the kernel
+  if ((lse_dot_vec != nullptr) != (lse_dot != nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (lse_dot_vec && (dot_group <= 0 || H % dot_group != 0 || !aligned16(lse_dot_vec))) return SAGE_ERR_INVALID_ARGUMENT;
+  const int nblk = (N + blk - 1) / blk;
+  const int gpb = gran == SAGE_GRAN_PER_BLOCK ? 1 : gran == SAGE_GRAN_PER_WARP ? blk / warp : (blk / warp) * (is_key ? 4 : 8);
+  if (gpb > 64) return SAGE_ERR_INVALID_ARGUMENT;
+  QuantParams& p = c.p;
+  p.x = (const uint16_t*)x->data; p.xsb = x->stride_b; p.xsh = x->stride_h; p.xsn = x->stride_n;
+  p.mean = (const uint16_t*)mean;
+  p.out = (int8_t*)out->data; p.osb = out->stride_b; p.osh = out->stride_h; p.osn = out->stride_n;
+  p.scale = scale; p.dot_vec = (const uint16_t*)lse_dot_vec; p.dot_out = lse_dot; p.dot_group = dot_group > 0 ? dot_group : 1;
+  p.cu = opt.cu;
+  p.mean_part = opt.mean_part; p.S = opt.S; p.km_out = (uint16_t*)opt.km_out;
+  p.o_blk = opt.out_blk_stride ? opt.out_blk_stride : (int64_t)blk * out->stride_n;
+  p.ss_b = opt.scale_strides ? opt.scale_strides[0] : (int64_t)H * nblk * gpb;
+  p.ss_h = opt.scale_strides ? opt.scale_strides[1] : (int64_t)nblk * gpb;
+  p.ss_blk = opt.scale_strides ? opt.scale_strides[2] : gpb;
+  if (opt.out_blk_stride < 0 || (opt.out_blk_stride & 7) || p.ss_blk < gpb) return SAGE_ERR_INVALID_ARGUMENT;
+  p.N = N; p.G = nblk * gpb; p.gran = gran; p.is_key = is_key ? 1 : 0; p.warp = warp; p.mult = mult; p.rounding = rounding;
+  p.warp_shift = warp == 16 ? 4 : warp == 32 ? 5 : warp == 64 ? 6 : 7;
+  c.B = B; c.H = H; c.D = D; c.blk = blk; c.bf16 = dtype == SAGE_BF16;
+  return SAGE_OK;
+}
+
+int quant_launch(const QuantCall& c, hipStream_t st) {
+  const dim3 grid((c.p.N + c.blk - 1) / c.blk, c.H, c.B);
+  launch_begin();
+  by_dim(c.D, [&](auto d) {
+    by_flag(c.blk == 128, [&](auto b128) {
+      by_flag(c.bf16, [&](auto bf) {
+        by_flag(c.p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+          constexpr int BLK = decltype(b128)::value ? 128 : 64;
+          hipLaunchKernelGGL((quant_qk_int8_kernel<decltype(d)::value, BLK, decltype(bf)::value, decltype(tr)::value>), grid,
+                             dim3(256), 0, st, c.p);
+        });
+      });
+    });
+  });
+  return launch_status();
+}
+
+int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
+                         float* scale, void* km, int gran, int rounding, void* workspace) {
+  if (!km || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(k, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
+  QuantOptions opt;
+  opt.mean_part = c.part = (float*)workspace;
+  opt.S = kmean_chunks(N);
+  opt.km_out = km;
+  if (const int s = quant_check(c.q, k, dtype, B, H, N, D, nullptr, out, scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1,
+                                nullptr, opt))
+    return s;
+  c.k = *k;
+  // as many blocks per workgroup as leave about as many workgroups per CU as the quantizer's registers allow to be resident
+  // (five at head_dim 64, four at 128), so that every workgroup is resident from the start and streams its share of a head
+  const int nblk = (N + 63) / 64;
+  c.per_wg = units_per_wg((int64_t)B * H, nblk, 256 * (D == 64 ? 5 : 4), nblk);
+  return SAGE_OK;
+}
+
+int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
+  const QuantParams& p = c.q.p;
+  launch_begin();
+  launch_k_mean_partial(c.k, c.q.B, c.q.H, p.N, c.q.D, c.q.bf16, c.part, p.S, st);
+  if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
+  const int nblk = (p.N + 63) / 64;
+  const dim3 grid((nblk + c.per_wg - 1) / c.per_wg, c.q.H, c.q.B);
+  launch_begin();
+  by_dim(c.q.D, [&](auto d) {
+    by_flag(c.q.bf16, [&](auto bf) {
+      by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        hipLaunchKernelGGL((k_quant_stream_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value>), grid,
+                           dim3(256), 0, st, p, c.per_wg);
+      });
+    });
+  });
+  return launch_status();
+}
+
+int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                     const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding, const sage_tensor* v_fp8,
+                     float* v_scale, float scale_max, void* workspace) {
+  if (!km || !workspace || !v_scale || !(scale_max > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(k, 8) || !tensor_ok(v, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v_fp8, 16)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
+  const int S = kmean_chunks(N);
+  c.kpart = (float*)workspace;
+  c.vpart = c.kpart + (size_t)B * H * S * D;
+  QuantOptions opt;
+  opt.mean_part = c.kpart;
+  opt.S = S;
+  opt.km_out = km;
+  if (const int s = quant_check(c.k, k, dtype, B, H, N, D, nullptr, k_int8, k_scale, gran, 1, 64, 64, 1.0f, rounding, nullptr,
+                                1, nullptr, opt))
+    return s;
+  VPrepParams& q = c.v;
+  q.v = (const uint16_t*)v->data; q.sb = v->stride_b; q.sh = v->stride_h; q.sn = v->stride_n;
+  q.out = (uint8_t*)v_fp8->data; q.ob = v_fp8->stride_b; q.oh = v_fp8->stride_h; q.od = v_fp8->stride_n; q.o_tile = 64;
+  q.v_scale = v_scale; q.part = c.vpart; q.scale_max = scale_max;
+  c.nblk_k = (N + 63) / 64;
+  const int blks = by_dim(D, [](auto d) { return VQuantGeom<decltype(d)::value>::BLKS; });
+  c.nunit_v = (c.nblk_k + blks - 1) / blks;
+  // each half gets about half of the workgroups the chip holds at once (as sage_k_smooth_quant), with at most 32 units per
+  // workgroup: beyond, more generations of workgroups measured better than longer walks
+  const int64_t target = 128 * (D == 64 ? 5 : 4), cap = 32;
+  c.per_k = units_per_wg((int64_t)B * H, c.nblk_k, target, cap);
+  c.per_v = units_per_wg((int64_t)B * H, c.nunit_v, target, cap);
+  // Streaming pays where a workgroup walks enough units to hide its start-up (measured, tools/prepass_ab.py, B*H = 128: head_dim
+  // 128: 4-8 units per workgroup +6..10 % slower than one unit per workgroup, 16-32 units 6-12 % faster, 64 even; head_dim 64:
+  // 2 units slower, 4 faster); below that the one-unit-per-workgroup kernel (seven or eight workgroups per CU) runs.
+  c.streaming = c.per_v >= (D == 64 ? 4 : 12);
+  return SAGE_OK;
+}
+
+int kv_prepare_launch(const KVPrepCall& c, hipStream_t st) {
+  const QuantParams& p = c.k.p;
+  const VPrepParams& q = c.v;
+  const int B = c.k.B, H = c.k.H;
+  launch_begin();
+  by_dim(c.k.D, [&](auto d) {
+    by_flag(c.k.bf16, [&](auto bf) {
+      hipLaunchKernelGGL((kv_partial_kernel<decltype(d)::value, decltype(bf)::value>), dim3(2 * p.S, H, B), dim3(256), 0, st,
+                         p.x, p.xsb, p.xsh, p.xsn, q.v, q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, p.S);
+    });
+  });
+  if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
+  const int nwg_k = (c.nblk_k + c.per_k - 1) / c.per_k, nwg_v = (c.nunit_v + c.per_v - 1) / c.per_v;
+  by_dim(c.k.D, [&](auto d) {
+    by_flag(c.k.bf16, [&](auto bf) {
+      by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        constexpr int DD = decltype(d)::value;
+        constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value;
+        if (c.streaming)
+          hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, TR>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q, c.per_k,
+                             nwg_k, c.per_v);
+        else
+          hipLaunchKernelGGL((kv_quant_kernel<DD, BF, TR>), dim3(c.nblk_k + c.nunit_v, H, B), dim3(256), 0, st, p, q, c.nblk_k);
+      });
+    });
+  });
+  return launch_status();
 }
 
 }  // namespace sage
@@ -648,75 +793,15 @@ extern "C" size_t sage_k_mean_workspace_bytes(int B, int H, int N, int D) {
 extern "C" int sage_k_mean(const sage_tensor* k, int dtype, int B, int H, int N, int D, void* km, void* workspace,
                            sage_stream_t stream) {
   if (!tensor_ok(k, 8) || !km || !workspace || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  const int rows = kmean_chunk_rows(N), S = (N + rows - 1) / rows;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
+  const int S = kmean_chunks(N);
+  float* const ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   launch_begin();
-  dim3 grid(S, H, B);
-  const uint16_t* kp = (const uint16_t*)k->data;
-  float* ws = (float*)workspace;
-#define LAUNCH(DD, BF)                                                                                         \
-  hipLaunchKernelGGL((k_mean_partial_kernel<DD, BF>), grid, dim3(256), 0, st, kp, k->stride_b, k->stride_h, \
-                     k->stride_n, N, ws, S)
-  if (D == 64) { if (dtype == SAGE_BF16) LAUNCH(64, true); else LAUNCH(64, false); }
-  else { if (dtype == SAGE_BF16) LAUNCH(128, true); else LAUNCH(128, false); }
-#undef LAUNCH
-  if (dtype == SAGE_BF16)
-    hipLaunchKernelGGL((k_mean_final_kernel<true>), dim3(B * H), dim3(128), 0, st, ws, S, D, N, (uint16_t*)km);
-  else
-    hipLaunchKernelGGL((k_mean_final_kernel<false>), dim3(B * H), dim3(128), 0, st, ws, S, D, N, (uint16_t*)km);
-  return launch_status();
-}
-
-static int quant_impl(const sage_tensor* x, int dtype, int B, int H, int N, int D, const void* mean,
-                      const sage_tensor* out, float* scale, int gran, int is_key, int blk, int warp,
-                      float mult, int rounding, const void* lse_dot_vec, int dot_group, float* lse_dot,
-                      sage_stream_t stream, const int* cu, int64_t out_blk_stride = 0, const int64_t* scale_strides = nullptr,
-                      const float* mean_part = nullptr, int S = 0, void* km_out = nullptr, QuantParams* params_only = nullptr) {
-  if (!tensor_ok(x, 8) || !tensor_ok(out, 8) || !scale || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  if (gran < SAGE_GRAN_PER_BLOCK || gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
-  if (rounding != SAGE_ROUND_TRITON && rounding != SAGE_ROUND_CUDA) return SAGE_ERR_INVALID_ARGUMENT;
-  if (blk != 64 && blk != 128) return SAGE_ERR_INVALID_ARGUMENT;
-  if (gran == SAGE_GRAN_PER_BLOCK) warp = blk;
-  if ((warp != 16 && warp != 32 && warp != 64 && warp != 128) || blk % warp != 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (mean && !aligned16(mean)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (mean_part && (S < 1 || S > 16 || !aligned16(mean_part))) return SAGE_ERR_INVALID_ARGUMENT;  // mpart[16][D] in the kernel
-  if ((lse_dot_vec != nullptr) != (lse_dot != nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (lse_dot_vec && (dot_group <= 0 || H % dot_group != 0 || !aligned16(lse_dot_vec))) return SAGE_ERR_INVALID_ARGUMENT;
-  const int nblk = (N + blk - 1) / blk;
-  const int gpb = gran == SAGE_GRAN_PER_BLOCK ? 1 : gran == SAGE_GRAN_PER_WARP ? blk / warp : (blk / warp) * (is_key ? 4 : 8);
-  if (gpb > 64) return SAGE_ERR_INVALID_ARGUMENT;
-  QuantParams p;
-  p.x = (const uint16_t*)x->data; p.xsb = x->stride_b; p.xsh = x->stride_h; p.xsn = x->stride_n;
-  p.mean = (const uint16_t*)mean;
-  p.out = (int8_t*)out->data; p.osb = out->stride_b; p.osh = out->stride_h; p.osn = out->stride_n;
-  p.scale = scale; p.dot_vec = (const uint16_t*)lse_dot_vec; p.dot_out = lse_dot; p.dot_group = dot_group > 0 ? dot_group : 1;
-  p.cu = cu;
-  p.mean_part = mean_part; p.S = S; p.km_out = (uint16_t*)km_out;
-  p.o_blk = out_blk_stride ? out_blk_stride : (int64_t)blk * out->stride_n;
-  p.ss_b = scale_strides ? scale_strides[0] : (int64_t)H * nblk * gpb;
-  p.ss_h = scale_strides ? scale_strides[1] : (int64_t)nblk * gpb;
-  p.ss_blk = scale_strides ? scale_strides[2] : gpb;
-  if (out_blk_stride < 0 || (out_blk_stride & 7) || p.ss_blk < gpb) return SAGE_ERR_INVALID_ARGUMENT;
-  p.N = N; p.G = nblk * gpb; p.gran = gran; p.is_key = is_key ? 1 : 0; p.warp = warp; p.mult = mult; p.rounding = rounding;
-  p.warp_shift = warp == 16 ? 4 : warp == 32 ? 5 : warp == 64 ? 6 : 7;
-  if (params_only) { *params_only = p; return SAGE_OK; }  // validated parameters for a fused launch (sage_kv_prepare_fp8)
-  dim3 grid(nblk, H, B);
-  hipStream_t st = (hipStream_t)stream;
-  launch_begin();
-#define LAUNCH(DD, BL, BF)                                                                                              \
-  do {                                                                                                                  \
-    if (rounding == SAGE_ROUND_TRITON) hipLaunchKernelGGL((quant_qk_int8_kernel<DD, BL, BF, true>), grid, dim3(256), 0, st, p);  \
-    else hipLaunchKernelGGL((quant_qk_int8_kernel<DD, BL, BF, false>), grid, dim3(256), 0, st, p);                      \
-  } while (0)
-#define BY_DT(DD, BL) do { if (dtype == SAGE_BF16) LAUNCH(DD, BL, true); else LAUNCH(DD, BL, false); } while (0)
-  if (D == 64) { if (blk == 64) BY_DT(64, 64); else BY_DT(64, 128); }
-  else { if (blk == 64) BY_DT(128, 64); else BY_DT(128, 128); }
-#undef BY_DT
-#undef LAUNCH
+  launch_k_mean_partial(*k, B, H, N, D, dtype == SAGE_BF16, ws, S, st);
+  by_flag(dtype == SAGE_BF16, [&](auto bf) {
+    hipLaunchKernelGGL((k_mean_final_kernel<decltype(bf)::value>), dim3(B * H), dim3(128), 0, st, ws, S, D, N, (uint16_t*)km);
+  });
   return launch_status();
 }
 
@@ -724,8 +809,11 @@ extern "C" int sage_quant_qk_int8(const sage_tensor* x, int dtype, int B, int H,
                                   const sage_tensor* out, float* scale, int gran, int is_key, int blk, int warp,
                                   float mult, int rounding, const void* lse_dot_vec, int dot_group, float* lse_dot,
                                   sage_stream_t stream) {
-  return quant_impl(x, dtype, B, H, N, D, mean, out, scale, gran, is_key, blk, warp, mult, rounding, lse_dot_vec, dot_group,
-                    lse_dot, stream, nullptr);
+  QuantCall c;
+  if (const int s = quant_check(c, x, dtype, B, H, N, D, mean, out, scale, gran, is_key, blk, warp, mult, rounding,
+                                lse_dot_vec, dot_group, lse_dot))
+    return s;
+  return quant_launch(c, (hipStream_t)stream);
 }
 
 extern "C" int sage_quant_qk_int8_varlen(const sage_tensor* x, int dtype, const int* cu_seqlens, int num_seqs, int H,
@@ -733,25 +821,27 @@ extern "C" int sage_quant_qk_int8_varlen(const sage_tensor* x, int dtype, const 
                                          int gran, int is_key, int blk, int warp, float mult, int rounding,
                                          sage_stream_t stream) {
   if (!cu_seqlens) return SAGE_ERR_INVALID_ARGUMENT;
-  return quant_impl(x, dtype, num_seqs, H, max_seqlen, D, mean, out, scale, gran, is_key, blk, warp, mult, rounding, nullptr,
-                    1, nullptr, stream, cu_seqlens);
+  QuantOptions opt;
+  opt.cu = cu_seqlens;
+  QuantCall c;
+  if (const int s = quant_check(c, x, dtype, num_seqs, H, max_seqlen, D, mean, out, scale, gran, is_key, blk, warp, mult,
+                                rounding, nullptr, 1, nullptr, opt))
+    return s;
+  return quant_launch(c, (hipStream_t)stream);
 }
 
 extern "C" int sage_sub_mean_f16(const sage_tensor* v, int dtype, int B, int H, int N, int D, const void* vm,
                                  const sage_tensor* out, sage_stream_t stream) {
   if (!tensor_ok(v, 8) || !tensor_ok(out, 8) || !vm || !aligned16(vm) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
   const int RPP = 256 / (D / 8);
-  dim3 grid((N + RPP - 1) / RPP, H, B);
-  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((N + RPP - 1) / RPP, H, B);
   launch_begin();
-  if (dtype == SAGE_BF16)
-    hipLaunchKernelGGL((sub_mean_f16_kernel<true>), grid, dim3(256), 0, st, (const uint16_t*)v->data, v->stride_b, v->stride_h,
-                       v->stride_n, (const uint16_t*)vm, (uint16_t*)out->data, out->stride_b, out->stride_h, out->stride_n, N, D);
-  else
-    hipLaunchKernelGGL((sub_mean_f16_kernel<false>), grid, dim3(256), 0, st, (const uint16_t*)v->data, v->stride_b, v->stride_h,
-                       v->stride_n, (const uint16_t*)vm, (uint16_t*)out->data, out->stride_b, out->stride_h, out->stride_n, N, D);
+  by_flag(dtype == SAGE_BF16, [&](auto bf) {
+    hipLaunchKernelGGL((sub_mean_f16_kernel<decltype(bf)::value>), grid, dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)v->data, v->stride_b, v->stride_h, v->stride_n, (const uint16_t*)vm,
+                       (uint16_t*)out->data, out->stride_b, out->stride_h, out->stride_n, N, D);
+  });
   return launch_status();
 }
 
@@ -760,32 +850,14 @@ extern "C" int sage_quant_k_int8_kvtiles(const sage_tensor* k, int dtype, int B,
                                          const int64_t* scale_strides, int gran, int rounding, sage_stream_t stream) {
   if (!scale_strides || out_tile_stride <= 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
-  return quant_impl(k, dtype, B, H, N, D, mean, out, scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1, nullptr, stream, nullptr,
-                    out_tile_stride, scale_strides);
-}
-
-// Blocks per workgroup of the streaming K quantizer: as many as leave about as many workgroups per CU as its registers allow
-// to be resident (five at head_dim 64, four at 128), so that every workgroup is resident from the start and streams its share
-// of a head.
-static int k_quant_blocks_per_wg(int B, int H, int N, int D) {
-  const int64_t nblk = (N + 63) / 64, total = (int64_t)B * H * nblk, target = 256 * (D == 64 ? 5 : 4);
-  const int64_t per = (total + target - 1) / target;
-  return (int)(per < 1 ? 1 : per > nblk ? nblk : per);
-}
-
-static int launch_k_quant(const QuantParams& p, int dtype, int B, int H, int N, int D, hipStream_t st) {
-  const int nblk = (N + 63) / 64, per_wg = k_quant_blocks_per_wg(B, H, N, D);
-  const dim3 grid((nblk + per_wg - 1) / per_wg, H, B);
-  launch_begin();
-#define LAUNCH(DD, BF)                                                                                                  \
-  do {                                                                                                                  \
-    if (p.rounding == SAGE_ROUND_TRITON) hipLaunchKernelGGL((k_quant_stream_kernel<DD, BF, true>), grid, dim3(256), 0, st, p, per_wg);  \
-    else hipLaunchKernelGGL((k_quant_stream_kernel<DD, BF, false>), grid, dim3(256), 0, st, p, per_wg);                 \
-  } while (0)
-  if (D == 64) { if (dtype == SAGE_BF16) LAUNCH(64, true); else LAUNCH(64, false); }
-  else { if (dtype == SAGE_BF16) LAUNCH(128, true); else LAUNCH(128, false); }
-#undef LAUNCH
-  return launch_status();
+  QuantOptions opt;
+  opt.out_blk_stride = out_tile_stride;
+  opt.scale_strides = scale_strides;
+  QuantCall c;
+  if (const int s = quant_check(c, k, dtype, B, H, N, D, mean, out, scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1, nullptr,
+                                opt))
+    return s;
+  return quant_launch(c, (hipStream_t)stream);
 }
 
 // K smoothing + quantization as one call: km = mean over the sequence (sage_k_mean) and the INT8 quantization of k - km
@@ -793,29 +865,9 @@ static int launch_k_quant(const QuantParams& p, int dtype, int B, int H, int N, 
 // (kmean_chunk_rows) and the quantizer finishes the mean itself; bit-identical to the two separate entry points.
 extern "C" int sage_k_smooth_quant(const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
                                    float* scale, void* km, int gran, int rounding, void* workspace, sage_stream_t stream) {
-  if (!km || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
-  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
-  const int rows = kmean_chunk_rows(N), S = (N + rows - 1) / rows;   // <= 16 chunks at every length
-  if (!tensor_ok(k, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  hipStream_t st = (hipStream_t)stream;
-  launch_begin();
-  const dim3 grid(S, H, B);
-  const uint16_t* kp = (const uint16_t*)k->data;
-  float* ws = (float*)workspace;
-#define LAUNCH(DD, BF)                                                                                         \
-  hipLaunchKernelGGL((k_mean_partial_kernel<DD, BF>), grid, dim3(256), 0, st, kp, k->stride_b, k->stride_h, \
-                     k->stride_n, N, ws, S)
-  if (D == 64) { if (dtype == SAGE_BF16) LAUNCH(64, true); else LAUNCH(64, false); }
-  else { if (dtype == SAGE_BF16) LAUNCH(128, true); else LAUNCH(128, false); }
-#undef LAUNCH
-  if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
-  QuantParams p;
-  const int st0 = quant_impl(k, dtype, B, H, N, D, nullptr, out, scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1, nullptr, stream,
-                             nullptr, 0, nullptr, ws, S, km, &p);
-  if (st0 != SAGE_OK) return st0;
-  return launch_k_quant(p, dtype, B, H, N, D, st);
+  KSmoothCall c;
+  if (const int s = k_smooth_quant_check(c, k, dtype, B, H, N, D, out, scale, km, gran, rounding, workspace)) return s;
+  return k_smooth_quant_launch(c, (hipStream_t)stream);
 }
 
 extern "C" size_t sage_kv_prepare_fp8_workspace_bytes(int B, int H, int N, int D) {
@@ -827,62 +879,9 @@ extern "C" int sage_kv_prepare_fp8(const sage_tensor* k, const sage_tensor* v, i
                                    const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding,
                                    const sage_tensor* v_fp8, float* v_scale, float scale_max, void* workspace,
                                    sage_stream_t stream) {
-  if (!km || !workspace || !v_scale || !(scale_max > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
-  if (!tensor_ok(k, 8) || !tensor_ok(v, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (!v_fp8 || !v_fp8->data || !aligned16(v_fp8->data) || v_fp8->stride_b % 16 || v_fp8->stride_h % 16 || v_fp8->stride_n % 16)
-    return SAGE_ERR_INVALID_ARGUMENT;
-  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
-  if (dtype != SAGE_F16 && dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  const int rows = kmean_chunk_rows(N), S = (N + rows - 1) / rows;   // <= 16 chunks at every length
-  float* kpart = (float*)workspace;
-  float* vpart = kpart + (size_t)B * H * S * D;
-  QuantParams p;
-  const int st0 = quant_impl(k, dtype, B, H, N, D, nullptr, k_int8, k_scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1, nullptr,
-                             stream, nullptr, 0, nullptr, kpart, S, km, &p);
-  if (st0 != SAGE_OK) return st0;
-  VPrepParams q;
-  q.v = (const uint16_t*)v->data; q.sb = v->stride_b; q.sh = v->stride_h; q.sn = v->stride_n;
-  q.out = (uint8_t*)v_fp8->data; q.ob = v_fp8->stride_b; q.oh = v_fp8->stride_h; q.od = v_fp8->stride_n; q.o_tile = 64;
-  q.v_scale = v_scale; q.part = vpart; q.scale_max = scale_max;
-  const int nblk_k = (N + 63) / 64;
-  const int vq_blks = D == 128 ? 1 : 2;  // 64-token blocks per V unit (VQuantGeom<D>::BLKS)
-  const int nunit_v = (nblk_k + vq_blks - 1) / vq_blks;
-  // K blocks / V units per workgroup: each half gets about half of the workgroups the chip holds at once (k_quant_blocks_per_wg)
-  const int64_t target = 128 * (D == 64 ? 5 : 4);
-  // (at most kUnitsCap units per workgroup: beyond, more generations of workgroups measured better than longer walks)
-  constexpr int64_t kUnitsCap = 32;
-  auto per_wg = [&](int units) { int64_t per = ((int64_t)B * H * units + target - 1) / target; per = per > kUnitsCap ? kUnitsCap : per; return (int)(per < 1 ? 1 : per > units ? units : per); };
-  const int per_k = per_wg(nblk_k), per_v = per_wg(nunit_v);
-  const int nwg_k = (nblk_k + per_k - 1) / per_k, nwg_v = (nunit_v + per_v - 1) / per_v;
-  hipStream_t st = (hipStream_t)stream;
-  launch_begin();
-  const dim3 ga(2 * S, H, B), gb(nwg_k + nwg_v, H, B);
-  const uint16_t* kp = (const uint16_t*)k->data;
-#define LA(DD, BF)                                                                                                          \
-  hipLaunchKernelGGL((kv_partial_kernel<DD, BF>), ga, dim3(256), 0, st, kp, k->stride_b, k->stride_h, k->stride_n, q.v, q.sb, \
-                     q.sh, q.sn, N, kpart, vpart, S)
-  // Streaming pays where a workgroup walks enough units to hide its start-up (measured, tools/prepass_ab.py, B*H = 128: head_dim
-  // 128: 4-8 units per workgroup +6..10 % slower than one unit per workgroup, 16-32 units 6-12 % faster, 64 even; head_dim 64:
-  // 2 units slower, 4 faster); below that the one-unit-per-workgroup kernel (seven or eight workgroups per CU) runs.
-  const bool stream_b = per_v >= (D == 64 ? 4 : 12);
-  const int nblk_v1 = nunit_v;
-  const dim3 gb1(nblk_k + nblk_v1, H, B);
-#define LB(DD, BF)                                                                                                      \
-  do {                                                                                                                  \
-    if (stream_b) {                                                                                                     \
-      if (rounding == SAGE_ROUND_TRITON) hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, true>), gb, dim3(256), 0, st, p, q, per_k, nwg_k, per_v);  \
-      else hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, false>), gb, dim3(256), 0, st, p, q, per_k, nwg_k, per_v); \
-    } else {                                                                                                            \
-      if (rounding == SAGE_ROUND_TRITON) hipLaunchKernelGGL((kv_quant_kernel<DD, BF, true>), gb1, dim3(256), 0, st, p, q, nblk_k);  \
-      else hipLaunchKernelGGL((kv_quant_kernel<DD, BF, false>), gb1, dim3(256), 0, st, p, q, nblk_k);                   \
-    }                                                                                                                   \
-  } while (0)
-  const bool bf = dtype == SAGE_BF16;
-  if (D == 64) { if (bf) LA(64, true); else LA(64, false); } else { if (bf) LA(128, true); else LA(128, false); }
-  if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
-  if (D == 64) { if (bf) LB(64, true); else LB(64, false); } else { if (bf) LB(128, true); else LB(128, false); }
-#undef LA
-#undef LB
-  return launch_status();
+  KVPrepCall c;
+  if (const int s = kv_prepare_check(c, k, v, dtype, B, H, N, D, k_int8, k_scale, km, gran, rounding, v_fp8, v_scale,
+                                     scale_max, workspace))
+    return s;
+  return kv_prepare_launch(c, (hipStream_t)stream);
 }

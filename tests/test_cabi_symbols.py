@@ -124,3 +124,209 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         _lib.lib()
+
+
+# ---- every argument is checked before the first launch ------------------------------------------------------------------
+# The cases below pass fake device addresses.  Where a GPU is visible a missed check would launch kernels on them, so they
+# run only where none is: there every launch attempt returns SAGE_ERR_LAUNCH (-5), which makes a launch observable.
+def _gpu_visible():
+    import torch
+    return torch.cuda.is_available()
+
+
+no_gpu = pytest.mark.skipif(_gpu_visible(), reason="passes fake device addresses: only where no GPU is visible")
+
+FAKE = 1 << 20  # a 16-byte aligned fake device address
+ODD = FAKE + 8  # an unaligned one
+
+# parameter names of every entry point that validates its arguments, in the order of include/sageattn_hip.h
+_PARAMS = {
+    "sage_k_mean": "k dtype B H N D km ws stream",
+    "sage_quant_qk_int8": "x dtype B H N D mean out scale gran is_key blk warp mult rounding dvec dgroup dot stream",
+    "sage_quant_qk_int8_varlen": "x dtype cu nseq H N D mean out scale gran is_key blk warp mult rounding stream",
+    "sage_sub_mean_f16": "v dtype B H N D vm out stream",
+    "sage_quant_k_int8_kvtiles": "k dtype B H N D mean out tile scale sstr gran rounding stream",
+    "sage_k_smooth_quant": "k dtype B H N D out scale km gran rounding ws stream",
+    "sage_kv_prepare_fp8": "k v dtype B H N D k8 ks km gran rounding v8 vs smax ws stream",
+    "sage_quant_v_fp8": "v dtype B H N D v8 vs vm smax ws stream",
+    "sage_seq_stats": "x dtype B H N D stats ws stream",
+    "sage_kv_stats_reduce": "kst vst parts pstride BH D n dtype smax km vs vc stream",
+    "sage_quant_v_fp8_apply": "v dtype B H N D v8 tile vc stream",
+    "sage_merge_attn_states": "oa la ob dtype lb rows D stream",
+    "sage_merge_attn_states_multi_ex": "obs lbs count dtype oo lo rows D mult corr cmult stream",
+    "sage_merge_attn_states_multi": "obs lbs count dtype oo lo rows D stream",
+    "sage_finish_lse": "l2 corr sm lo n stream",
+    "sage_attn_qk_int8_pv_f16": "q k v vdt o odt qs ks vm lse B Hq Hk M N D causal gran blkq warpq sm lm1 stream",
+    "sage_attn_qk_int8_pv_f8": "q k v o odt qs ks vs vm lse B Hq Hk M N D causal gran blkq warpq sm lm1 stream",
+    "sage_attn_qk_int8_pv_f16_varlen": "q k v vdt o odt qs ks cuq cuk B Hq Hk M N D causal gran blkq warpq sm lm1 stream",
+    "sage_attn_fusedq_pv_f16": "q qdt k v vdt o odt ks km vm lse B Hq Hk M N D causal gran warpq sm stream",
+    "sage_attn_fusedq_pv_f8": "q qdt k v o odt ks km vs vm lse B Hq Hk M N D causal gran warpq sm stream",
+    "sage_attn_qk_int8_pv_f16_masked": "q k v vdt o odt qs ks mask mkind mstr lse B Hq Hk M N D gran blkq warpq sm lm1 stream",
+    "sage_attn_qk_int8_pv_f16_kvtiles": "q k v vdt o odt qs ks lay lse B Hq Hk M N D causal gran blkq warpq sm stream",
+    "sage_attn_qk_int8_pv_f8_kvtiles": "q k v o odt qs ks vs lay lse B Hq Hk M N D causal gran blkq warpq sm stream",
+    "sage_sageattn_pv_f16": "q k v dtype o lse B Hq Hk M N D causal sm opts ws wsb stream",
+    "sage_sageattn_pv_f8": "q k v dtype o lse B Hq Hk M N D causal sm smax opts ws wsb stream",
+}
+
+
+def _t(data=FAKE, sn=64):
+    from sageattention_amd import _lib as L
+    return L.SageTensor(data, 1 << 16, 1 << 12, sn)
+
+
+def _valid_args():
+    """One valid argument set per entry point (every pointer a fake address)."""
+    import ctypes as C
+    from sageattention_amd import _lib as L
+    t, a = _t(), FAKE
+    shape = dict(dtype=0, B=1, H=1, N=64, D=64, stream=None)
+    quant = dict(shape, x=t, mean=None, out=t, scale=a, gran=3, is_key=0, blk=128, warp=32, mult=1.0, rounding=0)
+    attn = dict(q=t, k=t, v=t, vdt=0, o=t, odt=0, qs=a, ks=a, vs=a, vm=None, lse=None, B=1, Hq=2, Hk=1, M=64, N=64, D=64,
+                causal=0, gran=3, blkq=128, warpq=32, sm=0.125, lm1=0, stream=None)
+    blks = (C.c_void_p * 16)(*([a] * 16))
+    op = dict(q=t, k=t, v=t, dtype=0, o=t, lse=None, B=1, Hq=2, Hk=1, M=64, N=64, D=64, causal=0, sm=0.125, smax=448.0,
+              opts=L.OpOpts(3, 32, 1, -1, 0), ws=a, wsb=1 << 40, stream=None)
+    return {
+        "sage_k_mean": dict(shape, k=t, km=a, ws=a),
+        "sage_quant_qk_int8": dict(quant, dvec=None, dgroup=1, dot=None),
+        "sage_quant_qk_int8_varlen": dict(quant, cu=a, nseq=1),
+        "sage_sub_mean_f16": dict(shape, v=t, vm=a, out=t),
+        "sage_quant_k_int8_kvtiles": dict(shape, k=t, mean=None, out=t, tile=4096, scale=a, sstr=(C.c_int64 * 3)(256, 256, 4),
+                                          gran=3, rounding=0),
+        "sage_k_smooth_quant": dict(shape, k=t, out=t, scale=a, km=a, gran=3, rounding=0, ws=a),
+        "sage_kv_prepare_fp8": dict(shape, k=t, v=t, k8=t, ks=a, km=a, gran=3, rounding=0, v8=t, vs=a, smax=448.0, ws=a),
+        "sage_quant_v_fp8": dict(shape, v=t, v8=t, vs=a, vm=None, smax=448.0, ws=a),
+        "sage_seq_stats": dict(shape, x=t, stats=a, ws=a),
+        "sage_kv_stats_reduce": dict(kst=a, vst=a, parts=1, pstride=384, BH=1, D=64, n=64, dtype=0, smax=448.0, km=a, vs=a,
+                                     vc=a, stream=None),
+        "sage_quant_v_fp8_apply": dict(shape, v=t, v8=t, tile=0, vc=a),
+        "sage_merge_attn_states": dict(oa=a, la=a, ob=a, dtype=0, lb=a, rows=4, D=64, stream=None),
+        "sage_merge_attn_states_multi_ex": dict(obs=blks, lbs=blks, count=3, dtype=0, oo=a, lo=a, rows=4, D=64, mult=1.0,
+                                                corr=None, cmult=0.0, stream=None),
+        "sage_merge_attn_states_multi": dict(obs=blks, lbs=blks, count=3, dtype=0, oo=a, lo=a, rows=4, D=64, stream=None),
+        "sage_finish_lse": dict(l2=a, corr=None, sm=0.125, lo=a, n=64, stream=None),
+        "sage_attn_qk_int8_pv_f16": attn,
+        "sage_attn_qk_int8_pv_f8": attn,
+        "sage_attn_qk_int8_pv_f16_varlen": dict(attn, cuq=a, cuk=a),
+        "sage_attn_fusedq_pv_f16": dict(attn, qdt=0, km=a),
+        "sage_attn_fusedq_pv_f8": dict(attn, qdt=0, km=a),
+        "sage_attn_qk_int8_pv_f16_masked": dict(attn, mask=a, mkind=1, mstr=(C.c_int64 * 4)(0, 0, 64, 1)),
+        "sage_attn_qk_int8_pv_f16_kvtiles": dict(attn, lay=L.KvLayout(0, 0, 0, 0, 0)),
+        "sage_attn_qk_int8_pv_f8_kvtiles": dict(attn, lay=L.KvLayout(0, 0, 0, 0, 0)),
+        "sage_sageattn_pv_f16": op,
+        "sage_sageattn_pv_f8": op,
+    }
+
+
+def _call(fn, **change):
+    from sageattention_amd import _lib as L
+    args = dict(_valid_args()[fn], **change)
+    return getattr(L.lib(), fn)(*[args[n] for n in _PARAMS[fn].split()])
+
+
+def _single_faults():
+    """(entry point, the one argument made invalid, expected status).  Each of these was already rejected before any launch
+    before the entry points were split into check and launch, with the same status."""
+    import ctypes as C
+    from sageattention_amd import _lib as L
+    t = _t()
+    nul, odd, s4 = _t(data=0), _t(data=ODD), _t(sn=4)  # null data, unaligned data, a stride that is not a multiple of 8
+    s8 = _t(sn=8)                                       # ... of 16
+    bad = -1
+    shape = [("B", 0), ("H", 0), ("N", 0)]
+    dim = [("D", 96, -2), ("dtype", 7, bad)]
+
+    def rows(fn, *cases):
+        return [(fn, c[0], c[1], c[2] if len(c) > 2 else bad) for c in cases]
+
+    out = []
+    out += rows("sage_k_mean", ("k", None), ("k", nul), ("k", odd), ("k", s4), ("km", None), ("ws", None), *shape, *dim)
+    quant = [("x", None), ("x", odd), ("x", s4), ("out", None), ("out", s4), ("scale", None), ("gran", 0), ("gran", 4),
+             ("rounding", 2), ("blk", 32), ("warp", 8), ("warp", 48), ("mean", ODD), *dim]
+    out += rows("sage_quant_qk_int8", *quant, *shape, ("dvec", FAKE), ("dot", FAKE))
+    out += [("sage_quant_qk_int8", "dvec+dot", dict(dvec=FAKE, dot=FAKE, dgroup=0), bad),
+            ("sage_quant_qk_int8", "dvec+dot", dict(dvec=FAKE, dot=FAKE, dgroup=2), bad),
+            ("sage_quant_qk_int8", "dvec+dot", dict(dvec=ODD, dot=FAKE), bad),
+            ("sage_quant_qk_int8", "blk+warp", dict(blk=64, warp=128), bad)]
+    out += rows("sage_quant_qk_int8_varlen", *quant, ("cu", None), ("nseq", 0), ("H", 0), ("N", 0))
+    out += rows("sage_sub_mean_f16", ("v", None), ("v", odd), ("v", s4), ("vm", None), ("vm", ODD), ("out", nul),
+                ("out", s4), *shape, *dim)
+    out += rows("sage_quant_k_int8_kvtiles", ("k", odd), ("out", s4), ("scale", None), ("sstr", None), ("tile", 0),
+                ("tile", -4096), ("tile", 4100), ("sstr", (C.c_int64 * 3)(256, 256, 2)), ("gran", 2), ("gran", 0),
+                ("rounding", 2), ("mean", ODD), *shape, *dim)
+    out += rows("sage_k_smooth_quant", ("k", None), ("k", odd), ("k", s4), ("km", None), ("ws", None), ("gran", 2),
+                ("gran", 0), *shape, *dim)
+    out += rows("sage_kv_prepare_fp8", ("k", odd), ("v", None), ("v", s4), ("k8", odd), ("k8", s4), ("ks", None),
+                ("km", None), ("v8", None), ("v8", s8), ("vs", None), ("ws", None), ("smax", 0.0), ("smax", float("nan")),
+                ("gran", 2), ("gran", 4), ("rounding", 5), *shape, *dim)
+    out += rows("sage_quant_v_fp8", ("v", None), ("v", odd), ("v", s4), ("v8", nul), ("v8", s8), ("vs", None),
+                ("ws", None), ("smax", 0.0), ("smax", -1.0), *shape, *dim)
+    out += rows("sage_seq_stats", ("x", None), ("x", odd), ("x", s4), ("stats", None), ("ws", None), *shape, *dim)
+    out += rows("sage_kv_stats_reduce", ("parts", 0), ("BH", 0), ("n", 0), ("pstride", 191), ("kst", None),
+                ("km", None), ("vs", None), ("vc", None), ("smax", 0.0), *dim)
+    out += [("sage_kv_stats_reduce", "kst+vst", dict(kst=None, vst=None, km=None), bad)]
+    out += rows("sage_quant_v_fp8_apply", ("v", None), ("v", s4), ("v8", odd), ("v8", s8), ("vc", None), ("tile", -64),
+                ("tile", 24), *shape, *dim)
+    merge = [("rows", 0), ("D", 96, -2), ("dtype", 7)]
+    out += rows("sage_merge_attn_states", ("oa", None), ("oa", ODD), ("la", None), ("ob", None), ("ob", ODD),
+                ("lb", None), *merge)
+    blk = lambda i, v: (C.c_void_p * 16)(*[v if j == i else FAKE for j in range(16)])  # noqa: E731
+    multi = [("obs", None), ("lbs", None), ("oo", None), ("oo", ODD), ("count", 0), ("count", 17), ("obs", blk(2, None)),
+             ("obs", blk(1, ODD)), ("lbs", blk(0, None)), *merge]
+    out += rows("sage_merge_attn_states_multi_ex", *multi, ("mult", 0.0), ("mult", float("nan")))
+    out += rows("sage_merge_attn_states_multi", *multi)
+    out += rows("sage_finish_lse", ("l2", None), ("lo", None), ("n", 0))
+    attn = [("q", None), ("q", odd), ("q", s8), ("k", s8), ("o", _t(sn=2)), ("qs", None), ("ks", None), ("B", 0),
+            ("Hq", 0), ("Hk", 0), ("Hk", 3), ("M", 0), ("N", 0), ("sm", 0.0), ("sm", float("nan")), ("sm", float("inf")),
+            ("gran", 0), ("gran", 4), ("blkq", 32), ("warpq", 8), ("warpq", 48), ("odt", 7), ("D", 96, -2),
+            ("N", 1 << 25, -4)]
+    out += rows("sage_attn_qk_int8_pv_f16", *attn, ("v", s4), ("vdt", 7), ("vm", ODD))
+    out += rows("sage_attn_qk_int8_pv_f8", *attn, ("v", s8), ("vs", None), ("vs", ODD), ("vm", ODD))
+    out += rows("sage_attn_qk_int8_pv_f16_varlen", ("cuq", None), ("cuk", None), ("q", odd), ("D", 96, -2), ("vdt", 7))
+    fused = [("qdt", 7), ("gran", 1, -3), ("km", ODD, -3), ("q", odd), ("q", s4), ("ks", None), ("sm", 0.0), ("o", nul),
+             ("D", 96, -2), ("odt", 7)]
+    out += rows("sage_attn_fusedq_pv_f16", *fused, ("v", s4), ("vdt", 7))
+    out += rows("sage_attn_fusedq_pv_f8", *fused, ("v", s8), ("vs", None))
+    out += rows("sage_attn_qk_int8_pv_f16_masked", ("mask", None), ("mkind", 0), ("mkind", 4), ("mstr", None),
+                ("q", odd), ("sm", 0.0), ("D", 96, -2), ("vdt", 7))
+    lay = lambda *s: L.KvLayout(*s)  # noqa: E731
+    tiles = [("lay", None), ("lay", lay(-64, 0, 0, 0, 0)), ("lay", lay(0, -64, 0, 0, 0)), ("lay", lay(24, 0, 0, 0, 0)),
+             ("lay", lay(0, 0, 8, 8, 2)), ("lay", lay(0, 0, 6, 6, 4)), ("lay", lay(0, 0, -4, 4, 4)), ("q", odd),
+             ("D", 96, -2)]
+    out += rows("sage_attn_qk_int8_pv_f16_kvtiles", *tiles, ("lay", lay(0, 4, 0, 0, 0)))
+    out += rows("sage_attn_qk_int8_pv_f8_kvtiles", *tiles, ("lay", lay(0, 8, 0, 0, 0)), ("vs", None))
+    opts = lambda *o: L.OpOpts(*o)  # noqa: E731
+    op = [("q", None), ("k", None), ("v", None), ("o", None), ("opts", None), ("ws", None), ("ws", ODD), ("wsb", 4096),
+          ("D", 96, -2), ("dtype", 7), ("B", 0), ("Hk", 0), ("Hk", 3), ("M", 0), ("N", 0), ("k", odd),
+          ("opts", opts(3, 32, 0, -1, 0), -3), ("opts", opts(3, 32, 1, -1, 5)), ("opts", opts(1, 32, 1, -1, 0)),
+          ("opts", opts(3, 64, 1, -1, 0))]
+    out += rows("sage_sageattn_pv_f16", *op)
+    out += rows("sage_sageattn_pv_f8", *op, ("smax", 0.0), ("v", odd))
+    return [(fn, what, c if isinstance(c, dict) else {what: c}, st) for fn, what, c, st in out]
+
+
+@no_gpu
+def test_single_fault_status_table(built_lib):
+    """Each argument made invalid on its own is rejected with its status."""
+    cases = _single_faults()
+    assert {fn for fn, *_ in cases} == set(_PARAMS)
+    wrong = [(fn, what, st, got) for fn, what, change, st in cases if (got := _call(fn, **change)) != st]
+    assert not wrong, wrong
+
+
+@no_gpu
+def test_rejected_before_any_launch(built_lib):
+    """A call that returns an argument status has enqueued nothing: with no GPU every launch attempt fails, so a valid call
+    returns SAGE_ERR_LAUNCH, and an invalid one must return its argument status instead."""
+    from sageattention_amd import _lib as L
+    not_launched = [fn for fn in _PARAMS if _call(fn) != -5]
+    assert not not_launched, not_launched  # the control: every valid call reaches a launch
+    fuse0 = L.OpOpts(3, 32, 1, 0, 0)  # the stand-alone Q quantizer
+    cases = [("sage_k_smooth_quant", dict(out=_t(data=ODD))), ("sage_k_smooth_quant", dict(scale=None)),
+             ("sage_k_smooth_quant", dict(rounding=5))]
+    for fn in ("sage_sageattn_pv_f16", "sage_sageattn_pv_f8"):
+        for change in (dict(q=_t(data=ODD)), dict(o=_t(data=ODD)), dict(sm=0.0), dict(sm=float("nan"))):
+            cases += [(fn, change), (fn, dict(change, opts=fuse0))]
+    cases += [("sage_sageattn_pv_f16", dict(v=_t(data=ODD))), ("sage_sageattn_pv_f16", dict(v=_t(data=ODD), opts=fuse0))]
+    launched = [(fn, sorted(change), got) for fn, change in cases if (got := _call(fn, **change)) != -1]
+    assert not launched, launched
