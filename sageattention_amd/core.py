@@ -47,7 +47,17 @@ def _pad_head_dim(q, k, v):
         k = torch.nn.functional.pad(k, (0, pad))
         v = torch.nn.functional.pad(v, (0, pad))
     assert q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1, "Last dim of qkv must be contiguous."
-    return q, k, v, head_dim_og
+    return _abi_view(q), _abi_view(k), _abi_view(v), head_dim_og
+
+
+def _abi_view(t):
+    """The reference takes any tensor whose last dim is contiguous (core.py:592-601); the C ABI wants a 16-byte aligned
+    base and strides that are multiples of 16 bytes (csrc/sage_common.h tensor_ok).  A view that does not meet that --
+    ``x[..., 4:68]``, a row stride of D + 4 -- is passed as a contiguous copy; every other tensor as it is."""
+    unit = 16 // t.element_size()
+    if t.data_ptr() % 16 == 0 and all(s % unit == 0 for s in t.stride()[:-1]):
+        return t
+    return t.contiguous()
 
 
 def _quant_qk(q, k, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr, Hq, Hk):

@@ -302,7 +302,35 @@ def _single_faults():
           ("opts", opts(3, 64, 1, -1, 0))]
     out += rows("sage_sageattn_pv_f16", *op)
     out += rows("sage_sageattn_pv_f8", *op, ("smax", 0.0), ("v", odd))
+    out += _window_rows()
     return [(fn, what, c if isinstance(c, dict) else {what: c}, st) for fn, what, c, st in out]
+
+
+def _window_rows():
+    """The 2^31-byte window of a (b, h_kv) slice is measured with the STRIDES (ceil(N/64) tiles of 64 * stride_n), not
+    with N * D: 128K keys whose rows lie far apart -- a K or V slice of a packed QKV projection with many heads, an FP8 V
+    image whose channel rows are 16 MiB apart -- cross it although N * D is 16 MiB.  Each limit is pinned from both
+    sides: the largest stride below it reaches the launch (-5 where no GPU is visible), the next one is TOO_LARGE (-4)."""
+    N = 1 << 17  # 2048 tiles (+ one tile of slack in the check): k8 crosses at stride_n = 16376 bytes, a 16-bit v at 8188 elements
+    k_ok, k_big, k_qkv = _t(sn=16368), _t(sn=16384), _t(sn=3 * 64 * 128)
+    v_ok, v_big, v_qkv = _t(sn=8184), _t(sn=8192), _t(sn=3 * 32 * 128)
+    f8_ok, f8_big = _t(sn=(1 << 24) - 1040), _t(sn=(1 << 24) - 1024)  # D * stride_n + 64 * 2049 bytes
+    out = []
+    for fn, v_rows in (("sage_attn_qk_int8_pv_f16", (v_ok, v_big, v_qkv)), ("sage_attn_fusedq_pv_f16", (v_ok, v_big, v_qkv)),
+                       ("sage_attn_qk_int8_pv_f8", (f8_ok, f8_big, None)), ("sage_attn_fusedq_pv_f8", (f8_ok, f8_big, None))):
+        out += [(fn, "N", dict(N=N, D=128), -5),
+                (fn, "k window", dict(N=N, D=128, k=k_ok), -5), (fn, "k window", dict(N=N, D=128, k=k_big), -4),
+                (fn, "k window", dict(N=N, D=128, k=k_qkv), -4),
+                (fn, "v window", dict(N=N, D=128, v=v_rows[0]), -5), (fn, "v window", dict(N=N, D=128, v=v_rows[1]), -4)]
+        if v_rows[2] is not None:
+            out.append((fn, "v window", dict(N=N, D=128, v=v_rows[2]), -4))
+    # the one-call operators quantize K (and for FP8 PV also V) into dense workspace images: only the FP16-PV operator's v
+    # reaches the attention kernel with the caller's strides
+    fn = "sage_sageattn_pv_f16"
+    out += [(fn, "N", dict(N=N, D=128), -5), (fn, "v window", dict(N=N, D=128, v=v_ok), -5),
+            (fn, "v window", dict(N=N, D=128, v=v_big), -4), (fn, "v window", dict(N=N, D=128, v=v_qkv), -4),
+            (fn, "k stride", dict(N=N, D=128, k=k_qkv), -5), ("sage_sageattn_pv_f8", "k, v strides", dict(N=N, D=128, k=v_qkv, v=v_qkv), -5)]
+    return out
 
 
 @no_gpu
