@@ -377,6 +377,60 @@ int sage_merge_attn_states_multi_ex(const void* const* o_blks, const float* cons
                                     void* o_out, float* lse_out, int64_t rows, int D, float lse_in_mult,
                                     const float* corr, float corr_mult, sage_stream_t stream);
 
+/* ==== block-sparse attention (new: SpargeAttn-style block maps, sliding-tile / window patterns, text and padding
+ * cut-outs.  The reference has no counterpart beyond the tile skipping of its masked Triton kernels,
+ * triton/attn_qk_int8_per_block.py:38-39; geometry: those kernels' 128x64 tile) ====
+ * block_map[b, h_q, i, j] != 0: query rows [128 i, 128 i + 128) of head h_q attend keys [64 j, 64 j + 64).  Tiles that are
+ * off are neither copied nor computed; inside an active tile only the sequence end (N % 64) masks keys.  Non-causal.
+ * Query rows of a block row without any active tile are DEFINED: o = 0, lse = -inf (sage_attn_qk_int8_pv_f16_masked
+ * leaves such rows undefined).
+ *
+ * The attention kernels take the map as compacted tile lists, a caller-owned buffer of
+ * sage_block_sparse_workspace_bytes(B,Hq,M,N) bytes (0 for non-positive sizes), 16-byte aligned: one row of int32 per
+ * (b, h_q, block row) = [count, the active tile indices ascending, then the last of them repeated (>= 5 times)]; a row has
+ * 1 + ceil(N/64) + 5 entries rounded up to a multiple of 4.  A static pattern is compacted once and the lists are reused.
+ * sage_block_map_compact: block_map is a device pointer to a uint8/bool [B,Hq,ceil(M/128),ceil(N/64)] VIEW given by
+ * map_strides[4] in ELEMENTS (host array; 0 = broadcast dimension, as the attn_mask of sage_attn_qk_int8_pv_f16_masked).
+ * One wave per list row (ballot + prefix count): deterministic, no atomics. */
+size_t sage_block_sparse_workspace_bytes(int B, int Hq, int M, int N);
+int sage_block_map_compact(const void* block_map, const int64_t* map_strides, int B, int Hq, int M, int N,
+                           int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream);
+
+/* sage_attn_qk_int8_pv_{f16,f8} and sage_attn_fusedq_pv_{f16,f8} over the active tiles of a block map: the arguments of the
+ * dense twin, then the lists (block_lists, block_lists_bytes >= sage_block_sparse_workspace_bytes).  Same loop and same
+ * arithmetic in the same order as the dense kernel run on the active tiles gathered into one contiguous K/V: results are
+ * bit-identical to that.  Replace sage_attn_qk_int8_pv_f16_masked on an expanded [B,H,M,N] mask for block-granular
+ * patterns, and extend it to FP8 PV and the fused Q quantizer.  Workgroups always have 4 waves (128 rows = one block row of
+ * the map): SAGE_TUNE_NWAVES does not apply.  Not combinable: is_causal != 0 and v_mean != NULL return
+ * SAGE_ERR_UNSUPPORTED; there is no varlen, attn_mask or kv_layout form.  The kernels trust the lists (counts, ascending
+ * indices < ceil(N/64), the padded tail): pass what sage_block_map_compact wrote for the same (B, Hq, M, N).  The rows of
+ * empty block rows are written by a second, tiny launch on the same stream. */
+int sage_attn_qk_int8_pv_f16_blocksparse(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
+                                         int v_dtype, const sage_tensor* o, int o_dtype,
+                                         const float* q_scale, const float* k_scale, const float* v_mean,
+                                         float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                         int is_causal, int qk_gran, int blkq, int warpq,
+                                         float sm_scale, int logit_mult_is_one, const int32_t* block_lists,
+                                         int64_t block_lists_bytes, sage_stream_t stream);
+int sage_attn_qk_int8_pv_f8_blocksparse(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                        const sage_tensor* o, int o_dtype,
+                                        const float* q_scale, const float* k_scale, const float* v_scale,
+                                        const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N,
+                                        int D, int is_causal, int qk_gran, int blkq, int warpq,
+                                        float sm_scale, int logit_mult_is_one, const int32_t* block_lists,
+                                        int64_t block_lists_bytes, sage_stream_t stream);
+int sage_attn_fusedq_pv_f16_blocksparse(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                        int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale,
+                                        const void* km, const float* v_mean, float* lse, int B, int Hq, int Hk,
+                                        int M, int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                        const int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                       const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                       const float* k_scale, const void* km, const float* v_scale,
+                                       const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                       int is_causal, int qk_gran, int warpq, float sm_scale,
+                                       const int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

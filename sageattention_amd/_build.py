@@ -51,7 +51,9 @@ def _check_occupancy(src, compiler_output):
         if m:
             name = m.group(1)
         m = re.search(r" VGPRs: (\d+)", line)
-        if m and name and re.search(r"attn_i8_kernelILi64ELi4E(Lb[01]E){4}Lb0EEE", name) and int(m.group(1)) > 168:
+        guarded = name and (re.search(r"attn_i8_kernelILi64ELi4E(Lb[01]E){4}Lb0EEE", name) or
+                            re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name))  # the block-sparse twins
+        if m and guarded and int(m.group(1)) > 168:
             raise RuntimeError(f"{src}: kernel {name} uses {m.group(1)} VGPRs (> 168: two waves per SIMD instead of three)")
 
 

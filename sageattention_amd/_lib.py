@@ -98,6 +98,22 @@ SIGNATURES = {
     "sage_quant_v_fp8_apply": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p, c_void_p]),
     "sage_merge_attn_states_multi_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
                                                 c_float, c_void_p, c_float, c_void_p]),
+    "sage_block_sparse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sage_block_map_compact": (c_int, [c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_void_p, c_int64,
+                                       c_void_p]),
+    # the dense twins' arguments, then (block_lists, block_lists_bytes) in front of the stream
+    "sage_attn_qk_int8_pv_f16_blocksparse": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                     c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "sage_attn_qk_int8_pv_f8_blocksparse": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                    c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "sage_attn_fusedq_pv_f16_blocksparse": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                    c_float, c_void_p, c_int64, c_void_p]),
+    "sage_attn_fusedq_pv_f8_blocksparse": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                   c_float, c_void_p, c_int64, c_void_p]),
 }
 
 

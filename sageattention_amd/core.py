@@ -19,7 +19,8 @@ from . import _qattn
 from .quant import _quant, k_mean, k_smooth_quant, kv_prepare_fp8, per_channel_fp8, sub_mean
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
-           "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen"]
+           "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
+           "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan"]
 
 
 def _common_checks(q, k, v):
@@ -136,7 +137,8 @@ def _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr
 
 
 def _fused_attn(q, k8, ks, v, o, km, v_scale, v_mean, tensor_layout, is_causal, qk_quant_gran, warpq, sm_scale, return_lse,
-                pv_fp8):
+                pv_fp8, plan=None):
+    """sage_attn_fusedq_pv_{f16,f8}; with ``plan`` (a BlockSparsePlan) their block-sparse twins."""
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k8, tensor_layout)
     if Hq % Hk != 0:
@@ -147,18 +149,22 @@ def _fused_attn(q, k8, ks, v, o, km, v_scale, v_mean, tensor_layout, is_causal, 
     if pv_fp8:
         vd = (L.SageTensor(v.data_ptr(), v.stride(0), v.stride(1), v.stride(2)) if tensor_layout == "HND"
               else L.SageTensor(v.data_ptr(), v.stride(0), v.stride(2), v.stride(1)))
-        status = lib.sage_attn_fusedq_pv_f8(L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), vd,
-                                            L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km),
-                                            v_scale.data_ptr(), L.ptr(vm), L.ptr(lse), B, Hq, Hk, M, N, D, int(is_causal),
-                                            _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale), st)
-        L.check(status, "sage_attn_fusedq_pv_f8")
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), vd,
+                L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km),
+                v_scale.data_ptr(), L.ptr(vm), L.ptr(lse), B, Hq, Hk, M, N, D, int(is_causal),
+                _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
+        name = "sage_attn_fusedq_pv_f8"
     else:
-        status = lib.sage_attn_fusedq_pv_f16(L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout),
-                                             L.desc(v, tensor_layout), L.dtype_code(v.dtype), L.desc(o, tensor_layout),
-                                             L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km), L.ptr(vm), L.ptr(lse),
-                                             B, Hq, Hk, M, N, D, int(is_causal), _GRAN_CODE[qk_quant_gran], warpq,
-                                             float(sm_scale), st)
-        L.check(status, "sage_attn_fusedq_pv_f16")
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout),
+                L.desc(v, tensor_layout), L.dtype_code(v.dtype), L.desc(o, tensor_layout),
+                L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km), L.ptr(vm), L.ptr(lse),
+                B, Hq, Hk, M, N, D, int(is_causal), _GRAN_CODE[qk_quant_gran], warpq,
+                float(sm_scale))
+        name = "sage_attn_fusedq_pv_f16"
+    if plan is not None:
+        name += "_blocksparse"
+        args += (plan.lists.data_ptr(), plan.lists.numel() * 4)
+    L.check(getattr(lib, name)(*args, st), name)
     return lse
 
 
@@ -478,3 +484,107 @@ def sageattn_varlen(
                                                     int(max_seqlen_q), int(max_seqlen_k), D, int(is_causal), L.GRAN_PER_BLOCK,
                                                     128, 128, float(sm_scale), 1, st), "sage_attn_qk_int8_pv_f16_varlen")
         return o[..., :head_dim_og]
+
+
+# ---- block-sparse attention ------------------------------------------------------------------------------------------------
+class BlockSparsePlan:
+    """The compacted form of a block map (``block_sparse_plan``): per (batch, query head, 128-row q-block) the ascending
+    list of active 64-key tiles, as the attention kernel reads it.  A static pattern is compacted once and the plan reused
+    across layers and diffusion steps."""
+    __slots__ = ("lists", "B", "Hq", "M", "N")
+
+    def __init__(self, lists, B, Hq, M, N):
+        self.lists, self.B, self.Hq, self.M, self.N = lists, B, Hq, M, N
+
+
+def _check_block_map(block_map, B, Hq, M, N):
+    """[B|1, Hq|1, ceil(M/128), ceil(N/64)] bool / uint8 -> the [B,Hq,..] view (0 strides where it broadcasts)"""
+    if not isinstance(block_map, torch.Tensor):
+        raise TypeError("block_map must be a bool/uint8 tensor or a BlockSparsePlan")
+    if block_map.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"block_map must be of dtype bool or uint8, got {block_map.dtype}")
+    want = ((M + 127) // 128, (N + 63) // 64)
+    if (block_map.dim() != 4 or tuple(block_map.shape[2:]) != want or block_map.size(0) not in (1, B)
+            or block_map.size(1) not in (1, Hq)):
+        raise ValueError(f"block_map shape {tuple(block_map.shape)} does not match [B={B} or 1, Hq={Hq} or 1, "
+                         f"ceil(M/128)={want[0]}, ceil(N/64)={want[1]}]")
+    return block_map.expand(B, Hq, *want)
+
+
+def block_sparse_plan(block_map: torch.Tensor, M: int, N: int, B: Optional[int] = None, Hq: Optional[int] = None):
+    """Compact ``block_map`` ([B,Hq,ceil(M/128),ceil(N/64)] bool / uint8 on the GPU; any strides, sizes 1 broadcast over B
+    and Hq -- pass ``B`` / ``Hq`` to broadcast to more) into a ``BlockSparsePlan`` (sage_block_map_compact: one wave per
+    list, deterministic)."""
+    if isinstance(block_map, torch.Tensor) and block_map.dim() == 4:
+        B = block_map.size(0) if B is None else B
+        Hq = block_map.size(1) if Hq is None else Hq
+    m = _check_block_map(block_map, B, Hq, M, N)
+    if not m.is_cuda:
+        raise ValueError("block_map must be on the GPU")
+    lib = L.lib()
+    lists = torch.empty(lib.sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4, dtype=torch.int32, device=m.device)
+    with torch.cuda.device(m.device):
+        L.check(lib.sage_block_map_compact(m.data_ptr(), (ctypes.c_int64 * 4)(*m.stride()), B, Hq, M, N, lists.data_ptr(),
+                                           lists.numel() * 4, L.stream_ptr(m.device)), "sage_block_map_compact")
+    return BlockSparsePlan(lists, B, Hq, M, N)
+
+
+@torch.compiler.disable
+def sageattn_block_sparse(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    block_map,
+    tensor_layout: str = "HND",
+    sm_scale: Optional[float] = None,
+    pv: str = "fp16",
+    qk_quant_gran: str = "per_thread",
+    smooth_k: bool = True,
+    return_lse: bool = False,
+    is_causal: bool = False,
+):
+    """SageAttention over the active 128x64 tiles of a block map (SpargeAttn's ``mask_id`` geometry): ``block_map[b,h,i,j]``
+    non-zero means query rows [128 i, 128 i + 128) of head h attend keys [64 j, 64 j + 64); tiles that are off are neither
+    read nor computed.  ``block_map`` is a bool/uint8 tensor [B|1, Hq|1, ceil(M/128), ceil(N/64)] or a plan from
+    ``block_sparse_plan``.  Non-causal; ``pv`` ("fp16" | "fp8") is explicit.  Rows of a q-block without any active tile are
+    defined: o = 0, lse = -inf.  Same pre-passes and the same kernel loop as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda``."""
+    if is_causal:  # accepted only to be refused by name: unknown keywords are a TypeError
+        raise ValueError("sageattn_block_sparse is non-causal: express the causal structure in the block map")
+    if pv not in ("fp16", "fp8"):
+        raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
+    if qk_quant_gran not in ("per_warp", "per_thread"):
+        raise ValueError("qk_quant_gran must be either 'per_warp' or 'per_thread'.")
+    B, Hq, M, _ = L.dims(q, tensor_layout)
+    N = L.dims(k, tensor_layout)[2]
+    if isinstance(block_map, BlockSparsePlan):
+        if (block_map.B, block_map.Hq, block_map.M, block_map.N) != (B, Hq, M, N):
+            raise ValueError(f"the plan was made for (B, Hq, M, N) = {(block_map.B, block_map.Hq, block_map.M, block_map.N)}, "
+                             f"the call has {(B, Hq, M, N)}")
+        need = (B * Hq * ((M + 127) // 128) * (((1 + (N + 63) // 64 + 5) + 3) // 4 * 4))
+        if block_map.lists.dtype != torch.int32 or block_map.lists.numel() != need or not block_map.lists.is_contiguous():
+            raise ValueError(f"the plan's lists must be {need} contiguous int32, as block_sparse_plan makes them")
+        map_dev = block_map.lists.device
+    else:
+        block_map = _check_block_map(block_map, B, Hq, M, N)
+        map_dev = block_map.device
+    if map_dev != q.device:
+        raise ValueError(f"block_map is on {map_dev}, q on {q.device}")
+    dtype = _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        plan = block_map if isinstance(block_map, BlockSparsePlan) else block_sparse_plan(block_map, M, N)
+        v_scale = None
+        if pv == "fp8" and smooth_k and k.shape == v.shape:
+            gran, rnd = _k_pairing(qk_quant_gran)
+            k8, ks, km, v, v_scale = kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0)
+        else:
+            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
+            if pv == "fp8":
+                v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
+        o = torch.empty(q.size(), dtype=dtype, device=q.device)
+        lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
+                          pv == "fp8", plan=plan)
+        o = o[..., :head_dim_og]
+        return (o, lse) if return_lse else o

@@ -32,9 +32,13 @@ struct AttnParams {
   // attn_mask of sageattn_qk_int8_pv_fp16_triton (core.py:306-318; kernels attn_qk_int8_per_block.py:33-52):
   // [B,H,M,N] view with element strides (0 = broadcast); kind 1 = bool (False -> -1e6), 2 = fp16, 3 = bf16 (added to
   // the base-2 logits, exactly as the reference adds it after its sm_scale*log2e scaling)
-  const uint8_t* mask;
+  // (block-sparse attention has no attn_mask form: its list descriptor shares the two words, so the parameter block of the
+  //  dense kernels keeps its size and layout)
+  // bs_lists / bs_row: the tile lists of sage_block_map_compact, one row of bs_row int32 per (b, h_q, 128-row q-block):
+  // [count, tile_0 < tile_1 < ..., kBlockListPad copies of the last tile]
+  union { const uint8_t* mask; const int* bs_lists; };
   int64_t msb, msh, msm, msn;
-  int mask_kind;
+  union { int mask_kind; int bs_row; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
   // (b, h_kv) in k8 and in v (always set by run_attn; the dense defaults are 64 rows), and the strides of k_scale
   // (floats) per batch, kv head and 64-key tile.  Sequence-parallel exchange buffers are tile-major: tile j of every
@@ -45,6 +49,12 @@ struct AttnParams {
   int kv_tiled;  // non-default tile strides
   int o_vec16;   // every output row starts on a 16-byte boundary (all strides multiples of 8 elements): 16-byte stores
 };
+
+// entries a list row holds beyond its tiles: the deepest read-ahead of the attention loop (the four-slot ring copies K four
+// positions ahead and requests that entry one iteration earlier)
+constexpr int kBlockListPad = 5;
+// int32 entries per list row for N keys: the count, ceil(N/64) tiles, the pad; rounded up so that every row starts on 16 bytes
+constexpr int64_t block_list_row(int N) { return ((1 + ((int64_t)N + 63) / 64 + kBlockListPad) + 3) & ~(int64_t)3; }
 
 // v_max_f32 on values that are never signalling NaNs: fmaxf() makes hipcc canonicalise both operands first
 // (v_max_f32 x, x, x), two extra instructions on a kernel bound by the vector issue port
@@ -117,6 +127,13 @@ __device__ __forceinline__ float4 uniform_load4(const float* ptr) {
   return make_float4(v[0], v[1], v[2], v[3]);
 #else
   return make_float4(0.f, 0.f, 0.f, 0.f);
+#endif
+}
+__device__ __forceinline__ int uniform_load_i32(const int* ptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const __attribute__((address_space(4))) int*)(ptr);
+#else
+  return 0;
 #endif
 }
 __device__ __forceinline__ float uniform_load1(const float* ptr) {

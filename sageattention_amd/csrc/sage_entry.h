@@ -105,6 +105,9 @@ struct AttnOptions {
   const int64_t* mask_strides = nullptr;
   const sage_kv_layout* kvl = nullptr;  // tile-major K / V buffers
   int nwaves = 0;             // waves per workgroup (4 or 8); 0 = the thread's SAGE_TUNE_NWAVES if set, else the measured choice
+  bool block_sparse = false;  // block-sparse form: the tile lists of sage_block_map_compact and the size of their buffer
+  const int32_t* block_lists = nullptr;
+  int64_t block_lists_bytes = 0;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -112,12 +115,19 @@ struct AttnCall {
   AttnParams p;
   int D, nwaves;
   bool pv_fp8, causal, kthread, v_bf16;
+  bool sparse;  // attn_i8_blocksparse_kernel (always 4 waves)
 };
 int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
                const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
                const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
                int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt = AttnOptions());
 int attn_launch(const AttnCall& c, hipStream_t st);
+
+// ---- block-sparse tile lists (sage_misc.hip) ---------------------------------------------------------------------------
+// bytes of the lists of one call: a row of block_list_row(N) int32 per (b, h_q, 128-row q-block)
+inline int64_t block_sparse_bytes(int B, int Hq, int M, int N) {
+  return (int64_t)B * Hq * (((int64_t)M + 127) / 128) * block_list_row(N) * 4;
+}
 
 // ---- sage_finish_lse (sage_misc.hip) ------------------------------------------------------------------------------------
 struct FinishLseCall {

@@ -96,6 +96,33 @@ __global__ __launch_bounds__(256) void finish_lse_kernel(const float* __restrict
   out[i] = v;
 }
 
+// Block map -> per-(b, h, q-block) lists of active 64-key tiles (the operand of the block-sparse attention kernels).  One
+// wave per list row: 64 map entries per step, ballot + prefix popcount give every active tile its slot, so the list ascends
+// and the result is deterministic (no atomics).  The rest of the row is filled with the last active tile (kBlockListPad
+// entries at least): the attention loop reads ahead of the list's end without a clamp.
+__global__ __launch_bounds__(256) void block_map_compact_kernel(const uint8_t* __restrict__ map, int64_t sb, int64_t sh,
+                                                                int64_t si, int64_t sj, int64_t rows, int Hq, int nqb,
+                                                                int ntk, int row_ints, int* __restrict__ lists) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int qb = (int)(row % nqb);
+  const int64_t bh = row / nqb;
+  const uint8_t* m = map + (bh / Hq) * sb + (bh % Hq) * sh + qb * si;
+  int* out = lists + row * row_ints;
+  int count = 0, last = 0;
+  for (int j0 = 0; j0 < ntk; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j < ntk && m[(int64_t)j * sj] != 0;
+    const uint64_t bal = __ballot(on);
+    if (on) out[1 + count + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+    count += __popcll(bal);
+    if (bal) last = j0 + 63 - __clzll((long long)bal);
+  }
+  for (int i = 1 + count + lane; i < row_ints; i += 64) out[i] = last;
+  if (lane == 0) out[0] = count;
+}
+
 int finish_lse_check(FinishLseCall& c, const float* lse2, const float* corr, float sm_scale, float* lse_out, int64_t n) {
   if (!lse2 || !lse_out || n <= 0) return SAGE_ERR_INVALID_ARGUMENT;
   c = FinishLseCall{lse2, corr, sm_scale, lse_out, n};
@@ -178,6 +205,28 @@ extern "C" int sage_merge_attn_states_multi_ex(const void* const* o_blks, const 
 extern "C" int sage_merge_attn_states_multi(const void* const* o_blks, const float* const* lse_blks, int count, int o_dtype,
                                            void* o_out, float* lse_out, int64_t rows, int D, sage_stream_t stream) {
   return sage_merge_attn_states_multi_ex(o_blks, lse_blks, count, o_dtype, o_out, lse_out, rows, D, 1.0f, nullptr, 0.f, stream);
+}
+
+extern "C" size_t sage_block_sparse_workspace_bytes(int B, int Hq, int M, int N) {
+  if (B <= 0 || Hq <= 0 || M <= 0 || N <= 0) return 0;
+  return (size_t)block_sparse_bytes(B, Hq, M, N);
+}
+
+extern "C" int sage_block_map_compact(const void* block_map, const int64_t* map_strides, int B, int Hq, int M, int N,
+                                      int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream) {
+  if (!block_map || !map_strides || !block_lists || !aligned16(block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (B <= 0 || Hq <= 0 || M <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < 4; ++i)
+    if (map_strides[i] < 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (block_lists_bytes < block_sparse_bytes(B, Hq, M, N)) return SAGE_ERR_INVALID_ARGUMENT;
+  const int nqb = (M + 127) / 128, ntk = (N + 63) / 64;
+  const int64_t rows = (int64_t)B * Hq * nqb;
+  if ((rows + 3) / 4 >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
+  launch_begin();
+  hipLaunchKernelGGL(block_map_compact_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)block_map, map_strides[0], map_strides[1], map_strides[2], map_strides[3], rows, Hq, nqb,
+                     ntk, (int)block_list_row(N), (int*)block_lists);
+  return launch_status();
 }
 
 extern "C" int sage_finish_lse(const float* lse2, const float* corr, float sm_scale, float* lse_out, int64_t n,

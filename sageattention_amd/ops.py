@@ -4,17 +4,19 @@ instead of breaking the graph.  The reference marks every entry
 
     torch.ops.sageattention_amd.attn(q, k, v, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran) -> o
     torch.ops.sageattention_amd.attn_lse(...) -> (o, lse)
+    torch.ops.sageattention_amd.attn_block_sparse(q, k, v, block_map, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
+    torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, block_lists, plan_shape, ...) -> o   (a compacted plan)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
 keyword-friendly wrapper with the reference's signature."""
-from typing import Any, Optional, Tuple
+from typing import Any, Optional, Sequence, Tuple
 
 import torch
 
 from . import core
 
-__all__ = ["sageattn_compilable"]
+__all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable"]
 
 
 def _entry(pv: str):
@@ -54,6 +56,49 @@ def _(q, k, v, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran):
     else:
         B, M, H = q.shape[0], q.shape[1], q.shape[2]
     return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse", mutates_args=())
+def attn_block_sparse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, tensor_layout: str,
+                      sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_block_sparse(q, k, v, block_map, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_block_sparse.register_fake
+def _(q, k, v, block_map, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_plan", mutates_args=())
+def attn_block_sparse_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_lists: torch.Tensor,
+                           plan_shape: Sequence[int], tensor_layout: str, sm_scale: float, pv: str,
+                           qk_quant_gran: str) -> torch.Tensor:
+    # a plan travels as its lists and the (B, Hq, M, N) it was compacted for, which the operator checks against the call
+    plan = core.BlockSparsePlan(block_lists, *(int(x) for x in plan_shape))
+    return core.sageattn_block_sparse(q, k, v, plan, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_block_sparse_plan.register_fake
+def _(q, k, v, block_lists, plan_shape, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map,
+                                     tensor_layout: str = "HND", sm_scale: Optional[float] = None, pv: str = "fp16",
+                                     qk_quant_gran: str = "per_thread"):
+    """``sageattn_block_sparse`` (core.py) as a traceable custom op; ``block_map`` is the map tensor or a plan."""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if sm_scale is None:
+        sm_scale = q.size(-1) ** -0.5
+    if isinstance(block_map, core.BlockSparsePlan):
+        p = block_map
+        return torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, p.lists, [p.B, p.Hq, p.M, p.N], tensor_layout,
+                                                                  float(sm_scale), pv, qk_quant_gran)
+    return torch.ops.sageattention_amd.attn_block_sparse(q, k, v, block_map, tensor_layout, float(sm_scale), pv,
+                                                         qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
