@@ -431,6 +431,40 @@ int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dtype, const 
                                        int is_causal, int qk_gran, int warpq, float sm_scale,
                                        const int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream);
 
+/* ==== block-map predictor (new: makes the tile lists above from Q and K at run time, after SpargeAttn's first stage --
+ * pooled scores gated by the self-similarity of the blocks.  The reference has no counterpart; the rule below is this
+ * library's own statement).  Non-causal.  All arithmetic is fp32; inputs are finite. ====
+ *
+ * Block statistics of x [B,H,N,D] fp16/bf16 for blocks of blk rows (the last one may be ragged; c = its row count), with
+ * x'_r = float(x_r) - float(mean) (mean: optional [B,H,D], dtype of x, contiguous, 16-byte aligned):
+ *   pooled[b,h,i,:] = (sum_r x'_r) / c                      fp32 [B,H,ceil(N/blk),D] contiguous, 16-byte aligned
+ *   sim[b,h,i]      = |sum_r x'_r / |x'_r| |^2 / c^2        fp32 [B,H,ceil(N/blk)]   contiguous
+ * sim is the mean of the c x c matrix of cosines between the rows of the block (1 = all rows parallel), taken without
+ * forming the matrix; a row of zero norm contributes the zero vector.  blk in {64,128}; D in {64,128}; x as the k of
+ * sage_k_mean.  One pass over x, deterministic (fixed summation order, no atomics).  Q is pooled with blk = 128 and no mean,
+ * K with blk = 64 and mean = the smoothing mean km of the K quantizer: without it every K block looks self-similar, because
+ * all rows share the mean. */
+int sage_block_pool_sim(const sage_tensor* x, int dtype, int B, int H, int N, int D, int blk, const void* mean,
+                        float* pooled, float* sim, sage_stream_t stream);
+
+/* Selection, per query head h_q (kv head h_k = h_q / (Hq/Hk)) and q-block i, from the statistics of Q (blk 128, M rows) and K
+ * (blk 64, N rows), with the per-head thresholds simthreshd1[h_q] and cdfthreshd[h_q] (fp32 [Hq], device memory):
+ *   key block j is ELIGIBLE if sim_k[b,h_k,j] > simthreshd1, q-block i SELF-SIMILAR if sim_q[b,h_q,i] > simthreshd1;
+ *   p = softmax over the eligible j of sm_scale * dot(pooled_q[b,h_q,i], pooled_k[b,h_k,j]);
+ *   SELECTED = the shortest prefix of the eligible j in descending p (ties: the lower j first) whose sum is
+ *   >= cdfthreshd * sum(p); never empty when an eligible block exists; cdfthreshd >= 1 selects every eligible block;
+ *   tile (i, j) is ON if j is selected, or j is not eligible, or i is not self-similar (blocks whose rows disagree cannot be
+ *   summarised by their mean, so they are always computed).  Every q-block keeps at least one tile.
+ * block_lists receives exactly what sage_block_map_compact writes for that map (same sizes and alignment:
+ * sage_block_sparse_workspace_bytes(B,Hq,M,N)); block_map (optional) receives the map itself, uint8 [B,Hq,ceil(M/128),
+ * ceil(N/64)] contiguous.  One wave per list row; deterministic, no atomics.  The row of p is kept in LDS: at most
+ * SAGE_SPARGE_MAX_KEY_TILES key blocks (N <= 131072), SAGE_ERR_TOO_LARGE beyond.  sm_scale positive and finite. */
+#define SAGE_SPARGE_MAX_KEY_TILES 2048
+int sage_block_select_cdf(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                          int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                          const float* cdfthreshd, int32_t* block_lists, int64_t block_lists_bytes,
+                          uint8_t* block_map, sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

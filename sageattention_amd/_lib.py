@@ -114,6 +114,9 @@ SIGNATURES = {
     "sage_attn_fusedq_pv_f8_blocksparse": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_float, c_void_p, c_int64, c_void_p]),
+    "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

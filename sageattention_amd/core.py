@@ -16,11 +16,11 @@ import torch
 
 from . import _lib as L
 from . import _qattn
-from .quant import _quant, k_mean, k_smooth_quant, kv_prepare_fp8, per_channel_fp8, sub_mean
+from .quant import _quant, block_pool_sim, k_mean, k_smooth_quant, kv_prepare_fp8, per_channel_fp8, sub_mean
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
-           "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan"]
+           "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan"]
 
 
 def _common_checks(q, k, v):
@@ -588,3 +588,101 @@ def sageattn_block_sparse(
                           pv == "fp8", plan=plan)
         o = o[..., :head_dim_og]
         return (o, lse) if return_lse else o
+
+
+# ---- block-map predictor -----------------------------------------------------------------------------------------------------
+def _per_head(value, Hq, device, name):
+    """A threshold as the fp32 [Hq] device tensor the selection kernel reads: a float is broadcast, a tensor checked."""
+    if isinstance(value, torch.Tensor):
+        if tuple(value.shape) != (Hq,):
+            raise ValueError(f"{name} must be a float or a tensor of shape [Hq={Hq}], got {tuple(value.shape)}")
+        return value.to(device=device, dtype=torch.float32).contiguous()
+    return torch.full((Hq,), float(value), dtype=torch.float32, device=device)
+
+
+def _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, want_map):
+    """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select_cdf -> (plan, uint8
+    map or None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
+    B, Hq, M, D = L.dims(q, tensor_layout)
+    _, Hk, N, _ = L.dims(k, tensor_layout)
+    if Hq % Hk != 0:
+        raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
+    thr = _per_head(simthreshd1, Hq, q.device, "simthreshd1")
+    cdf = _per_head(cdfthreshd, Hq, q.device, "cdfthreshd")
+    pq, sq = block_pool_sim(q, 128, tensor_layout)
+    pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
+    lib = L.lib()
+    lists = torch.empty(lib.sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4, dtype=torch.int32, device=q.device)
+    bmap = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.uint8, device=q.device) if want_map else None
+    L.check(lib.sage_block_select_cdf(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
+                                      float(sm_scale), thr.data_ptr(), cdf.data_ptr(), lists.data_ptr(), lists.numel() * 4,
+                                      L.ptr(bmap), L.stream_ptr(q.device)), "sage_block_select_cdf")
+    return BlockSparsePlan(lists, B, Hq, M, N), bmap
+
+
+def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", simthreshd1=0.6, cdfthreshd=0.98,
+                sm_scale: Optional[float] = None, km: Optional[torch.Tensor] = None, return_map: bool = False):
+    """Predict the block map of ``sageattn_block_sparse`` from Q and K (the rule: include/sageattn_hip.h,
+    sage_block_select_cdf): pooled 128-row q-blocks against pooled 64-row key blocks of ``k - km``, per q-block the fewest key
+    blocks that hold ``cdfthreshd`` of the softmax mass, and every tile of a block whose rows are not alike (mean cosine
+    similarity <= ``simthreshd1``).  Thresholds are floats or fp32 tensors [Hq]; ``km`` defaults to ``k_mean(k)``, the
+    smoothing mean of the K quantizer.  Returns a ``BlockSparsePlan``, with ``return_map=True`` also the bool map
+    [B,Hq,ceil(M/128),ceil(N/64)].  Non-causal."""
+    assert q.is_cuda, "Input tensors must be on cuda."
+    assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
+    assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
+    with torch.cuda.device(q.device):
+        q, k, _, head_dim_og = _pad_head_dim(q, k, k)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        if km is None:
+            km = k_mean(k, tensor_layout)
+        else:
+            km = torch.nn.functional.pad(km, (0, k.size(-1) - km.size(-1))).to(k.dtype).contiguous()
+        plan, bmap = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, return_map)
+    return (plan, bmap.view(torch.bool)) if return_map else plan
+
+
+@torch.compiler.disable
+def sageattn_sparge(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    tensor_layout: str = "HND",
+    simthreshd1=0.6,
+    cdfthreshd=0.98,
+    sm_scale: Optional[float] = None,
+    pv: str = "fp16",
+    qk_quant_gran: str = "per_thread",
+    return_lse: bool = False,
+    return_plan: bool = False,
+):
+    """``sageattn_block_sparse`` on the block map that ``sparge_plan`` predicts for this q and k: the K (or K + V) pre-pass
+    runs once, the predictor uses its smoothing mean, and the block-sparse attention kernel reads the predicted lists.
+    Bit-identical to ``sageattn_block_sparse(q, k, v, sparge_plan(q, k, ...))``.  Returns o, then the LSE with
+    ``return_lse``, then the ``BlockSparsePlan`` with ``return_plan``.  Non-causal."""
+    if pv not in ("fp16", "fp8"):
+        raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
+    if qk_quant_gran not in ("per_warp", "per_thread"):
+        raise ValueError("qk_quant_gran must be either 'per_warp' or 'per_thread'.")
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    dtype = _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        v_scale = None
+        if pv == "fp8" and k.shape == v.shape:
+            gran, rnd = _k_pairing(qk_quant_gran)
+            k8, ks, km, v, v_scale = kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0)
+        else:
+            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
+            if pv == "fp8":
+                v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
+        plan, _ = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, False)
+        o = torch.empty(q.size(), dtype=dtype, device=q.device)
+        lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
+                          pv == "fp8", plan=plan)
+        out = (o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((plan,) if return_plan else ())
+        return out if len(out) > 1 else out[0]

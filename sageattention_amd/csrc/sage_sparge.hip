@@ -1,0 +1,347 @@
+// Block-map predictor (SpargeAttn-style): which 128x64 tiles of a block-sparse attention call are
+// worth computing, decided at run time from Q and K.
+//   block_pool_sim_kernel   per block of BLK rows: the mean row and the mean pairwise cosine similarity ("self-similarity")
+//                           of its rows.  One pass over the tensor, HBM-bound.
+//   block_select_kernel     per (b, h_q, q-block): softmax of the pooled scores over the self-similar key blocks, the
+//                           shortest descending prefix that holds cdfthreshd of its mass, written as the tile list the
+//                           block-sparse attention kernels read (and optionally as a map).
+// The rule itself is stated in include/sageattn_hip.h.
+#include "sage_entry.h"
+
+namespace sage {
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_lane_f(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+}
+// sum over the TPR (8 or 16) consecutive lanes that hold one row.  Every step adds a lane's value to its partner's, so both
+// partners -- and at the end all TPR lanes -- hold the same bits (a + b = b + a).
+template <int TPR>
+__device__ __forceinline__ float row_lanes_sum(float a) {
+  static_assert(TPR == 8 || TPR == 16, "a row is 8 or 16 lanes");
+  a += dpp_lane_f<0xB1>(a);   // quad_perm [1,0,3,2]
+  a += dpp_lane_f<0x4E>(a);   // quad_perm [2,3,0,1]
+  a += dpp_lane_f<0x141>(a);  // row_half_mirror: the other quad of the 8 lanes
+  if constexpr (TPR == 16) a += dpp_lane_f<0x140>(a);  // row_mirror: the other half of the 16 lanes
+  return a;
+}
+// xor butterflies over the wave: every lane ends with the same bits
+__device__ __forceinline__ float wave_sum(float a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+  return a;
+}
+__device__ __forceinline__ float wave_max(float a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+  return a;
+}
+__device__ __forceinline__ int wave_sum_i(int a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------
+// block statistics
+// ------------------------------------------------------------------------------------------------
+struct PoolParams {
+  const uint16_t* x;
+  int64_t sb, sh, sn;
+  const uint16_t* mean;  // [B,H,D] or null
+  float* pooled;         // [B,H,nblk,D]
+  float* sim;            // [B,H,nblk]
+  int H, N, nblk;
+  int per_wg, chunks;    // blocks per workgroup, workgroups per head
+};
+
+// A workgroup walks per_wg consecutive blocks of one head.  D/8 threads hold a row (16 bytes each), 256/(D/8) rows per pass,
+// BLK rows = NP loads per thread, all issued before the first use; the next block's rows are requested as soon as this
+// block's are unpacked and fly during its reduction.  Rows past the end re-read the last row of the tensor (a valid address)
+// and enter the sums through selects, so the ragged block costs no branch around a load.
+// Summation order (fixed, so results are deterministic): a row's squared norm over the 8 channels of a thread and then
+// over the row's lanes; a channel's sums over a thread's NP rows, then over the RPP thread rows in LDS; sim over the 64
+// lanes of wave 0.  Zero rows (past the end, or a zero vector) add exact zeros.
+template <int D, int BLK, bool BF16>
+__global__ __launch_bounds__(256) void block_pool_sim_kernel(const PoolParams p) {
+  constexpr int TPR = D / 8, RPP = 256 / TPR, NP = BLK / RPP;
+  static_assert(NP >= 1, "block too small");
+  __shared__ float red[2][RPP][D + 1];
+  __shared__ float ssum[D];
+  const int chunk = (int)(blockIdx.x % (unsigned)p.chunks);
+  const int64_t bh = blockIdx.x / (unsigned)p.chunks;
+  const int h = (int)(bh % p.H);
+  const int64_t b = bh / p.H;
+  const int tr = threadIdx.x / TPR, tc = threadIdx.x % TPR;
+  const uint16_t* xbase = p.x + b * p.sb + h * p.sh + tc * 8;
+  float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (p.mean) unpack8<BF16>(*reinterpret_cast<const uint4*>(p.mean + bh * D + tc * 8), m);
+  const int blk0 = chunk * p.per_wg, blk1 = min(blk0 + p.per_wg, p.nblk);  // the host launches no empty workgroup
+  const int last = p.N - 1;
+  uint4 raw[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i)
+    raw[i] = *reinterpret_cast<const uint4*>(xbase + (int64_t)min(blk0 * BLK + i * RPP + tr, last) * p.sn);
+  for (int blk = blk0; blk < blk1; ++blk) {
+    float f[NP][8];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      unpack8<BF16>(raw[i], f[i]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[i][j] -= m[j];
+    }
+    if (blk + 1 < blk1) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+        raw[i] = *reinterpret_cast<const uint4*>(xbase + (int64_t)min((blk + 1) * BLK + i * RPP + tr, last) * p.sn);
+    }
+    float accx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, accu[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const bool valid = blk * BLK + i * RPP + tr <= last;
+      float nsq = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) nsq = __builtin_fmaf(f[i][j], f[i][j], nsq);
+      nsq = row_lanes_sum<TPR>(nsq);
+      const float inv = valid && nsq > 0.f ? rsqrtf(nsq) : 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        accx[j] += valid ? f[i][j] : 0.f;
+        accu[j] = __builtin_fmaf(f[i][j], inv, accu[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      red[0][tr][tc * 8 + j] = accx[j];
+      red[1][tr][tc * 8 + j] = accu[j];
+    }
+    __syncthreads();
+    const int c = min(BLK, p.N - blk * BLK);
+    const int64_t oblk = bh * p.nblk + blk;
+    if (threadIdx.x < 2 * D) {  // the first D threads finish the mean, the next D the sum of unit rows
+      const int which = threadIdx.x / D, d = threadIdx.x % D;
+      float s = 0.f;
+      for (int r = 0; r < RPP; ++r) s += red[which][r][d];  // fixed order
+      if (which == 0) p.pooled[oblk * D + d] = s / (float)c;
+      else ssum[d] = s;
+    }
+    __syncthreads();  // also: every read of `red` is done before the next block's writes
+    if (threadIdx.x < 64) {
+      float v = ssum[threadIdx.x] * ssum[threadIdx.x];
+      if constexpr (D == 128) v = __builtin_fmaf(ssum[threadIdx.x + 64], ssum[threadIdx.x + 64], v);
+      v = wave_sum(v);
+      if (threadIdx.x == 0) p.sim[oblk] = v / (float)(c * c);
+    }
+    // wave 0 reads ssum before it arrives at the next block's first barrier; the others write it only behind that barrier
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// selection
+// ------------------------------------------------------------------------------------------------
+struct SelectParams {
+  const float *pq, *sq, *pk, *sk;  // [B,Hq,nqb,D], [B,Hq,nqb], [B,Hk,ntk,D], [B,Hk,ntk]
+  const float *thr, *cdf;          // [Hq]
+  int* lists;
+  uint8_t* map;  // [B,Hq,nqb,ntk] or null
+  int64_t rows;
+  int Hq, Hk, nqb, ntk, row_ints;
+  float sm_scale;
+};
+
+// orders a wave's LDS writes before its own later reads of other lanes' words (one wave owns a row: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One wave per list row (b, h_q, q-block), four rows per workgroup (mostly q-blocks of one head: their reads of pooled K
+// meet in the CU's cache); the row's p lives in the wave's quarter of LDS.
+//  1. scores: 8 lanes per key block, each D/8 channels as float4 (a 128-byte run per 8 lanes), summed over the 8 lanes.
+//  2. p = exp(s - max) over the eligible blocks (ineligible ones hold -1: negative as a float and as an int).
+//  3. the prefix without a sort: p >= 0 orders like its bit pattern, so bisect on the pattern t for the largest t with
+//     sum{p >= t} >= cdfthreshd * sum p (about 30 wave-reduced sums).  That t is one of the p; everything above it is
+//     selected, and of the blocks equal to it the lowest indices, as many as the threshold still needs (one at least).
+//  4. emission as block_map_compact_kernel: ballot + prefix popcount, ascending, the tail padded with the last tile.
+// Every sum runs in a fixed order and every decision is taken on values all lanes hold alike: deterministic, no atomics.
+template <int D>
+__global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p) {
+  extern __shared__ float prow_all[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  if (row >= p.rows) return;
+  float* prow = prow_all + (int64_t)w * p.ntk;
+  const int ntk = p.ntk;
+  const int64_t bh = row / p.nqb;
+  const int hq = (int)(bh % p.Hq);
+  const int64_t b = bh / p.Hq;
+  const int64_t bhk = b * p.Hk + hq / (p.Hq / p.Hk);
+  const float thr = p.thr[hq], cdf = p.cdf[hq];
+  // a q-block that is not self-similar, or a threshold of 1 and above (or NaN), keeps every tile
+  bool all_on = !(p.sq[row] > thr) || !(cdf < 1.0f);
+  float mx = -INFINITY;
+  if (!all_on) {
+    const int sub = lane & 7, g = lane >> 3;
+    const float* pk = p.pk + bhk * ntk * D;
+    const float* sk = p.sk + bhk * ntk;
+    float4 q4[D / 32];
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) q4[i] = *reinterpret_cast<const float4*>(p.pq + row * D + (i * 8 + sub) * 4);
+    constexpr int U = 2;  // key blocks per lane group and step: all their loads are issued before the first use
+    for (int j0 = 0; j0 < ntk; j0 += 8 * U) {
+      float4 k4[U][D / 32];
+      float skv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int jc = min(j0 + 8 * u + g, ntk - 1);  // past the end: the last block again, not stored
+#pragma unroll
+        for (int i = 0; i < D / 32; ++i) k4[u][i] = *reinterpret_cast<const float4*>(pk + (int64_t)jc * D + (i * 8 + sub) * 4);
+        skv[u] = sk[jc];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int j = j0 + 8 * u + g;
+        float dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < D / 32; ++i) {
+          dot = __builtin_fmaf(q4[i].x, k4[u][i].x, dot);
+          dot = __builtin_fmaf(q4[i].y, k4[u][i].y, dot);
+          dot = __builtin_fmaf(q4[i].z, k4[u][i].z, dot);
+          dot = __builtin_fmaf(q4[i].w, k4[u][i].w, dot);
+        }
+        dot = row_lanes_sum<8>(dot);
+        if (sub == 0 && j < ntk) prow[j] = skv[u] > thr ? dot * p.sm_scale : -INFINITY;
+      }
+    }
+    wave_lds_sync();
+    for (int j = lane; j < ntk; j += 64) mx = fmaxf(mx, prow[j]);
+    mx = wave_max(mx);
+    all_on = mx == -INFINITY;  // no eligible key block: every tile is forced on
+  }
+  int tbits = 0, take = 0;
+  if (!all_on) {
+    float tot = 0.f;
+    for (int j = lane; j < ntk; j += 64) {  // each lane rewrites the words it read
+      const float s = prow[j];
+      const float pj = s == -INFINITY ? -1.0f : expf(s - mx);
+      prow[j] = pj;
+      tot += fmaxf(pj, 0.f);
+    }
+    wave_lds_sync();
+    const float target = cdf * wave_sum(tot);
+    // sum of the p whose pattern is >= t, in the order of `tot`: skipped terms add exact zeros
+    auto mass_from = [&](int t) {
+      float gsum = 0.f;
+      for (int j = lane; j < ntk; j += 64) {
+        const float pj = prow[j];
+        gsum += __float_as_int(pj) >= t ? pj : 0.f;
+      }
+      return wave_sum(gsum);
+    };
+    int lo = 0, hi = 0x3F800001;  // mass_from(lo) >= target; no p is above 1.0f
+    while (hi - lo > 1) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (mass_from(mid) >= target) lo = mid; else hi = mid;
+    }
+    tbits = lo;
+    const float tstar = __int_as_float(tbits);
+    const float above = mass_from(tbits + 1);
+    int nties = 0;
+    for (int j = lane; j < ntk; j += 64) nties += __float_as_int(prow[j]) == tbits ? 1 : 0;
+    nties = wave_sum_i(nties);
+    take = 1;
+    if (tstar > 0.f) {
+      const float need = ceilf((target - above) / tstar);
+      take = need >= (float)nties ? nties : need > 1.f ? (int)need : 1;
+      if (take > 1 && above + (float)(take - 1) * tstar >= target) --take;
+      if (take < nties && above + (float)take * tstar < target) ++take;
+    }
+  }
+  int* out = p.lists + row * p.row_ints;
+  uint8_t* mrow = p.map ? p.map + row * ntk : nullptr;
+  int count = 0, lastj = 0, ties_before = 0;
+  for (int j0 = 0; j0 < ntk; j0 += 64) {
+    const int j = j0 + lane;
+    const bool in = j < ntk;
+    bool on = in;
+    if (!all_on) {
+      const int pb = in ? __float_as_int(prow[j]) : 0;
+      const bool tie = in && pb == tbits;
+      const uint64_t tbal = __ballot(tie);
+      const int rank = ties_before + __popcll(tbal & ((1ull << lane) - 1ull));
+      ties_before += __popcll(tbal);
+      on = in && (pb < 0 || pb > tbits || (tie && rank < take));
+    }
+    const uint64_t bal = __ballot(on);
+    if (on) out[1 + count + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+    if (mrow && in) mrow[j] = on ? 1 : 0;
+    count += __popcll(bal);
+    if (bal) lastj = j0 + 63 - __clzll((long long)bal);
+  }
+  for (int i = 1 + count + lane; i < p.row_ints; i += 64) out[i] = lastj;
+  if (lane == 0) out[0] = count;
+}
+
+// Blocks per workgroup of the pooling kernel: as many as leave about `target` workgroups for all B*H heads.
+static int blocks_per_wg(int64_t BH, int nblk, int64_t target) {
+  const int64_t per = (BH * nblk + target - 1) / target;
+  return (int)(per < 1 ? 1 : per > nblk ? nblk : per);
+}
+
+}  // namespace sage
+
+using namespace sage;
+
+extern "C" int sage_block_pool_sim(const sage_tensor* x, int dtype, int B, int H, int N, int D, int blk, const void* mean,
+                                   float* pooled, float* sim, sage_stream_t stream) {
+  if (!tensor_ok(x, 8) || !pooled || !sim || !aligned16(pooled) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(D, dtype)) return s;
+  if (blk != 64 && blk != 128) return SAGE_ERR_INVALID_ARGUMENT;
+  if (mean && !aligned16(mean)) return SAGE_ERR_INVALID_ARGUMENT;
+  PoolParams p;
+  p.x = (const uint16_t*)x->data; p.sb = x->stride_b; p.sh = x->stride_h; p.sn = x->stride_n;
+  p.mean = (const uint16_t*)mean; p.pooled = pooled; p.sim = sim;
+  p.H = H; p.N = N; p.nblk = (int)(((int64_t)N + blk - 1) / blk);
+  // eight resident workgroups per CU stream their share of a head each
+  p.per_wg = blocks_per_wg((int64_t)B * H, p.nblk, 256 * 8);
+  p.chunks = (p.nblk + p.per_wg - 1) / p.per_wg;
+  const int64_t grid = (int64_t)B * H * p.chunks;
+  if (grid >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    by_flag(blk == 128, [&](auto big) {
+      by_flag(dtype == SAGE_BF16, [&](auto bf) {
+        hipLaunchKernelGGL((block_pool_sim_kernel<decltype(d)::value, decltype(big)::value ? 128 : 64, decltype(bf)::value>),
+                           dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+      });
+    });
+  });
+  return launch_status();
+}
+
+extern "C" int sage_block_select_cdf(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                                     int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                                     const float* cdfthreshd, int32_t* block_lists, int64_t block_lists_bytes,
+                                     uint8_t* block_map, sage_stream_t stream) {
+  if (!pooled_q || !sim_q || !pooled_k || !sim_k || !simthreshd1 || !cdfthreshd || !block_lists) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!aligned16(pooled_q) || !aligned16(pooled_k) || !aligned16(block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (B <= 0 || Hq <= 0 || Hk <= 0 || Hq % Hk != 0 || M <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
+  if (!(sm_scale > 0.f) || !(sm_scale < INFINITY)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (((int64_t)N + 63) / 64 > SAGE_SPARGE_MAX_KEY_TILES) return SAGE_ERR_TOO_LARGE;  // the p rows of a workgroup in LDS
+  if (block_lists_bytes < block_sparse_bytes(B, Hq, M, N)) return SAGE_ERR_INVALID_ARGUMENT;
+  SelectParams p;
+  p.pq = pooled_q; p.sq = sim_q; p.pk = pooled_k; p.sk = sim_k; p.thr = simthreshd1; p.cdf = cdfthreshd;
+  p.lists = (int*)block_lists; p.map = block_map;
+  p.Hq = Hq; p.Hk = Hk; p.nqb = (M + 127) / 128; p.ntk = (N + 63) / 64; p.row_ints = (int)block_list_row(N);
+  p.rows = (int64_t)B * Hq * p.nqb;
+  p.sm_scale = sm_scale;
+  if ((p.rows + 3) / 4 >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    hipLaunchKernelGGL((block_select_kernel<decltype(d)::value>), dim3((unsigned)((p.rows + 3) / 4)), dim3(256),
+                       (size_t)4 * p.ntk * sizeof(float), (hipStream_t)stream, p);
+  });
+  return launch_status();
+}

@@ -6,6 +6,8 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_lse(...) -> (o, lse)
     torch.ops.sageattention_amd.attn_block_sparse(q, k, v, block_map, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
     torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, block_lists, plan_shape, ...) -> o   (a compacted plan)
+    torch.ops.sageattention_amd.attn_sparge(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
+    torch.ops.sageattention_amd.attn_sparge_lse(...) -> (o, lse)          (the block map predicted from q and k)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -16,7 +18,7 @@ import torch
 
 from . import core
 
-__all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable"]
+__all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable", "sageattn_sparge_compilable"]
 
 
 def _entry(pv: str):
@@ -99,6 +101,51 @@ def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.
                                                                   float(sm_scale), pv, qk_quant_gran)
     return torch.ops.sageattention_amd.attn_block_sparse(q, k, v, block_map, tensor_layout, float(sm_scale), pv,
                                                          qk_quant_gran)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge", mutates_args=())
+def attn_sparge(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, cdfthreshd: torch.Tensor,
+                tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    # the thresholds travel as fp32 [Hq] tensors: per-head values are tensors anyway, and a float is broadcast by the wrapper
+    return core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, cdfthreshd=cdfthreshd,
+                                sm_scale=sm_scale, pv=pv, qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_sparge.register_fake
+def _(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_lse", mutates_args=())
+def attn_sparge_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, cdfthreshd: torch.Tensor,
+                    tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, cdfthreshd=cdfthreshd,
+                                  sm_scale=sm_scale, pv=pv, qk_quant_gran=qk_quant_gran, return_lse=True)
+    return o.contiguous(), lse
+
+
+@attn_sparge_lse.register_fake
+def _(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    if tensor_layout == "HND":
+        B, H, M = q.shape[0], q.shape[1], q.shape[2]
+    else:
+        B, M, H = q.shape[0], q.shape[1], q.shape[2]
+    return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+
+
+def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
+                               simthreshd1=0.6, cdfthreshd=0.98, sm_scale: Optional[float] = None, pv: str = "fp16",
+                               qk_quant_gran: str = "per_thread", return_lse: bool = False):
+    """``sageattn_sparge`` (core.py) as a traceable custom op; thresholds are floats or fp32 tensors [Hq]."""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if sm_scale is None:
+        sm_scale = q.size(-1) ** -0.5
+    Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
+    thr, cdf = (t if isinstance(t, torch.Tensor) else torch.full((Hq,), float(t), dtype=torch.float32, device=q.device)
+                for t in (simthreshd1, cdfthreshd))
+    op = torch.ops.sageattention_amd.attn_sparge_lse if return_lse else torch.ops.sageattention_amd.attn_sparge
+    return op(q, k, v, thr, cdf, tensor_layout, float(sm_scale), pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",

@@ -65,6 +65,21 @@ def k_mean(k: torch.Tensor, tensor_layout: str = "HND") -> torch.Tensor:
     return km
 
 
+def block_pool_sim(x: torch.Tensor, blk: int, tensor_layout: str = "HND", mean: Optional[torch.Tensor] = None):
+    """Block statistics of the block-map predictor (sage_block_pool_sim): per block of ``blk`` (64 | 128) rows of ``x - mean``
+    the mean row, fp32 [B,H,ceil(N/blk),D], and the mean pairwise cosine similarity of its rows, fp32 [B,H,ceil(N/blk)].
+    ``mean``: optional [B,H,D] in x's dtype (the smoothing mean of K)."""
+    B, H, N, D = L.dims(x, tensor_layout)
+    nb = (N + blk - 1) // blk
+    if mean is not None and (tuple(mean.shape) != (B, H, D) or mean.dtype != x.dtype or not mean.is_contiguous()):
+        raise ValueError(f"mean must be a contiguous [B={B}, H={H}, D={D}] tensor of dtype {x.dtype}")
+    pooled = torch.empty((B, H, nb, D), dtype=torch.float32, device=x.device)
+    sim = torch.empty((B, H, nb), dtype=torch.float32, device=x.device)
+    L.check(L.lib().sage_block_pool_sim(L.desc(x, tensor_layout), L.dtype_code(x.dtype), B, H, N, D, blk, L.ptr(mean),
+                                        pooled.data_ptr(), sim.data_ptr(), L.stream_ptr(x.device)), "sage_block_pool_sim")
+    return pooled, sim
+
+
 def k_smooth_quant(k: torch.Tensor, tensor_layout: str, gran: int, rounding: int, dense_heads: bool = True):
     """``km = k.mean(seq)`` (core.py:612) and the INT8 quantization of ``k - km`` (K half of core.py:621-624) as one call
     of the library (sage_k_smooth_quant): bit-identical to ``k_mean`` + ``_quant(..., mean=km)``, two launches at every

@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""The block-map predictor (sage_block_pool_sim, sage_block_select_cdf) measured in ONE process with alternating windows
+(HIP events around `--launches` launches each), on clustered synthetic inputs (tests/sparge_util.py's generator at scale:
+per 128-row q-block / 64-row key block a centre ~ N(0, 4 I), tokens = centre + N(0, I), every 4th q-block and every 5th key
+block pure noise, K shifted by +3 on every channel).
+
+  1. block_pool_sim on K beside sage_k_mean on the same K (k_mean_partial reads the same bytes): time and GB/s from the
+     bytes of the shape.  `--mode kernels` only launches those kernels a few times, for `rocprofv3 --kernel-trace --stats`.
+  2. the predictor (pool Q + pool K + select) as a share of the dense sageattn call and of the resulting sparse call.
+  3. at cdfthreshd 0.9 / 0.95 / 0.98: density of the predicted map, end-to-end sageattn_sparge against dense sageattn, and
+     calc_diff (1 - 2<x,y>/(|x|^2+|y|^2)) of its output against dense sageattn's.
+SYNTHETIC data: the densities and errors say nothing about a real model.
+
+usage: sparge_bench.py [--launches 300] [--shapes c3,wan] [--pv fp16] [--mode all|kernels] [--commit HASH] [--out table.md]"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import sageattention_amd as sa  # noqa: E402
+from sageattention_amd import core, quant  # noqa: E402
+
+SHAPES = {"c3": (4, 32, 8192, 128), "wan": (1, 40, 32760, 128), "small": (2, 4, 2048, 128)}
+ap = argparse.ArgumentParser()
+ap.add_argument("--launches", type=int, default=300)
+ap.add_argument("--shapes", default="c3,wan")
+ap.add_argument("--pv", default="fp16")
+ap.add_argument("--mode", default="all", choices=("all", "kernels"))
+ap.add_argument("--simthreshd1", type=float, default=0.6)
+ap.add_argument("--cdfs", default="0.9,0.95,0.98")
+ap.add_argument("--commit", default="")
+ap.add_argument("--out", default="")
+a = ap.parse_args()
+lines = []
+
+
+def emit(s=""):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def clustered(B, H, n, D, blk, noise_every, offset, gen):
+    nb = (n + blk - 1) // blk
+    c = torch.randn(B, H, nb, 1, D, generator=gen, device="cuda") * 2.0
+    noisy = (torch.arange(nb, device="cuda") % noise_every == noise_every - 1).view(1, 1, nb, 1, 1)
+    c = torch.where(noisy, torch.zeros_like(c), c)
+    x = c + torch.randn(B, H, nb, blk, D, generator=gen, device="cuda")
+    return (x.reshape(B, H, nb * blk, D)[:, :, :n] + offset).half().contiguous()
+
+
+def window(fn, n):
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / n  # ms per call
+
+
+def calc_diff(x, y):
+    x, y = x.double(), y.double()
+    return float(1 - 2 * (x * y).sum() / (x * x + y * y).sum())
+
+
+def spread(ts):
+    return f"median {statistics.median(ts):.4f} ms, min {min(ts):.4f}, max {max(ts):.4f}"
+
+
+emit("# Block-map predictor: times on MI355X")
+emit()
+emit(f"commit {a.commit or 'unknown'}; tools/sparge_bench.py, {a.launches} calls per window, HIP events, one process, windows")
+emit(f"alternating.  fp16, per-thread scales, {a.pv.upper()} PV, simthreshd1 = {a.simthreshd1}.  Clustered SYNTHETIC inputs: densities and")
+emit("errors below describe this generator, not a model.")
+for sname in a.shapes.split(","):
+    B, H, N, D = SHAPES[sname]
+    gen = torch.Generator(device="cuda").manual_seed(N + D)
+    q = clustered(B, H, N, D, 128, 4, 0.0, gen)
+    k = clustered(B, H, N, D, 64, 5, 3.0, gen)
+    v = torch.randn(B, H, N, D, generator=gen, device="cuda").half()
+    km = quant.k_mean(k)
+    nbytes = q.numel() * 2
+
+    def pool_k():
+        quant.block_pool_sim(k, 64, mean=km)
+
+    def pool_q():
+        quant.block_pool_sim(q, 128)
+
+    def kmean():
+        quant.k_mean(k)
+
+    def predict(cdf=0.98):
+        return core._sparge_predict(q, k, km, "HND", a.simthreshd1, cdf, D ** -0.5, False)[0]
+
+    if a.mode == "kernels":
+        for _ in range(20):
+            pool_k(); pool_q(); kmean(); predict()
+        torch.cuda.synchronize()
+        continue
+    emit()
+    emit(f"## {sname} (B, H, N, D) = {(B, H, N, D)}: {nbytes / 1e6:.0f} MB per tensor")
+    emit()
+    emit("| call (host-timed, allocations included) | repeats | ms | GB/s of the tensor's bytes |")
+    emit("|---|---|---|---|")
+    rows = {"block_pool_sim(k - km, 64)": pool_k, "sage_k_mean(k) (partial + final)": kmean, "block_pool_sim(q, 128)": pool_q}
+    ts = {n: [] for n in rows}
+    for _ in range(3):
+        for n, fn in rows.items():
+            ts[n].append(window(fn, a.launches))
+    for n in rows:
+        med = statistics.median(ts[n])
+        emit(f"| {n} | {spread(ts[n])} | {med:.4f} | {nbytes / med / 1e6:.0f} |")
+    emit()
+    emit("| cdfthreshd | density | tiles per q-block min / mean / max | predictor ms | dense sageattn ms | sparse call ms | predictor / dense | "
+         "predictor / sparse | sageattn_sparge ms | speed-up over dense | calc_diff vs dense |")
+    emit("|---|---|---|---|---|---|---|---|---|---|---|")
+    dense_fn = sa.sageattn_qk_int8_pv_fp16_cuda if a.pv == "fp16" else sa.sageattn_qk_int8_pv_fp8_cuda
+    o_dense = dense_fn(q, k, v)
+    dense_all = []
+    for cdf in (float(x) for x in a.cdfs.split(",")):
+        plan, bmap = sa.sparge_plan(q, k, simthreshd1=a.simthreshd1, cdfthreshd=cdf, km=km, return_map=True)
+        cnt = bmap.sum(-1).float()
+        dens = float(bmap.float().mean())
+        t_p = window(lambda: predict(cdf), a.launches)
+        t_d = window(lambda: dense_fn(q, k, v), a.launches)
+        t_s = window(lambda: sa.sageattn_block_sparse(q, k, v, plan, pv=a.pv), a.launches)
+        t_e = window(lambda: sa.sageattn_sparge(q, k, v, simthreshd1=a.simthreshd1, cdfthreshd=cdf, pv=a.pv), a.launches)
+        dense_all.append(t_d)
+        o = sa.sageattn_sparge(q, k, v, simthreshd1=a.simthreshd1, cdfthreshd=cdf, pv=a.pv)
+        emit(f"| {cdf} | {dens:.3f} | {int(cnt.min())} / {float(cnt.mean()):.1f} / {int(cnt.max())} | {t_p:.4f} | {t_d:.4f} | {t_s:.4f} | "
+             f"{t_p / t_d:.4f} | {t_p / t_s:.4f} | {t_e:.4f} | {t_d / t_e:.2f} | {calc_diff(o, o_dense):.3e} |")
+    emit()
+    emit(f"dense sageattn, {len(dense_all)} repeated windows: {spread(dense_all)}")
+    del q, k, v, o_dense
+    torch.cuda.empty_cache()
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
