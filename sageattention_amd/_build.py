@@ -12,7 +12,7 @@ ARCH = "gfx950"
 
 # (source, extra flags).  The quantizers need exact IEEE semantics (bit-exact vs the oracle).
 SOURCES = [
-    ("sage_quant.hip", ["-ffp-contract=off"]),
+    ("sage_quant.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # packed f32 VALU is slower beside MFMAs; contraction off: the fused Q-quantizer prologue must round exactly like
     # K1 (sage_quant.hip) -- the tile loop spells its fmas out (__builtin_fmaf), so it is unaffected
     ("sage_attn.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),

@@ -1,4 +1,4 @@
-// HBM-bound pre-pass kernels of the SageAttention hot path for gfx950:
+// Pre-pass kernels of the SageAttention hot path for gfx950 (every one a single pass over its tensor):
 //   K0  k_mean            (replaces torch k.mean at sageattention/core.py:612)
 //   K1  quant_qk_int8     (replaces QuantInt8Kernel csrc/fused/fused.cu:64-198 and the Triton
 //                          quantizers sageattention/triton/quant_per_{block,thread}.py)
@@ -6,8 +6,14 @@
 //                         head per workgroup with the next block's rows prefetched (k_quant_stream_kernel); with the FP8 V
 //                         quantizer in one launch: kv_quant_kernel / kv_quant_stream_kernel
 //   K2  sub_mean_f16      (replaces SubMeanKernel csrc/fused/fused.cu:200-260)
-// Roofline: HBM. Algorithmic traffic per element: 2 B read + 1 B written (K1), 2 B read (K0).
-// Every thread moves 16 B per load (8 fp16/bf16), the widest coalesced access on CDNA4.
+// Algorithmic traffic per element: 2 B read + 1 B written (K1), 2 B read (K0); every thread moves 16 B per load (8
+// fp16/bf16), the widest coalesced access on CDNA4.  The floor of each kernel is that traffic over the streaming rate of
+// HBM (6.29 TB/s measured), but a quantizer reaches it only while its vector work stays small: at (4,32,8192,128) every
+// vector instruction per element is 3.4-3.9 us of issue time on the whole chip (134 M elements over 1024 SIMDs x 16 lanes
+// at 2.1-2.4 GHz) against a floor of 64 us, with four or five waves per SIMD and a barrier per block to hide it behind.
+// The streaming K quantizer held 27 vector instructions per element outside its exact-division fallback and took 98 us
+// there -- co-limited by vector issue, not by HBM; written for what a dense K call fixes it holds 9 and takes 66 us
+// (profiles/k_quant_valu_diet.md: the instruction census and the in-step traces).
 // Compiled with -ffp-contract=off: the integer outputs must match the oracle bit for bit.
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
@@ -105,20 +111,25 @@ __global__ void k_mean_final_kernel(const float* __restrict__ part, int S, int D
 // (QuantParams, the kernels' parameter block: sage_entry.h)
 
 // max over the TPR (8 or 16) consecutive lanes that hold one row, on DPP (quad swaps, then the mirrored half rows / rows): every
-// lane ends with the row's maximum; 3-4 v_max_f32_dpp instead of as many ds_bpermute round trips.  (A maximum does not depend
-// on the order it is taken in: bit-identical to the xor butterfly.)
+// lane ends with the row's maximum; 3-4 DPP maxima instead of as many ds_bpermute round trips.  The values are finite and
+// non-negative (maxima of |x| that start at 0), so their bit patterns order like the numbers and the maximum is taken on
+// the bits: an integer maximum needs no canonicalising v_max x, x in front, and with every lane a valid source (full row
+// and bank masks, permutations only) the lane move folds into the v_max_u32 as its DPP operand -- ONE instruction per
+// step where fmaxf(a, moved a) cost four (v_mov 0, v_mov_b32_dpp, v_max a, a, v_max).  (A maximum does not depend on the
+// order it is taken in: bit-identical to the xor butterfly.)
 template <int CTRL>
-__device__ __forceinline__ float dpp_lane(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+__device__ __forceinline__ unsigned int dpp_max_u32(unsigned int x) {
+  return max(x, (unsigned int)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xf, 0xf, true));
 }
 template <int TPR>
 __device__ __forceinline__ float row_lanes_max(float a) {
   static_assert(TPR == 8 || TPR == 16, "a row is 8 or 16 lanes");
-  a = fmaxf(a, dpp_lane<0xB1>(a));    // quad_perm [1,0,3,2]
-  a = fmaxf(a, dpp_lane<0x4E>(a));    // quad_perm [2,3,0,1]
-  a = fmaxf(a, dpp_lane<0x141>(a));   // row_half_mirror: the other quad of the 8 lanes
-  if constexpr (TPR == 16) a = fmaxf(a, dpp_lane<0x140>(a));  // row_mirror: the other half of the 16 lanes
-  return a;
+  unsigned int u = __float_as_uint(a);
+  u = dpp_max_u32<0xB1>(u);    // quad_perm [1,0,3,2]
+  u = dpp_max_u32<0x4E>(u);    // quad_perm [2,3,0,1]
+  u = dpp_max_u32<0x141>(u);   // row_half_mirror: the other quad of the 8 lanes
+  if constexpr (TPR == 16) u = dpp_max_u32<0x140>(u);  // row_mirror: the other half of the 16 lanes
+  return __uint_as_float(u);
 }
 
 __device__ __forceinline__ int group_of_row(int lr, int gran, int is_key, int warp_shift) {
@@ -130,7 +141,7 @@ __device__ __forceinline__ int group_of_row(int lr, int gran, int is_key, int wa
   return is_key ? w * 4 + ((lr & 7) >> 1) : w * 8 + (lr & 7);
 }
 
-// ---- the quantizer in three steps, shared by the one-block-per-workgroup kernels and the streaming K quantizer ----
+// ---- the quantizer in three steps (the streaming K quantizer below shares the geometry, the mean and sub_mean8) ----
 template <int D, int BLK>
 struct QuantGeom {
   static constexpr int TPR = D / 8;        // threads per row (16 B each)
@@ -201,17 +212,40 @@ __device__ __forceinline__ uint4 quant_mean_bits(const QuantParams& p, const int
   return mbits;
 }
 
+// x - mean for the 8 elements of one 16-byte load (no mean: mbits = 0 and x - 0 is x in either form).
+//   TRITON: `k - km` in the input dtype (torch).   CUDA: in fp32 (fused.cu).
+// fp16, TRITON: the subtraction runs as v_pk_add_f16 -- the correctly rounded fp16 difference, which is what rounding the
+// fp32 difference of two fp16 values gives as well (24 >= 2*11+2 bits: the double rounding is innocuous) -- 4 packed
+// subtractions + 8 converts per 8 elements instead of 8 + 8 + 16.  mean_f: the mean unpacked (read unless TRITON && !BF16)
+template <bool BF16, bool TRITON>
+__device__ __forceinline__ void sub_mean8(const uint4& raw, const uint4& mbits, const float (&mean_f)[8], float (&xf)[8]) {
+  if constexpr (TRITON && !BF16) {
+    const uint32_t xw[4] = {raw.x, raw.y, raw.z, raw.w}, mw[4] = {mbits.x, mbits.y, mbits.z, mbits.w};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const v2h d = __builtin_bit_cast(v2h, xw[w]) - __builtin_bit_cast(v2h, mw[w]);
+      xf[2 * w] = (float)d[0];
+      xf[2 * w + 1] = (float)d[1];
+    }
+  } else {
+    unpack8<BF16>(raw, xf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      xf[j] = xf[j] - mean_f[j];
+      if constexpr (TRITON) xf[j] = round_to_elem<BF16>(xf[j]);
+    }
+  }
+}
+
 // step 3: block `blk` from its rows: group maxima (gmax: 64 zeroed dwords), ONE barrier, scales, rounding, stores.
-// zero_next: 64 dwords zeroed behind the barrier (the streaming kernel's group maxima of the block after next), or null.
-// after_phase1(): runs when `raw` has been consumed (the streaming kernel reloads it with the next block's rows there)
-template <int D, int BLK, bool BF16, bool TRITON, typename AfterPhase1>
+template <int D, int BLK, bool BF16, bool TRITON>
 __device__ __forceinline__ void quant_block(const QuantParams& p, const int blk, const int h, const int b, const int H, const int N_,
                                             const int64_t o_boff, uint4 (&raw)[QuantGeom<D, BLK>::NP], const uint4 mbits,
-                                            unsigned int* gmax, unsigned int* zero_next, AfterPhase1 after_phase1) {
+                                            unsigned int* gmax) {
   using G = QuantGeom<D, BLK>;
   constexpr int TPR = G::TPR, RPP = G::RPP, NP = G::NP;
-  // (the thread id is made opaque per block: in the streaming kernel's loop hipcc otherwise hoists every row / group /
-  //  address term that depends only on it out of the loop and keeps ~40 registers alive for them)
+  // (the thread id is made opaque: hipcc otherwise computes every row / group / address term that depends only on it up
+  //  front and keeps it alive across the barrier -- several instantiations then lose a wave per SIMD to the registers)
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int tr = tid / TPR, tc = tid % TPR;
@@ -223,11 +257,7 @@ __device__ __forceinline__ void quant_block(const QuantParams& p, const int blk,
     unpack8<BF16>(ud, dvec);
   }
 
-  // x - mean (no mean: mbits = 0 and x - 0 is x in either form), times the multiplier, and the group maxima
-  //   TRITON: `k - km` in the input dtype (torch).   CUDA: in fp32 (fused.cu).
-  // fp16, TRITON: the subtraction runs as v_pk_add_f16 -- the correctly rounded fp16 difference, which is what rounding the
-  // fp32 difference of two fp16 values gives as well (24 >= 2*11+2 bits: the double rounding is innocuous) -- 4 packed
-  // subtractions + 8 converts per 8 elements instead of 8 + 8 + 16.
+  // x - mean (sub_mean8), times the multiplier, and the group maxima
   {
     float mean_f[8];
     if constexpr (!TRITON || BF16) unpack8<BF16>(mbits, mean_f);
@@ -246,22 +276,7 @@ __device__ __forceinline__ void quant_block(const QuantParams& p, const int blk,
         for (int o = 1; o < TPR; o <<= 1) dot += __shfl_xor(dot, o);
         if (tc == 0 && valid) p.dot_out[((int64_t)b * H + h) * p.N + row] = dot;
       }
-      if constexpr (TRITON && !BF16) {
-        const uint32_t xw[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w}, mw[4] = {mbits.x, mbits.y, mbits.z, mbits.w};
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          const v2h d = __builtin_bit_cast(v2h, xw[w]) - __builtin_bit_cast(v2h, mw[w]);
-          xf[i][2 * w] = (float)d[0];
-          xf[i][2 * w + 1] = (float)d[1];
-        }
-      } else {
-        unpack8<BF16>(raw[i], xf[i]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          xf[i][j] = xf[i][j] - mean_f[j];
-          if constexpr (TRITON) xf[i][j] = round_to_elem<BF16>(xf[i][j]);
-        }
-      }
+      sub_mean8<BF16, TRITON>(raw[i], mbits, mean_f, xf[i]);
       float amax = 0.f;
       const float mult_row = valid ? p.mult : 0.f;  // rows past the end contribute zeros (finite inputs: raw is 0 there)
 #pragma unroll
@@ -273,9 +288,7 @@ __device__ __forceinline__ void quant_block(const QuantParams& p, const int blk,
       if (tc == 0) atomicMax(&gmax[group_of_row(lr, p.gran, p.is_key, p.warp_shift)], __float_as_uint(amax));
     }
   }
-  after_phase1();
   __syncthreads();
-  if (zero_next && threadIdx.x < 64) zero_next[threadIdx.x] = 0u;
 
   const int groups_per_blk = p.gran == SAGE_GRAN_PER_BLOCK ? 1
                              : p.gran == SAGE_GRAN_PER_WARP ? BLK >> p.warp_shift
@@ -298,7 +311,7 @@ __device__ __forceinline__ void quant_block(const QuantParams& p, const int blk,
     // and rint() of it is at most 127 in magnitude.
     if constexpr (TRITON) {
       // q = trunc(x/sc + 0.5*sign) with an IEEE division (quant_per_block.py:42-44).  The division costs ~10 VALU
-      // ops per element and made this HBM-bound kernel VALU-bound, so: multiply by the correctly rounded reciprocal
+      // ops per element and made the kernel VALU-bound, so: multiply by the correctly rounded reciprocal
       // (|x*r - x/sc| <= 1.5 ulp <= 2.3e-5 for |x/sc| <= 127, plus <= 7.6e-6 from the +0.5) and fall back to the exact
       // division, for the whole 8-element chunk of the wave, only when some value lands within 2^-14 of a
       // rounding boundary, where the two could differ (~6 % of the chunks).  Bit-exact by construction.
@@ -343,7 +356,7 @@ __device__ __forceinline__ void quant_qk_int8_body(const QuantParams& p, const i
   uint4 raw[QuantGeom<D, BLK>::NP];
   quant_load_rows<D, BLK>(p.x + x_boff + h * p.xsh + (threadIdx.x % (D / 8)) * 8, p.xsn, blk, N_, raw);
   const uint4 mbits = quant_mean_bits<D, BF16>(p, h, b, H, blk == 0, mpart);
-  quant_block<D, BLK, BF16, TRITON>(p, blk, h, b, H, N_, o_boff, raw, mbits, gmax, nullptr, [] {});
+  quant_block<D, BLK, BF16, TRITON>(p, blk, h, b, H, N_, o_boff, raw, mbits, gmax);
 }
 
 // (the rounding flavour is a template parameter: with both flavours in one kernel the register allocation of the shared
@@ -364,28 +377,170 @@ __global__ __launch_bounds__(256, BLK * D <= 64 * 128 ? 7 : 4) void quant_qk_int
 // One barrier per block: the group maxima rotate through three buffers (block i accumulates into buffer i % 3 and, behind
 // its barrier, zeroes buffer (i + 2) % 3 -- last read by block i-1, whose readers have all passed this barrier, and next
 // written by block i+2, behind the barrier of block i+1).
-template <int D, bool BF16, bool TRITON>
-__device__ __forceinline__ void k_quant_stream_body(const QuantParams& p, const int per_wg, const int wg, const int h, const int b,
+//
+// The kernel is limited by vector issue as much as by HBM (profiles/k_quant_valu_diet.md), so its block is written for
+// what a dense K call fixes -- is_key, 64-row blocks in one warp group, no dot_vec, mult == 1 (x * 1 is x: the multiply
+// is gone), granularity per_block or per_thread as a template flag -- instead of going through quant_block:
+//  * a thread's rows 16 i + tr (head_dim 128) or 32 i + tr (64) all fall into ONE group, (tr & 7) >> 1 or 0: one maximum
+//    over all its elements, one DPP reduction and one LDS atomic per block instead of one per pass, and the scale, its two
+//    IEEE divisions included, once per block.  (A maximum does not depend on the order: the same bits.)
+//  * RAGGED (the last block of a head when N % 64 != 0) alone knows rows past the end: they are loaded as copies of row
+//    N - 1, kept out of the maxima (after the subtraction they are not zeros) and not stored.  Full blocks carry no selects.
+
+// the rows of block `blk`; CLAMP: rows past the end read row N - 1 (always in bounds; the caller ignores them)
+template <int D, bool CLAMP>
+__device__ __forceinline__ void k_load_rows(const uint16_t* xbase, const int64_t xsn, const int blk, const int N,
+                                            uint4 (&raw)[QuantGeom<D, 64>::NP]) {
+  using G = QuantGeom<D, 64>;
+  const int row0 = blk * 64 + (int)threadIdx.x / G::TPR;
+#pragma unroll
+  for (int i = 0; i < G::NP; ++i) {
+    const int row = CLAMP ? min(row0 + i * G::RPP, N - 1) : row0 + i * G::RPP;
+    raw[i] = *reinterpret_cast<const uint4*>(xbase + (int64_t)row * xsn);
+  }
+}
+
+// Eight quotients x / sc rounded half away from zero (the Triton quantizers, quant_per_block.py:42-44: an IEEE division,
+// + 0.5 sign, truncation) as two dwords of int8, WITHOUT the division; `near` is set when the chunk must be redone with
+// it.  With r = fl(1 / sc) and M = 1.5 * 2^23, per element
+//     t = fma(x, r, M)      res = fma(x, r, -(t - M))
+// |x r| <= 127 (1 + 2^-22) (x belongs to the group whose maximum made sc), so x r + M lies in [2^23, 2^24), where floats are
+// the integers: the one rounding of the fma makes t = M + n exactly, n the integer nearest to the EXACT product x r, and
+// the low byte of t's bit pattern, 0x4B400000 + n, is n as a two's-complement int8.  t - M = n is exact and res is
+// x r - n to within 2^-25.  The chunk passes when every |res| <= 1/2 - 2^-14.  Then, with e = x / sc exact:
+// |x r - e| <= 2^-24 |e| < 7.7e-6 (r is correctly rounded), so |e - n| < 1/2 - 5.3e-5; the reference's quotient fl(e) is within
+// 7.7e-6 of e and its fl(. +- 0.5) within another 3.9e-6 (half an ulp below 128): the sum lies strictly between n and n + sign
+// and truncates to n.  No clamp: |n| <= 127.  The margin in use, 1.9e-5 of 6.1e-5, leaves the 2^-14 of the contract whole.
+// 3 VALU per element and 1/2 for the test (v_max3 over |res|) against mul, rndne, sub, cmp, cvt and a scalar or; the bytes
+// are picked straight out of t: 3 v_perm_b32 per dword, no conversion to integer, no 16-bit shifts.
+__device__ __forceinline__ uint2 round_half_away_pack8(const float (&x)[8], const float r, bool& near) {
+  constexpr float M = 12582912.f;
+  uint32_t tb[8];
+  float res[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float t = __builtin_fmaf(x[j], r, M);
+    res[j] = __builtin_fmaf(x[j], r, -(t - M));
+    tb[j] = __float_as_uint(t);
+  }
+  float m = fmaxf(fmaxf(fabsf(res[0]), fabsf(res[1])), fabsf(res[2]));
+  m = fmaxf(fmaxf(m, fabsf(res[3])), fabsf(res[4]));
+  m = fmaxf(fmaxf(m, fabsf(res[5])), fabsf(res[6]));
+  m = fmaxf(m, fabsf(res[7]));
+  near = !(m <= 0.5f - 6.1035156e-5f);  // (a NaN is near)
+  return make_uint2(pack_i8x4(tb[0], tb[1], tb[2], tb[3]), pack_i8x4(tb[4], tb[5], tb[6], tb[7]));
+}
+
+// block `blk` of head (b, h) from its rows: as quant_block, for the fixed K form above.  gmax, zero_next: PER_THREAD ? 4 : 1
+// group maxima of this block / of the block after next; after_phase1(): `raw` may be reloaded
+template <int D, bool BF16, bool TRITON, bool PER_THREAD, bool RAGGED, typename AfterPhase1>
+__device__ __forceinline__ void k_quant_block(const QuantParams& p, const int blk, const int h, const int b,
+                                              uint4 (&raw)[QuantGeom<D, 64>::NP], const uint4 mbits, unsigned int* gmax,
+                                              unsigned int* zero_next, AfterPhase1 after_phase1) {
+  using G = QuantGeom<D, 64>;
+  constexpr int TPR = G::TPR, RPP = G::RPP, NP = G::NP, NG = PER_THREAD ? 4 : 1;
+  static_assert(RPP % 8 == 0, "the group of a row must not depend on the pass");
+  const int tr = (int)threadIdx.x / TPR, tc = (int)threadIdx.x % TPR;
+  const int g = PER_THREAD ? (tr & 7) >> 1 : 0;  // triton/quant_per_thread.py:73-80 (K: (r % 8) / 2), one warp group
+  const int row0 = blk * 64 + tr;
+  float xf[NP][8];
+  {
+    float mean_f[8];
+    if constexpr (!TRITON || BF16) unpack8<BF16>(mbits, mean_f);
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      sub_mean8<BF16, TRITON>(raw[i], mbits, mean_f, xf[i]);
+      float am = RAGGED ? 0.f : amax;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(xf[i][j]));
+      if constexpr (RAGGED) amax = fmaxf(amax, row0 + i * RPP < p.N ? am : 0.f);
+      else amax = am;
+    }
+    amax = row_lanes_max<TPR>(amax);
+    if (tc == 0) atomicMax(&gmax[g], __float_as_uint(amax));
+  }
+  after_phase1();
+  __syncthreads();
+  if (threadIdx.x < NG) zero_next[threadIdx.x] = 0u;
+
+  const float a = __uint_as_float(gmax[g]);
+  // TRITON: sc = a / 127 (+ 1e-7 per_thread) and q = x / sc half away from zero;  CUDA: sc = max(a, 1e-7) / 127 and
+  // q = rint(x * (127 / max(a, 1e-7))) (fused.cu:176-181).  One thread per group stores the scale (rows 0, 2, 4, 6).
+  const float sc = TRITON ? a / 127.f + (PER_THREAD ? 0.0000001f : 0.f) : 0.f;
+  const float r = TRITON ? 1.0f / sc : 127.f / fmaxf(a, 0.0000001f);
+  if (tc == 0 && tr < 2 * NG && !(tr & 1))
+    p.scale[b * p.ss_b + h * p.ss_h + blk * p.ss_blk + g] = TRITON ? sc : fmaxf(a, 0.0000001f) / 127.f;
+  const bool r_unusable = TRITON && !(fabsf(r) < 3.0e38f);  // a == 0 without epsilon: the division's 0 / 0 decides
+
+  int8_t* obase = p.out + b * p.osb + h * p.osh + blk * p.o_blk + (int64_t)tr * p.osn + tc * 8;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    uint2 w;
+    if constexpr (TRITON) {
+      // the exact division, for the whole 8-element chunk of the wave, only where round_half_away_pack8 asks for it
+      // (~6 % of the chunks) or the reciprocal is not finite.  Bit-exact by construction.
+      bool near;
+      w = round_half_away_pack8(xf[i], r, near);
+      if (__builtin_amdgcn_ballot_w64(near || r_unusable) != 0) {
+        int q[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float y = xf[i][j] / sc;  // IEEE division
+          y = y + (y >= 0.f ? 0.5f : -0.5f);
+          q[j] = min(max((int)y, -128), 127);  // truncation, as tl `.to(int8)`
+        }
+        w = make_uint2(pack_i8x4(q[0], q[1], q[2], q[3]), pack_i8x4(q[4], q[5], q[6], q[7]));
+      }
+    } else {
+      // rint and the byte from one addition: |x r| <= 127 (1 + 3 ulp), so fl(x r) + M is M + rint(fl(x r)) exactly (ties to
+      // even on both sides: M is even) and its low byte the int8 -- what (int)rintf(x * r) packs
+      uint32_t tb[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tb[j] = __float_as_uint(xf[i][j] * r + 12582912.f);
+      w = make_uint2(pack_i8x4(tb[0], tb[1], tb[2], tb[3]), pack_i8x4(tb[4], tb[5], tb[6], tb[7]));
+    }
+    if (!RAGGED || row0 + i * RPP < p.N) *reinterpret_cast<uint2*>(obase + (int64_t)(i * RPP) * p.osn) = w;
+  }
+}
+
+template <int D, bool BF16, bool TRITON, bool PER_THREAD>
+__device__ __forceinline__ void k_quant_stream_walk(const QuantParams& p, const int per_wg, const int wg, const int h, const int b,
                                                     const int H, unsigned int (*gmax)[64], float (*mpart)[D]) {
-  constexpr int BLK = 64;
-  using G = QuantGeom<D, BLK>;
-  const int nblk = (p.N + BLK - 1) / BLK;
+  using G = QuantGeom<D, 64>;
+  const int nblk = (p.N + 63) / 64, nfull = p.N / 64;  // blocks [0, nfull) are whole
   const int blk0 = wg * per_wg, blk1 = min(blk0 + per_wg, nblk);  // the host launches no empty workgroup
   if (threadIdx.x < 192) (&gmax[0][0])[threadIdx.x] = 0u;
   const uint16_t* xbase = p.x + b * p.xsb + h * p.xsh + (threadIdx.x % G::TPR) * 8;
-  const int64_t o_boff = b * p.osb;
   uint4 raw[G::NP];
-  quant_load_rows<D, BLK>(xbase, p.xsn, blk0, p.N, raw);
+  if (blk0 < nfull) k_load_rows<D, false>(xbase, p.xsn, blk0, p.N, raw);
+  else k_load_rows<D, true>(xbase, p.xsn, blk0, p.N, raw);
   const uint4 mbits = quant_mean_bits<D, BF16>(p, h, b, H, wg == 0, mpart);
   int par = 0;
   for (int blk = blk0; blk < blk1; ++blk) {
-    // the rows of the next block are requested as soon as this block's are unpacked (their registers are free then) and
-    // fly during the barrier, the rounding and the stores of this block
-    quant_block<D, BLK, BF16, TRITON>(p, blk, h, b, H, p.N, o_boff, raw, mbits, gmax[par], gmax[par == 0 ? 2 : par - 1], [&] {
-      if (blk + 1 < blk1) quant_load_rows<D, BLK>(xbase, p.xsn, blk + 1, p.N, raw);
-    });
+    unsigned int* const zero_next = gmax[par == 0 ? 2 : par - 1];
+    if (blk < nfull) {
+      // the rows of the next block are requested as soon as this block's are unpacked (their registers are free then) and
+      // fly during the barrier, the rounding and the stores of this block
+      k_quant_block<D, BF16, TRITON, PER_THREAD, false>(p, blk, h, b, raw, mbits, gmax[par], zero_next, [&] {
+        if (blk + 1 < blk1) {
+          if (blk + 1 < nfull) k_load_rows<D, false>(xbase, p.xsn, blk + 1, p.N, raw);
+          else k_load_rows<D, true>(xbase, p.xsn, blk + 1, p.N, raw);
+        }
+      });
+    } else {
+      k_quant_block<D, BF16, TRITON, PER_THREAD, true>(p, blk, h, b, raw, mbits, gmax[par], zero_next, [] {});  // the last
+    }
     par = par == 2 ? 0 : par + 1;
   }
+}
+
+template <int D, bool BF16, bool TRITON>
+__device__ __forceinline__ void k_quant_stream_body(const QuantParams& p, const int per_wg, const int wg, const int h, const int b,
+                                                    const int H, unsigned int (*gmax)[64], float (*mpart)[D]) {
+  // (the host admits per_block and per_thread for K: k_smooth_quant_check, kv_prepare_check)
+  if (p.gran == SAGE_GRAN_PER_THREAD) k_quant_stream_walk<D, BF16, TRITON, true>(p, per_wg, wg, h, b, H, gmax, mpart);
+  else k_quant_stream_walk<D, BF16, TRITON, false>(p, per_wg, wg, h, b, H, gmax, mpart);
 }
 
 template <int D, bool BF16, bool TRITON>
