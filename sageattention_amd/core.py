@@ -448,7 +448,13 @@ def sageattn_varlen(
 ) -> torch.Tensor:
     """Packed variable-length SageAttention (reference core.py:363-477): q ``[cu_seqlens_q[-1], Hq, D]``, k/v
     ``[cu_seqlens_k[-1], Hk, D]``; per-block INT8 Q/K (blocks restart at each sequence), FP16 PV; the K smoothing
-    mean is taken over ALL packed tokens (core.py:461).  The cumulative lengths stay on the device: no host sync."""
+    mean is taken over ALL packed tokens (core.py:461).  The cumulative lengths stay on the device: no host sync.
+
+    ``max_seqlen_q`` / ``max_seqlen_k`` may be upper bounds of the true maxima (a serving bucket size): they size the scale
+    arrays and the grid and feed the workgroup-geometry choice, and the output has the bits of the call with the exact maxima.
+    ``is_causal`` masks top-left PER SEQUENCE: query row i of a sequence sees its keys 0..i, whatever the two lengths are (a
+    sequence with more queries than keys shows all its keys to the rows beyond them).  A sequence with queries and no keys
+    gives zero rows."""
     dtype = _common_checks(q, k, v)
     assert cu_seqlens_q.is_contiguous() and cu_seqlens_k.is_contiguous(), "cu_seqlens_q and cu_seqlens_k must be contiguous."
     assert q.dim() == 3 and k.dim() == 3 and v.dim() == 3, "q, k, v must be [total_tokens, heads, head_dim]"
