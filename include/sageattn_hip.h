@@ -465,6 +465,34 @@ int sage_block_select_cdf(const float* pooled_q, const float* sim_q, const float
                           const float* cdfthreshd, int32_t* block_lists, int64_t block_lists_bytes,
                           uint8_t* block_map, sage_stream_t stream);
 
+/* Selection with a choice of rule and with key blocks pinned on (text tokens at one end of the key sequence, an
+ * attention-sink block).  Statistics, ELIGIBLE and SELF-SIMILAR as for sage_block_select_cdf; ntk = ceil(N/64):
+ *   key block j is KEPT if j < keep_first or j >= ntk - keep_last (ints >= 0, one pair per call; values beyond ntk act as ntk);
+ *   j is a CANDIDATE if it is eligible and not kept; n = the number of candidates of (b, h_q) (it depends on h_q through
+ *   simthreshd1[h_q]);  s_j = sm_scale * dot(pooled_q[b,h_q,i], pooled_k[b,h_k,j]) in fp32.
+ *   rule SAGE_SELECT_CDF   rule_param = cdfthreshd[h_q]: the rule of sage_block_select_cdf with "eligible" read as
+ *                          "candidate" -- the softmax of s and its mass run over the candidates only.  With keep_first =
+ *                          keep_last = 0 it IS that rule: sage_block_select_cdf is this call, bit for bit.
+ *   rule SAGE_SELECT_TOPK  rule_param = topk[h_q], the fraction of the candidates each q-block may attend:
+ *                          kcount = n if !(topk < 1) (1 and above, and NaN), otherwise
+ *                          kcount = min(n, max(1, (int)ceilf(topk * (float)n))), the product ONE fp32 multiplication;
+ *                          SELECTED = the kcount candidates with the greatest s (equal values: the lower j first; +0 and -0
+ *                          are equal).  No exponential is taken.
+ *   tile (i, j) is ON if j is selected, or j is not a candidate, or i is not self-similar.  If n == 0 every tile of the row
+ *   is on.  Every q-block keeps at least one tile.
+ * Consequence of TOPK: every self-similar q-block of one (b, h_q) has exactly (ntk - n) + kcount active tiles -- lists of
+ * equal length per head, a cost known before the call runs.
+ * rule_param is fp32 [Hq] in device memory.  Outputs, limits and argument checks as for sage_block_select_cdf; an unknown
+ * rule, a NULL rule_param and a negative keep_first / keep_last return SAGE_ERR_INVALID_ARGUMENT.  TOPK needs no softmax
+ * and no float sums: scores become order-preserving unsigned keys and the kernel bisects on the key by counting. */
+#define SAGE_SELECT_CDF  0
+#define SAGE_SELECT_TOPK 1
+int sage_block_select(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                      int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                      int rule, const float* rule_param /* cdfthreshd or topk, fp32 [Hq] */,
+                      int keep_first, int keep_last, int32_t* block_lists, int64_t block_lists_bytes,
+                      uint8_t* block_map, sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

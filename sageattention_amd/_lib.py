@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libsageattn_hip.so")
 SAGE_F16, SAGE_BF16 = 0, 1
 GRAN_PER_BLOCK, GRAN_PER_WARP, GRAN_PER_THREAD = 1, 2, 3
 ROUND_TRITON, ROUND_CUDA = 0, 1
+SELECT_CDF, SELECT_TOPK = 0, 1  # SAGE_SELECT_*: the rule of sage_block_select
 
 
 class SageTensor(ctypes.Structure):
@@ -117,6 +118,9 @@ SIGNATURES = {
     "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    # ... with (rule, rule_param, keep_first, keep_last) in the place of cdfthreshd
+    "sage_block_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

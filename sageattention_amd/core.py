@@ -606,34 +606,57 @@ def _per_head(value, Hq, device, name):
     return torch.full((Hq,), float(value), dtype=torch.float32, device=device)
 
 
-def _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, want_map):
-    """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select_cdf -> (plan, uint8
-    map or None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
+def _check_select_args(topk, keep_first, keep_last):
+    """The selection's keywords, checked before anything touches a tensor.  A per-head ``topk`` tensor is not read here (no
+    host synchronisation): the kernel takes values <= 0 as "one candidate" and NaN as 1."""
+    if topk is not None and not isinstance(topk, torch.Tensor) and not float(topk) > 0.0:
+        raise ValueError(f"topk must be a fraction > 0 (1 and above keep every candidate), got {topk}")
+    for name, value in (("keep_first", keep_first), ("keep_last", keep_last)):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+            raise ValueError(f"{name} must be an int >= 0 (a number of 64-key blocks), got {value!r}")
+
+
+def _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, want_map, topk=None, keep_first=0,
+                    keep_last=0):
+    """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select (rule TOPK when
+    ``topk`` is given, else CDF) -> (plan, uint8 map or None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k, tensor_layout)
     if Hq % Hk != 0:
         raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
     thr = _per_head(simthreshd1, Hq, q.device, "simthreshd1")
-    cdf = _per_head(cdfthreshd, Hq, q.device, "cdfthreshd")
+    if topk is None:
+        rule, par = L.SELECT_CDF, _per_head(cdfthreshd, Hq, q.device, "cdfthreshd")
+    else:
+        rule, par = L.SELECT_TOPK, _per_head(topk, Hq, q.device, "topk")
     pq, sq = block_pool_sim(q, 128, tensor_layout)
     pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
     lib = L.lib()
     lists = torch.empty(lib.sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4, dtype=torch.int32, device=q.device)
     bmap = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.uint8, device=q.device) if want_map else None
-    L.check(lib.sage_block_select_cdf(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
-                                      float(sm_scale), thr.data_ptr(), cdf.data_ptr(), lists.data_ptr(), lists.numel() * 4,
-                                      L.ptr(bmap), L.stream_ptr(q.device)), "sage_block_select_cdf")
+    ntk = (N + 63) // 64  # keeps beyond it act as ntk
+    L.check(lib.sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
+                                  float(sm_scale), thr.data_ptr(), rule, par.data_ptr(), min(keep_first, ntk),
+                                  min(keep_last, ntk), lists.data_ptr(), lists.numel() * 4, L.ptr(bmap),
+                                  L.stream_ptr(q.device)), "sage_block_select")
     return BlockSparsePlan(lists, B, Hq, M, N), bmap
 
 
 def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", simthreshd1=0.6, cdfthreshd=0.98,
-                sm_scale: Optional[float] = None, km: Optional[torch.Tensor] = None, return_map: bool = False):
+                sm_scale: Optional[float] = None, km: Optional[torch.Tensor] = None, return_map: bool = False,
+                topk=None, keep_first: int = 0, keep_last: int = 0):
     """Predict the block map of ``sageattn_block_sparse`` from Q and K (the rule: include/sageattn_hip.h,
-    sage_block_select_cdf): pooled 128-row q-blocks against pooled 64-row key blocks of ``k - km``, per q-block the fewest key
+    sage_block_select): pooled 128-row q-blocks against pooled 64-row key blocks of ``k - km``, per q-block the fewest key
     blocks that hold ``cdfthreshd`` of the softmax mass, and every tile of a block whose rows are not alike (mean cosine
     similarity <= ``simthreshd1``).  Thresholds are floats or fp32 tensors [Hq]; ``km`` defaults to ``k_mean(k)``, the
     smoothing mean of the K quantizer.  Returns a ``BlockSparsePlan``, with ``return_map=True`` also the bool map
-    [B,Hq,ceil(M/128),ceil(N/64)].  Non-causal."""
+    [B,Hq,ceil(M/128),ceil(N/64)].  Non-causal.
+
+    ``topk`` (a float > 0 or an fp32 tensor [Hq]) selects by budget instead: per q-block the ``ceil(topk * n)`` best-scoring
+    of the head's n candidate key blocks, so that every self-similar q-block of a head gets a list of the same length;
+    ``cdfthreshd`` is then not read.  ``keep_first`` / ``keep_last`` (ints >= 0) pin the first / last key blocks on under
+    either rule (text tokens, an attention sink): they are always computed and take no part in the selection."""
+    _check_select_args(topk, keep_first, keep_last)
     assert q.is_cuda, "Input tensors must be on cuda."
     assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
     assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
@@ -645,7 +668,8 @@ def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", si
             km = k_mean(k, tensor_layout)
         else:
             km = torch.nn.functional.pad(km, (0, k.size(-1) - km.size(-1))).to(k.dtype).contiguous()
-        plan, bmap = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, return_map)
+        plan, bmap = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, return_map, topk,
+                                     keep_first, keep_last)
     return (plan, bmap.view(torch.bool)) if return_map else plan
 
 
@@ -662,11 +686,16 @@ def sageattn_sparge(
     qk_quant_gran: str = "per_thread",
     return_lse: bool = False,
     return_plan: bool = False,
+    topk=None,
+    keep_first: int = 0,
+    keep_last: int = 0,
 ):
     """``sageattn_block_sparse`` on the block map that ``sparge_plan`` predicts for this q and k: the K (or K + V) pre-pass
     runs once, the predictor uses its smoothing mean, and the block-sparse attention kernel reads the predicted lists.
     Bit-identical to ``sageattn_block_sparse(q, k, v, sparge_plan(q, k, ...))``.  Returns o, then the LSE with
-    ``return_lse``, then the ``BlockSparsePlan`` with ``return_plan``.  Non-causal."""
+    ``return_lse``, then the ``BlockSparsePlan`` with ``return_plan``.  Non-causal.  ``topk``, ``keep_first`` and
+    ``keep_last`` as for ``sparge_plan``: with ``topk`` the budget rule is used and ``cdfthreshd`` is not read."""
+    _check_select_args(topk, keep_first, keep_last)
     if pv not in ("fp16", "fp8"):
         raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
     if qk_quant_gran not in ("per_warp", "per_thread"):
@@ -686,7 +715,8 @@ def sageattn_sparge(
             k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
             if pv == "fp8":
                 v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
-        plan, _ = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, False)
+        plan, _ = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, False, topk, keep_first,
+                                  keep_last)
         o = torch.empty(q.size(), dtype=dtype, device=q.device)
         lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
                           pv == "fp8", plan=plan)

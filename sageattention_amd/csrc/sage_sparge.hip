@@ -2,9 +2,11 @@
 // worth computing, decided at run time from Q and K.
 //   block_pool_sim_kernel   per block of BLK rows: the mean row and the mean pairwise cosine similarity ("self-similarity")
 //                           of its rows.  One pass over the tensor, HBM-bound.
-//   block_select_kernel     per (b, h_q, q-block): softmax of the pooled scores over the self-similar key blocks, the
-//                           shortest descending prefix that holds cdfthreshd of its mass, written as the tile list the
-//                           block-sparse attention kernels read (and optionally as a map).
+//   block_select_kernel     per (b, h_q, q-block): the pooled scores of the candidate key blocks (self-similar and not
+//                           pinned on by keep_first / keep_last), then one of two rules -- CDF: the shortest descending
+//                           prefix that holds cdfthreshd of their softmax mass; TOPK: the topk fraction of them with the
+//                           greatest scores -- written as the tile list the block-sparse attention kernels read (and
+//                           optionally as a map).
 // The rule itself is stated in include/sageattn_hip.h.
 #include "sage_entry.h"
 
@@ -141,11 +143,12 @@ __global__ __launch_bounds__(256) void block_pool_sim_kernel(const PoolParams p)
 // ------------------------------------------------------------------------------------------------
 struct SelectParams {
   const float *pq, *sq, *pk, *sk;  // [B,Hq,nqb,D], [B,Hq,nqb], [B,Hk,ntk,D], [B,Hk,ntk]
-  const float *thr, *cdf;          // [Hq]
+  const float *thr, *par;          // [Hq]: simthreshd1, and the rule's parameter (cdfthreshd or topk)
   int* lists;
   uint8_t* map;  // [B,Hq,nqb,ntk] or null
   int64_t rows;
   int Hq, Hk, nqb, ntk, row_ints;
+  int kf, kl;  // key blocks j < kf and j >= ntk - kl are kept: always on, never candidates (both clamped to ntk)
   float sm_scale;
 };
 
@@ -156,17 +159,32 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A score as an unsigned key that orders like the score (-0 = +0), >= 1: 0 is left for the blocks that are no candidates.
+__device__ __forceinline__ uint32_t score_key(float s) {
+  const uint32_t u = __float_as_uint(s == 0.f ? 0.f : s);
+  const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return key ? key : 1u;
+}
+
 // One wave per list row (b, h_q, q-block), four rows per workgroup (mostly q-blocks of one head: their reads of pooled K
 // meet in the CU's cache); the row's p lives in the wave's quarter of LDS.
 //  1. scores: 8 lanes per key block, each D/8 channels as float4 (a 128-byte run per 8 lanes), summed over the 8 lanes.
-//  2. p = exp(s - max) over the eligible blocks (ineligible ones hold -1: negative as a float and as an int).
+//     Only candidates (eligible, not kept) get one; the other blocks are forced on under either rule.
+// RULE = SAGE_SELECT_CDF:
+//  2. p = exp(s - max) over the candidates (the other blocks hold -1: negative as a float and as an int).
 //  3. the prefix without a sort: p >= 0 orders like its bit pattern, so bisect on the pattern t for the largest t with
 //     sum{p >= t} >= cdfthreshd * sum p (about 30 wave-reduced sums).  That t is one of the p; everything above it is
 //     selected, and of the blocks equal to it the lowest indices, as many as the threshold still needs (one at least).
+// RULE = SAGE_SELECT_TOPK: no softmax and no float sums.
+//  2. the row holds score_key(s) for the candidates and 0 for the other blocks; n = count{key >= 1}, kcount from topk and n.
+//  3. bisect on the key for the largest t with count{key >= t} >= kcount (32 counts, each ballots + popcounts: a value all
+//     lanes hold).  Everything above t is selected, and of the keys equal to t the lowest indices, kcount - count{key > t}.
+// Both:
 //  4. emission as block_map_compact_kernel: ballot + prefix popcount, ascending, the tail padded with the last tile.
 // Every sum runs in a fixed order and every decision is taken on values all lanes hold alike: deterministic, no atomics.
-template <int D>
+template <int D, int RULE>
 __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p) {
+  static_assert(RULE == SAGE_SELECT_CDF || RULE == SAGE_SELECT_TOPK, "two rules");
   extern __shared__ float prow_all[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + w;
@@ -177,10 +195,12 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
   const int hq = (int)(bh % p.Hq);
   const int64_t b = bh / p.Hq;
   const int64_t bhk = b * p.Hk + hq / (p.Hq / p.Hk);
-  const float thr = p.thr[hq], cdf = p.cdf[hq];
-  // a q-block that is not self-similar, or a threshold of 1 and above (or NaN), keeps every tile
-  bool all_on = !(p.sq[row] > thr) || !(cdf < 1.0f);
+  const float thr = p.thr[hq], par = p.par[hq];
+  // a q-block that is not self-similar, or a cdfthreshd / topk of 1 and above (or NaN), keeps every tile
+  bool all_on = !(p.sq[row] > thr) || !(par < 1.0f);
   float mx = -INFINITY;
+  uint32_t tbits = 0;
+  int take = 0;
   if (!all_on) {
     const int sub = lane & 7, g = lane >> 3;
     const float* pk = p.pk + bhk * ntk * D;
@@ -211,16 +231,47 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
           dot = __builtin_fmaf(q4[i].w, k4[u][i].w, dot);
         }
         dot = row_lanes_sum<8>(dot);
-        if (sub == 0 && j < ntk) prow[j] = skv[u] > thr ? dot * p.sm_scale : -INFINITY;
+        const bool cand = skv[u] > thr && j >= p.kf && j < ntk - p.kl;
+        const float s = dot * p.sm_scale;
+        if (sub == 0 && j < ntk) {
+          if constexpr (RULE == SAGE_SELECT_TOPK) prow[j] = __uint_as_float(cand ? score_key(s) : 0u);
+          else prow[j] = cand ? s : -INFINITY;
+        }
       }
     }
     wave_lds_sync();
-    for (int j = lane; j < ntk; j += 64) mx = fmaxf(mx, prow[j]);
-    mx = wave_max(mx);
-    all_on = mx == -INFINITY;  // no eligible key block: every tile is forced on
+    if constexpr (RULE == SAGE_SELECT_CDF) {
+      for (int j = lane; j < ntk; j += 64) mx = fmaxf(mx, prow[j]);
+      mx = wave_max(mx);
+      all_on = mx == -INFINITY;  // no candidate: every tile is forced on
+    }
   }
-  int tbits = 0, take = 0;
-  if (!all_on) {
+  if constexpr (RULE == SAGE_SELECT_TOPK) {
+    if (!all_on) {
+      // candidates whose key is >= t (t >= 1), from ballots: the same value in every lane
+      auto count_from = [&](uint32_t t) {
+        int c = 0;
+        for (int j0 = 0; j0 < ntk; j0 += 64) {
+          const int j = j0 + lane;
+          c += __popcll(__ballot(j < ntk && __float_as_uint(prow[j]) >= t));
+        }
+        return c;
+      };
+      const int n = count_from(1u);
+      all_on = n == 0;  // no candidate: every tile is forced on
+      if (!all_on) {
+        const float want = ceilf(par * (float)n);  // one fp32 product; par < 1 here
+        const int kcount = want >= (float)n ? n : want > 1.f ? (int)want : 1;
+        uint64_t lo = 1, hi = 1ull << 32;  // count_from(lo) >= kcount > count_from(hi): no key is 2^32
+        while (hi - lo > 1) {
+          const uint64_t mid = lo + ((hi - lo) >> 1);
+          if (count_from((uint32_t)mid) >= kcount) lo = mid; else hi = mid;
+        }
+        tbits = (uint32_t)lo;  // one of the keys; hi = lo + 1
+        take = kcount - (hi < (1ull << 32) ? count_from((uint32_t)hi) : 0);
+      }
+    }
+  } else if (!all_on) {
     float tot = 0.f;
     for (int j = lane; j < ntk; j += 64) {  // each lane rewrites the words it read
       const float s = prow[j];
@@ -229,7 +280,7 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
       tot += fmaxf(pj, 0.f);
     }
     wave_lds_sync();
-    const float target = cdf * wave_sum(tot);
+    const float target = par * wave_sum(tot);
     // sum of the p whose pattern is >= t, in the order of `tot`: skipped terms add exact zeros
     auto mass_from = [&](int t) {
       float gsum = 0.f;
@@ -244,11 +295,11 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
       const int mid = lo + ((hi - lo) >> 1);
       if (mass_from(mid) >= target) lo = mid; else hi = mid;
     }
-    tbits = lo;
-    const float tstar = __int_as_float(tbits);
-    const float above = mass_from(tbits + 1);
+    tbits = (uint32_t)lo;
+    const float tstar = __int_as_float(lo);
+    const float above = mass_from(lo + 1);
     int nties = 0;
-    for (int j = lane; j < ntk; j += 64) nties += __float_as_int(prow[j]) == tbits ? 1 : 0;
+    for (int j = lane; j < ntk; j += 64) nties += __float_as_int(prow[j]) == lo ? 1 : 0;
     nties = wave_sum_i(nties);
     take = 1;
     if (tstar > 0.f) {
@@ -266,12 +317,15 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
     const bool in = j < ntk;
     bool on = in;
     if (!all_on) {
-      const int pb = in ? __float_as_int(prow[j]) : 0;
+      const uint32_t pb = in ? __float_as_uint(prow[j]) : 0u;
       const bool tie = in && pb == tbits;
       const uint64_t tbal = __ballot(tie);
       const int rank = ties_before + __popcll(tbal & ((1ull << lane) - 1ull));
       ties_before += __popcll(tbal);
-      on = in && (pb < 0 || pb > tbits || (tie && rank < take));
+      // forced on: the blocks that are no candidates hold -1.0f (CDF) or the key 0 (TOPK)
+      const bool forced = RULE == SAGE_SELECT_TOPK ? pb == 0u : (int)pb < 0;
+      const bool above = RULE == SAGE_SELECT_TOPK ? pb > tbits : (int)pb > (int)tbits;
+      on = in && (forced || above || (tie && rank < take));
     }
     const uint64_t bal = __ballot(on);
     if (on) out[1 + count + __popcll(bal & ((1ull << lane) - 1ull))] = j;
@@ -320,28 +374,42 @@ extern "C" int sage_block_pool_sim(const sage_tensor* x, int dtype, int B, int H
   return launch_status();
 }
 
-extern "C" int sage_block_select_cdf(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
-                                     int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
-                                     const float* cdfthreshd, int32_t* block_lists, int64_t block_lists_bytes,
-                                     uint8_t* block_map, sage_stream_t stream) {
-  if (!pooled_q || !sim_q || !pooled_k || !sim_k || !simthreshd1 || !cdfthreshd || !block_lists) return SAGE_ERR_INVALID_ARGUMENT;
+extern "C" int sage_block_select(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                                 int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                                 int rule, const float* rule_param, int keep_first, int keep_last, int32_t* block_lists,
+                                 int64_t block_lists_bytes, uint8_t* block_map, sage_stream_t stream) {
+  if (!pooled_q || !sim_q || !pooled_k || !sim_k || !simthreshd1 || !rule_param || !block_lists) return SAGE_ERR_INVALID_ARGUMENT;
   if (!aligned16(pooled_q) || !aligned16(pooled_k) || !aligned16(block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
   if (B <= 0 || Hq <= 0 || Hk <= 0 || Hq % Hk != 0 || M <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (rule != SAGE_SELECT_CDF && rule != SAGE_SELECT_TOPK) return SAGE_ERR_INVALID_ARGUMENT;
+  if (keep_first < 0 || keep_last < 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (D != 64 && D != 128) return SAGE_ERR_UNSUPPORTED_HEAD_DIM;
   if (!(sm_scale > 0.f) || !(sm_scale < INFINITY)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (((int64_t)N + 63) / 64 > SAGE_SPARGE_MAX_KEY_TILES) return SAGE_ERR_TOO_LARGE;  // the p rows of a workgroup in LDS
+  if (((int64_t)N + 63) / 64 > SAGE_SPARGE_MAX_KEY_TILES) return SAGE_ERR_TOO_LARGE;  // the rows of a workgroup in LDS
   if (block_lists_bytes < block_sparse_bytes(B, Hq, M, N)) return SAGE_ERR_INVALID_ARGUMENT;
   SelectParams p;
-  p.pq = pooled_q; p.sq = sim_q; p.pk = pooled_k; p.sk = sim_k; p.thr = simthreshd1; p.cdf = cdfthreshd;
+  p.pq = pooled_q; p.sq = sim_q; p.pk = pooled_k; p.sk = sim_k; p.thr = simthreshd1; p.par = rule_param;
   p.lists = (int*)block_lists; p.map = block_map;
   p.Hq = Hq; p.Hk = Hk; p.nqb = (M + 127) / 128; p.ntk = (N + 63) / 64; p.row_ints = (int)block_list_row(N);
+  p.kf = keep_first < p.ntk ? keep_first : p.ntk; p.kl = keep_last < p.ntk ? keep_last : p.ntk;
   p.rows = (int64_t)B * Hq * p.nqb;
   p.sm_scale = sm_scale;
   if ((p.rows + 3) / 4 >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
   launch_begin();
   by_dim(D, [&](auto d) {
-    hipLaunchKernelGGL((block_select_kernel<decltype(d)::value>), dim3((unsigned)((p.rows + 3) / 4)), dim3(256),
-                       (size_t)4 * p.ntk * sizeof(float), (hipStream_t)stream, p);
+    by_flag(rule == SAGE_SELECT_TOPK, [&](auto topk) {
+      hipLaunchKernelGGL((block_select_kernel<decltype(d)::value, decltype(topk)::value ? SAGE_SELECT_TOPK : SAGE_SELECT_CDF>),
+                         dim3((unsigned)((p.rows + 3) / 4)), dim3(256), (size_t)4 * p.ntk * sizeof(float),
+                         (hipStream_t)stream, p);
+    });
   });
   return launch_status();
+}
+
+extern "C" int sage_block_select_cdf(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                                     int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                                     const float* cdfthreshd, int32_t* block_lists, int64_t block_lists_bytes,
+                                     uint8_t* block_map, sage_stream_t stream) {
+  return sage_block_select(pooled_q, sim_q, pooled_k, sim_k, B, Hq, Hk, M, N, D, sm_scale, simthreshd1, SAGE_SELECT_CDF,
+                           cdfthreshd, 0, 0, block_lists, block_lists_bytes, block_map, stream);
 }

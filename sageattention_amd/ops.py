@@ -8,6 +8,9 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, block_lists, plan_shape, ...) -> o   (a compacted plan)
     torch.ops.sageattention_amd.attn_sparge(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
     torch.ops.sageattention_amd.attn_sparge_lse(...) -> (o, lse)          (the block map predicted from q and k)
+    torch.ops.sageattention_amd.attn_sparge_select(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layout,
+                                                   sm_scale, pv, qk_quant_gran) -> o      (rule "cdf" | "topk", kept key blocks)
+    torch.ops.sageattention_amd.attn_sparge_select_lse(...) -> (o, lse)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -133,19 +136,68 @@ def _(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gr
     return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
 
 
+def _select_kwargs(rule_param: torch.Tensor, rule: str):
+    if rule not in ("cdf", "topk"):
+        raise ValueError(f"rule must be 'cdf' or 'topk', got {rule}")
+    return {"topk": rule_param} if rule == "topk" else {"cdfthreshd": rule_param}
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_select", mutates_args=())
+def attn_sparge_select(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, rule_param: torch.Tensor,
+                       rule: str, keep_first: int, keep_last: int, tensor_layout: str, sm_scale: float, pv: str,
+                       qk_quant_gran: str) -> torch.Tensor:
+    # attn_sparge with the rule named ("cdf": rule_param = cdfthreshd, "topk": rule_param = topk) and key blocks pinned on
+    return core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                qk_quant_gran=qk_quant_gran, keep_first=keep_first, keep_last=keep_last,
+                                **_select_kwargs(rule_param, rule)).contiguous()
+
+
+@attn_sparge_select.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_select_lse", mutates_args=())
+def attn_sparge_select_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor,
+                           rule_param: torch.Tensor, rule: str, keep_first: int, keep_last: int, tensor_layout: str,
+                           sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                  qk_quant_gran=qk_quant_gran, return_lse=True, keep_first=keep_first, keep_last=keep_last,
+                                  **_select_kwargs(rule_param, rule))
+    return o.contiguous(), lse
+
+
+@attn_sparge_select_lse.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layout, sm_scale, pv, qk_quant_gran):
+    if tensor_layout == "HND":
+        B, H, M = q.shape[0], q.shape[1], q.shape[2]
+    else:
+        B, M, H = q.shape[0], q.shape[1], q.shape[2]
+    return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+
+
 def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
                                simthreshd1=0.6, cdfthreshd=0.98, sm_scale: Optional[float] = None, pv: str = "fp16",
-                               qk_quant_gran: str = "per_thread", return_lse: bool = False):
-    """``sageattn_sparge`` (core.py) as a traceable custom op; thresholds are floats or fp32 tensors [Hq]."""
+                               qk_quant_gran: str = "per_thread", return_lse: bool = False, topk=None,
+                               keep_first: int = 0, keep_last: int = 0):
+    """``sageattn_sparge`` (core.py) as a traceable custom op; thresholds and ``topk`` are floats or fp32 tensors [Hq].
+    With ``topk`` the budget rule is used and ``cdfthreshd`` is not read; ``keep_first`` / ``keep_last`` pin key blocks on.
+    Without any of the three it calls ``attn_sparge`` / ``attn_sparge_lse`` as before, otherwise the ``attn_sparge_select``
+    pair."""
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    core._check_select_args(topk, keep_first, keep_last)
     if sm_scale is None:
         sm_scale = q.size(-1) ** -0.5
     Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
-    thr, cdf = (t if isinstance(t, torch.Tensor) else torch.full((Hq,), float(t), dtype=torch.float32, device=q.device)
-                for t in (simthreshd1, cdfthreshd))
-    op = torch.ops.sageattention_amd.attn_sparge_lse if return_lse else torch.ops.sageattention_amd.attn_sparge
-    return op(q, k, v, thr, cdf, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+    rule, par = ("cdf", cdfthreshd) if topk is None else ("topk", topk)
+    thr, par = (t if isinstance(t, torch.Tensor) else torch.full((Hq,), float(t), dtype=torch.float32, device=q.device)
+                for t in (simthreshd1, par))
+    if topk is None and keep_first == 0 and keep_last == 0:
+        op = torch.ops.sageattention_amd.attn_sparge_lse if return_lse else torch.ops.sageattention_amd.attn_sparge
+        return op(q, k, v, thr, par, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+    op = torch.ops.sageattention_amd.attn_sparge_select_lse if return_lse else torch.ops.sageattention_amd.attn_sparge_select
+    return op(q, k, v, thr, par, rule, keep_first, keep_last, tensor_layout, float(sm_scale), pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
