@@ -431,6 +431,57 @@ int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dtype, const 
                                        int is_causal, int qk_gran, int warpq, float sm_scale,
                                        const int32_t* block_lists, int64_t block_lists_bytes, sage_stream_t stream);
 
+/* ... with SpargeAttn's second stage, the P.V skip (pvthreshd): inside the tile loop a wave -- 32 query rows of a 128-row
+ * q-block -- leaves out the exponentials, the packing of P, the row sums and the P.V products of a tile whose scores are
+ * all negligible against what its rows have already seen.  The arguments of the _blocksparse twin, then
+ *   pv_thresh  device, fp32 [Hq], 4-byte aligned, required: the threshold of every query head, a positive number in the
+ *              natural-log units of the scaled logits (the units of lse; the kernel multiplies it by log2 e)
+ *   skipped    device, int32 [B, Hq, ceil(M/128), 4], 4-byte aligned, or NULL: per wave the number of tiles it skipped
+ * The rule, for a wave and the tile at list position pos of its q-block's list:
+ *   m_ref[r]  the kernel's running reference maximum of row r when the tile is reached (after the lazy rescale for this
+ *             tile).  It lags the true running maximum of the row by at most lazy = 6 ln 2 (FP16 / BF16 PV), 3 ln 2 (FP8 PV).
+ *   t[r]      the row maximum of this tile's logits, over keys < N only.
+ *   The wave skips the tile iff pos > 0 and, for every row r of the wave with r < M, t[r] <= m_ref[r] - pv_thresh[h].
+ * Rows at or beyond M take no part (the padded rows of a ragged q-block would otherwise veto every skip).  A skipped tile
+ * changes nothing for the wave: running maximum, row sums and O stay as they are, as if the tile were not in the wave's
+ * list -- o and lse of the wave's rows are bit-identical to the _blocksparse twin run without that tile.  So every P of a
+ * skipped tile is at most e^-pv_thresh relative to the row's true running maximum, a tile whose gap is at least
+ * pv_thresh + lazy on all valid rows is certainly skipped, and the first tile of a list never is.  A threshold that is not
+ * greater than 0, +inf or NaN means "never skip" for that head (mapped to +inf by the kernel; the tensor is not read on
+ * the host).  Every entry of skipped is written by every call: waves whose rows are all >= M and the waves of empty
+ * q-blocks report 0.  No atomics.  A skipping wave issues the same tile copies, waits and barriers as a computing one; it
+ * saves the V fragment reads, the softmax vector work and the P.V MFMAs.
+ * Checked before any launch: pv_thresh NULL or unaligned, skipped unaligned -> SAGE_ERR_INVALID_ARGUMENT; is_causal != 0
+ * and v_mean != NULL -> SAGE_ERR_UNSUPPORTED, as for the twins. */
+int sage_attn_qk_int8_pv_f16_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
+                                                int v_dtype, const sage_tensor* o, int o_dtype, const float* q_scale,
+                                                const float* k_scale, const float* v_mean, float* lse, int B, int Hq,
+                                                int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
+                                                int warpq, float sm_scale, int logit_mult_is_one,
+                                                const int32_t* block_lists, int64_t block_lists_bytes,
+                                                const float* pv_thresh, int32_t* skipped, sage_stream_t stream);
+int sage_attn_qk_int8_pv_f8_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                               const sage_tensor* o, int o_dtype, const float* q_scale,
+                                               const float* k_scale, const float* v_scale, const float* v_mean,
+                                               float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
+                                               int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
+                                               const int32_t* block_lists, int64_t block_lists_bytes,
+                                               const float* pv_thresh, int32_t* skipped, sage_stream_t stream);
+int sage_attn_fusedq_pv_f16_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                               const sage_tensor* v, int v_dtype, const sage_tensor* o, int o_dtype,
+                                               const float* k_scale, const void* km, const float* v_mean, float* lse,
+                                               int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+                                               int warpq, float sm_scale, const int32_t* block_lists,
+                                               int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                               sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                              const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                              const float* k_scale, const void* km, const float* v_scale,
+                                              const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N,
+                                              int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                              const int32_t* block_lists, int64_t block_lists_bytes,
+                                              const float* pv_thresh, int32_t* skipped, sage_stream_t stream);
+
 /* ==== block-map predictor (new: makes the tile lists above from Q and K at run time, after SpargeAttn's first stage --
  * pooled scores gated by the self-similarity of the blocks.  The reference has no counterpart; the rule below is this
  * library's own statement).  Non-causal.  All arithmetic is fp32; inputs are finite. ====

@@ -16,6 +16,9 @@ SOURCES = [
     # packed f32 VALU is slower beside MFMAs; contraction off: the fused Q-quantizer prologue must round exactly like
     # K1 (sage_quant.hip) -- the tile loop spells its fmas out (__builtin_fmaf), so it is unaffected
     ("sage_attn.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # the block-sparse kernels with the P.V skip: the same body and flags, and the wave-uniform skip branch is left a
+    # scalar if / else instead of being structurized (see the file: +40 registers otherwise)
+    ("sage_attn_pvskip.hip", ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-structurizecfg-skip-uniform-regions"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -53,7 +56,9 @@ def _check_occupancy(src, compiler_output):
             name = m.group(1)
         m = re.search(r" VGPRs: (\d+)", line)
         guarded = name and (re.search(r"attn_i8_kernelILi64ELi4E(Lb[01]E){4}Lb0EEE", name) or
-                            re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name))  # the block-sparse twins
+                            re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name) or  # the block-sparse twins
+                            # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
+                            re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name))
         if m and guarded and int(m.group(1)) > 168:
             raise RuntimeError(f"{src}: kernel {name} uses {m.group(1)} VGPRs (> 168: two waves per SIMD instead of three)")
 
@@ -152,6 +157,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # is a text search of the disassembly for `m0` operands; instructions that use M0 implicitly (s_movrel*, GWS,
     # s_sendmsg) would not be caught -- none of them occurs in code hipcc emits for these sources.
     _check_m0_private(os.path.join(CSRC, "sage_attn.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_pvskip.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

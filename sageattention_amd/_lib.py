@@ -115,6 +115,23 @@ SIGNATURES = {
     "sage_attn_fusedq_pv_f8_blocksparse": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_float, c_void_p, c_int64, c_void_p]),
+    # the _blocksparse twins' arguments, then (pv_thresh, skipped) in front of the stream
+    "sage_attn_qk_int8_pv_f16_blocksparse_pvskip": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                            c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
+                                                            c_void_p, c_void_p]),
+    "sage_attn_qk_int8_pv_f8_blocksparse_pvskip": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                           c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
+                                                           c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f16_blocksparse_pvskip": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p,
+                                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                           c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                                           c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f8_blocksparse_pvskip": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                          c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                                          c_void_p, c_void_p]),
     "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -137,8 +137,9 @@ def _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr
 
 
 def _fused_attn(q, k8, ks, v, o, km, v_scale, v_mean, tensor_layout, is_causal, qk_quant_gran, warpq, sm_scale, return_lse,
-                pv_fp8, plan=None):
-    """sage_attn_fusedq_pv_{f16,f8}; with ``plan`` (a BlockSparsePlan) their block-sparse twins."""
+                pv_fp8, plan=None, pv_thresh=None, skipped=None):
+    """sage_attn_fusedq_pv_{f16,f8}; with ``plan`` (a BlockSparsePlan) their block-sparse twins, and with ``pv_thresh``
+    (fp32 [Hq]) on top of it the twins with the P.V skip, which fill ``skipped`` (int32 [B,Hq,ceil(M/128),4] or None)."""
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k8, tensor_layout)
     if Hq % Hk != 0:
@@ -164,6 +165,9 @@ def _fused_attn(q, k8, ks, v, o, km, v_scale, v_mean, tensor_layout, is_causal, 
     if plan is not None:
         name += "_blocksparse"
         args += (plan.lists.data_ptr(), plan.lists.numel() * 4)
+        if pv_thresh is not None:
+            name += "_pvskip"
+            args += (pv_thresh.data_ptr(), L.ptr(skipped))
     L.check(getattr(lib, name)(*args, st), name)
     return lse
 
@@ -548,12 +552,22 @@ def sageattn_block_sparse(
     smooth_k: bool = True,
     return_lse: bool = False,
     is_causal: bool = False,
+    pvthreshd=None,
+    return_skipped: bool = False,
 ):
     """SageAttention over the active 128x64 tiles of a block map (SpargeAttn's ``mask_id`` geometry): ``block_map[b,h,i,j]``
     non-zero means query rows [128 i, 128 i + 128) of head h attend keys [64 j, 64 j + 64); tiles that are off are neither
     read nor computed.  ``block_map`` is a bool/uint8 tensor [B|1, Hq|1, ceil(M/128), ceil(N/64)] or a plan from
     ``block_sparse_plan``.  Non-causal; ``pv`` ("fp16" | "fp8") is explicit.  Rows of a q-block without any active tile are
-    defined: o = 0, lse = -inf.  Same pre-passes and the same kernel loop as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda``."""
+    defined: o = 0, lse = -inf.  Same pre-passes and the same kernel loop as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda``.
+
+    ``pvthreshd`` (a float > 0 or an fp32 tensor [Hq]; natural-log units of the scaled logits, the units of the LSE) turns on
+    SpargeAttn's second stage: a wave (32 query rows) leaves out the softmax and the P.V product of a tile, other than the
+    first of its list, whose scores all lie at least ``pvthreshd`` below the running maximum of their rows (the rule:
+    include/sageattn_hip.h, sage_attn_*_blocksparse_pvskip).  Every probability left out is below e^-pvthreshd.  Values of
+    a tensor that are not > 0, +inf or NaN never skip.  ``return_skipped`` appends the int32 counters
+    [B, Hq, ceil(M/128), 4]: how many tiles each wave skipped.  Returns o, then lse, then the counters, each when asked for."""
+    _check_pvskip_args(pvthreshd, return_skipped)
     if is_causal:  # accepted only to be refused by name: unknown keywords are a TypeError
         raise ValueError("sageattn_block_sparse is non-causal: express the causal structure in the block map")
     if pv not in ("fp16", "fp8"):
@@ -590,10 +604,11 @@ def sageattn_block_sparse(
             if pv == "fp8":
                 v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
         o = torch.empty(q.size(), dtype=dtype, device=q.device)
+        thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, B, Hq, M, q.device)
         lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
-                          pv == "fp8", plan=plan)
-        o = o[..., :head_dim_og]
-        return (o, lse) if return_lse else o
+                          pv == "fp8", plan=plan, pv_thresh=thr, skipped=skipped)
+        out = (o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((skipped,) if return_skipped else ())
+        return out if len(out) > 1 else out[0]
 
 
 # ---- block-map predictor -----------------------------------------------------------------------------------------------------
@@ -604,6 +619,25 @@ def _per_head(value, Hq, device, name):
             raise ValueError(f"{name} must be a float or a tensor of shape [Hq={Hq}], got {tuple(value.shape)}")
         return value.to(device=device, dtype=torch.float32).contiguous()
     return torch.full((Hq,), float(value), dtype=torch.float32, device=device)
+
+
+def _check_pvskip_args(pvthreshd, return_skipped):
+    """The keywords of the P.V skip, checked before anything touches a tensor.  A per-head tensor is not read here (no host
+    synchronisation): the kernel takes values that are not > 0, +inf and NaN as "never skip"."""
+    if pvthreshd is None:
+        if return_skipped:
+            raise ValueError("return_skipped needs pvthreshd: without it nothing is skipped and nothing counted")
+    elif not isinstance(pvthreshd, torch.Tensor) and not float(pvthreshd) > 0.0:
+        raise ValueError(f"pvthreshd must be > 0 (natural-log units of the scaled logits), got {pvthreshd}")
+
+
+def _pvskip_tensors(pvthreshd, return_skipped, B, Hq, M, device):
+    """-> (fp32 [Hq] thresholds or None, int32 [B,Hq,ceil(M/128),4] counters or None); every counter is written by the call"""
+    if pvthreshd is None:
+        return None, None
+    thr = _per_head(pvthreshd, Hq, device, "pvthreshd")
+    skipped = torch.empty((B, Hq, (M + 127) // 128, 4), dtype=torch.int32, device=device) if return_skipped else None
+    return thr, skipped
 
 
 def _check_select_args(topk, keep_first, keep_last):
@@ -689,13 +723,18 @@ def sageattn_sparge(
     topk=None,
     keep_first: int = 0,
     keep_last: int = 0,
+    pvthreshd=None,
+    return_skipped: bool = False,
 ):
     """``sageattn_block_sparse`` on the block map that ``sparge_plan`` predicts for this q and k: the K (or K + V) pre-pass
     runs once, the predictor uses its smoothing mean, and the block-sparse attention kernel reads the predicted lists.
     Bit-identical to ``sageattn_block_sparse(q, k, v, sparge_plan(q, k, ...))``.  Returns o, then the LSE with
     ``return_lse``, then the ``BlockSparsePlan`` with ``return_plan``.  Non-causal.  ``topk``, ``keep_first`` and
-    ``keep_last`` as for ``sparge_plan``: with ``topk`` the budget rule is used and ``cdfthreshd`` is not read."""
+    ``keep_last`` as for ``sparge_plan``: with ``topk`` the budget rule is used and ``cdfthreshd`` is not read.
+    ``pvthreshd`` and ``return_skipped`` as for ``sageattn_block_sparse`` (SpargeAttn's second stage, on the predicted
+    tiles); the counters come last: o, lse, plan, skipped."""
     _check_select_args(topk, keep_first, keep_last)
+    _check_pvskip_args(pvthreshd, return_skipped)
     if pv not in ("fp16", "fp8"):
         raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
     if qk_quant_gran not in ("per_warp", "per_thread"):
@@ -718,7 +757,9 @@ def sageattn_sparge(
         plan, _ = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, False, topk, keep_first,
                                   keep_last)
         o = torch.empty(q.size(), dtype=dtype, device=q.device)
+        thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, plan.B, plan.Hq, plan.M, q.device)
         lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
-                          pv == "fp8", plan=plan)
-        out = (o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((plan,) if return_plan else ())
+                          pv == "fp8", plan=plan, pv_thresh=thr, skipped=skipped)
+        out = ((o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((plan,) if return_plan else ())
+               + ((skipped,) if return_skipped else ()))
         return out if len(out) > 1 else out[0]

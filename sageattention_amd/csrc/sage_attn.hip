@@ -22,9 +22,6 @@
 
 namespace sage {
 
-// K/V slots of the LDS tile ring (see the kernel): 4 for the FP8-PV loop where every wave copies a full share of each tile
-constexpr int attn_ring_slots(int D, int nwaves, bool pv_fp8) { return (pv_fp8 && nwaves * 64 <= 4 * D) ? 4 : 2; }
-
 // PV_FP8 = false: V fp16 [N][D] row major, PV on v_mfma_f32_32x32x16_f16.  V_BF16: V stays bf16 -- P is packed to bf16
 //                 (v_cvt_pk_bf16_f32) and P.V runs on v_mfma_f32_32x32x16_bf16, so the tile is staged and read exactly
 //                 like an fp16 one and nothing is converted (the reference converts V to fp16 first, core.py:633).
@@ -46,7 +43,7 @@ template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8
 //  without scratch, but left alone hipcc settles a few registers above the line)
 __global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kernel(const AttnParams p) {
-  constexpr bool SPARSE = false;
+  constexpr bool SPARSE = false, PVSKIP = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -58,14 +55,18 @@ template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(256, (D == 64 && PV_FP8) ? 3 : 2)
 void attn_i8_blocksparse_kernel(const AttnParams p) {
   constexpr int NWAVES = 4;
-  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true;
+  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
 }
 
+// (attn_i8_blocksparse_pvskip_kernel, the twin with SpargeAttn's second stage -- PVSKIP = true -- is built from the same body
+//  in sage_attn_pvskip.hip: a file of its own because it needs a compiler option of its own, see there)
+
 // The rows of the empty q-blocks of a block-sparse call (no active tile: the attention kernel returns at once): o = 0,
-// lse = -inf.  One workgroup per list row; all but the empty ones leave after one scalar load.
+// lse = -inf, and with skip counters (pv_skipped, else null) the four counters of the q-block = 0.  One workgroup per list
+// row; all but the empty ones leave after one scalar load.
 __global__ __launch_bounds__(256) void attn_blocksparse_empty_kernel(const AttnParams p, const int D) {
   const int qb = blockIdx.x % p.nqb, bh = blockIdx.x / p.nqb;
   if (uniform_load_i32(p.bs_lists + (int64_t)blockIdx.x * p.bs_row) > 0) return;
@@ -75,13 +76,7 @@ __global__ __launch_bounds__(256) void attn_blocksparse_empty_kernel(const AttnP
   for (int i = threadIdx.x; i < rows * per_row; i += 256)
     *reinterpret_cast<uint2*>(ob + (int64_t)(i / per_row) * p.osn + (i % per_row) * 4) = make_uint2(0u, 0u);
   if (p.lse && (int)threadIdx.x < rows) p.lse[((int64_t)b * p.Hq + h) * p.M + qb * 128 + threadIdx.x] = -INFINITY;
-}
-
-// dynamic LDS above the 48 KiB default needs the function attribute; its status is part of the launch status
-static bool allow_lds(const void* kern, size_t bytes) {
-  launch_begin();
-  return bytes <= 48 * 1024 ||
-         hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  if (p.pv_skipped && threadIdx.x < 4) p.pv_skipped[(int64_t)blockIdx.x * 4 + threadIdx.x] = 0;
 }
 
 template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8, bool HAS_MASK>
@@ -96,6 +91,11 @@ static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
 template <int D>
 static int launch_blocksparse(const AttnCall& c, hipStream_t st) {
   const AttnParams& p = c.p;
+  if (c.pvskip) {  // the twin with the P.V skip, then the same empty-row launch (which also zeroes the counters of its rows)
+    if (const int s = launch_blocksparse_pvskip(c, st)) return s;
+    hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(p.nqb * p.Hq * p.B), dim3(256), 0, st, p, c.D);
+    return launch_status();
+  }
   return by_flag(c.pv_fp8, [&](auto fp8) {
     constexpr bool PV_FP8 = decltype(fp8)::value;
     const size_t smem = (size_t)attn_ring_slots(D, 4, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));
@@ -158,6 +158,8 @@ int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const 
   const bool sparse = opt.block_sparse;
   if (sparse) {  // a block map combines with none of the other forms; its lists are read 16 bytes aligned rows
     if (!opt.block_lists || !aligned16(opt.block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
+    if (opt.pv_skip && (!opt.pv_thresh || ((uintptr_t)opt.pv_thresh & 3) || ((uintptr_t)opt.pv_skipped & 3)))
+      return SAGE_ERR_INVALID_ARGUMENT;
     if (is_causal || cu_q || cu_k || mask || kvl || v_mean) return SAGE_ERR_UNSUPPORTED;
   }
   if (mask && (opt.mask_kind < 1 || opt.mask_kind > 3 || !opt.mask_strides || is_causal || pv_fp8 || cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
@@ -247,6 +249,8 @@ int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const 
                                      : ((D == 64 || (pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
   p.nqb = (M + nw * 32 - 1) / (nw * 32);
   if (sparse) { p.bs_lists = opt.block_lists; p.bs_row = (int)block_list_row(N); }  // (share the words of mask / mask_kind)
+  c.pvskip = sparse && opt.pv_skip;
+  if (c.pvskip) { p.pv_thresh = opt.pv_thresh; p.pv_skipped = opt.pv_skipped; }  // (... and those of two mask strides)
   c.D = D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = pv_fp8; c.causal = is_causal != 0; c.kthread = qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = v_dtype == SAGE_BF16;
   return SAGE_OK;
@@ -441,6 +445,74 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dt
                                                   sage_stream_t stream) {
   if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
   AttnOptions opt = blocksparse_options(block_lists, block_lists_bytes);
+  opt.q_dtype = q_dtype;
+  opt.km = km;
+  return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                  is_causal, qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+}
+
+// ---- ... with the P.V skip: the block-sparse twins' arguments, then the per-head thresholds and the skip counters
+static AttnOptions pvskip_options(const int32_t* block_lists, int64_t block_lists_bytes, const float* pv_thresh,
+                                  int32_t* skipped) {
+  AttnOptions opt = blocksparse_options(block_lists, block_lists_bytes);
+  opt.pv_skip = true;
+  opt.pv_thresh = pv_thresh;
+  opt.pv_skipped = skipped;
+  return opt;
+}
+
+extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
+                                                           int v_dtype, const sage_tensor* o, int o_dtype,
+                                                           const float* q_scale, const float* k_scale, const float* v_mean,
+                                                           float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                                           int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
+                                                           int logit_mult_is_one, const int32_t* block_lists,
+                                                           int64_t block_lists_bytes, const float* pv_thresh,
+                                                           int32_t* skipped, sage_stream_t stream) {
+  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream,
+                  pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped));
+}
+
+extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8,
+                                                          const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                                          const float* q_scale, const float* k_scale, const float* v_scale,
+                                                          const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                                          int N, int D, int is_causal, int qk_gran, int blkq, int warpq,
+                                                          float sm_scale, int logit_mult_is_one, const int32_t* block_lists,
+                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                                          sage_stream_t stream) {
+  return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream,
+                  pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped));
+}
+
+extern "C" int sage_attn_fusedq_pv_f16_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                                          const sage_tensor* v, int v_dtype, const sage_tensor* o,
+                                                          int o_dtype, const float* k_scale, const void* km,
+                                                          const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                                          int N, int D, int is_causal, int qk_gran, int warpq,
+                                                          float sm_scale, const int32_t* block_lists,
+                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                                          sage_stream_t stream) {
+  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt = pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped);
+  opt.q_dtype = q_dtype;
+  opt.km = km;
+  return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                  qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+}
+
+extern "C" int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                                         const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                                         const float* k_scale, const void* km, const float* v_scale,
+                                                         const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                                         int N, int D, int is_causal, int qk_gran, int warpq,
+                                                         float sm_scale, const int32_t* block_lists,
+                                                         int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                                         sage_stream_t stream) {
+  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  AttnOptions opt = pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped);
   opt.q_dtype = q_dtype;
   opt.km = km;
   return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,

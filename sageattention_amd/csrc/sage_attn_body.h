@@ -1,12 +1,14 @@
-// The body of the attention kernels (sage_attn.hip): included INTO attn_i8_kernel and attn_i8_blocksparse_kernel, not a
-// header in the usual sense.  Expects in scope: the kernel parameter block `p` and the compile-time constants D, NWAVES,
-// CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE (see sage_attn.hip for what they select).
+// The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip) and
+// attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip), not a header in the usual sense.  Expects in scope: the kernel
+// parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE, PVSKIP
+// (see those two files for what they select).
 #ifndef SAGE_ATTN_BODY_OF_KERNEL
-#error "sage_attn_body.h is the body of the two attention kernels of sage_attn.hip and is included nowhere else"
+#error "sage_attn_body.h is the body of the attention kernels (sage_attn.hip, sage_attn_pvskip.hip): included nowhere else"
 #endif
   static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
   static_assert(!HAS_MASK || (!CAUSAL && !PV_FP8), "attn_mask: non-causal 16-bit-PV operator");
   static_assert(!SPARSE || (NWAVES == 4 && !CAUSAL && !HAS_MASK), "block-sparse: 4 waves = one block row of the map, non-causal");
+  static_assert(!PVSKIP || SPARSE, "the P.V skip exists in the block-sparse form only");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -71,9 +73,12 @@
   // with the count: one scalar round trip in front of the first tile copies.
   const int* bsl = nullptr;
   int bs_count = 0, bs_first[5] = {0, 0, 0, 0, 0};
+  float pv_thr = 0.f;  // PVSKIP: the head's threshold (sage_attn_*_blocksparse_pvskip), in base-2 logit units below
+  (void)pv_thr;
   if constexpr (SPARSE) {
     bsl = p.bs_lists + ((int64_t)bh * p.nqb + qb) * p.bs_row;
     bs_count = uniform_load_i32(bsl);
+    if constexpr (PVSKIP) pv_thr = uniform_load1(p.pv_thresh + h);
     ++bsl;
 #pragma unroll
     for (int i = 0; i < 5; ++i) bs_first[i] = uniform_load_i32(bsl + i);
@@ -94,6 +99,18 @@
   const int q0 = qb * QB + wave * 32;
   const int row = q0 + r;
   const int rowc = min(row, M_ - 1);
+  // PVSKIP: the lanes whose rows take part in the skip decision (rows >= M do not: the padded rows of a ragged q-block
+  // would veto every skip), as a 64-bit lane mask in scalar registers; the skipped tiles of this wave, counted in one
+  uint64_t pv_rows = 0;
+  int n_skipped = 0;
+  (void)pv_rows; (void)n_skipped;
+  if constexpr (PVSKIP) {
+    const int nvalid = min(32, max(0, M_ - q0));
+    const uint64_t half = nvalid >= 32 ? 0xffffffffull : ((1ull << nvalid) - 1ull);
+    pv_rows = half | (half << 32);
+    // a threshold that is not a positive finite number (<= 0, +inf, NaN) never skips
+    pv_thr = (pv_thr > 0.f && pv_thr < __builtin_huge_valf()) ? pv_thr * 1.44269504f : __builtin_huge_valf();
+  }
   // the lane's row / key-half as the masked tiles and the epilogue see them: re-derived from the lane id after the fast loop
   // (below), so that neither they nor the output addresses built from them occupy registers while it runs
   int row_l = row, hh_l = hh;
@@ -516,6 +533,20 @@
         for (int e = 0; e < 16; ++e) acc_o[dt][e] *= alpha;
     }
   };
+  // PVSKIP: the wave leaves out the softmax and P.V of the tile at list position `pos` (row maximum `mx`) iff pos > 0 and
+  // on every row < M the tile's maximum lies at least the threshold below the running reference maximum.  Asked AFTER
+  // maybe_rescale(mx): a row whose maximum grew has m_run = mx there and vetoes.  Wave uniform.
+  auto pv_skip = [&](const int pos, const float mx) __attribute__((always_inline)) -> bool {
+    if constexpr (PVSKIP) {
+      // (the position is made opaque: seeing that `pos > 0` holds from the second tile on, hipcc peels the first round of
+      //  the unrolled fast loops -- a second copy of the hand-placed stream with a register assignment of its own)
+      int po = pos;
+      asm volatile("" : "+s"(po));
+      return po > 0 && (__builtin_amdgcn_ballot_w64(mx > m_run - pv_thr) & pv_rows) == 0;
+    } else {
+      return false;
+    }
+  };
   // P pair -> two packed 16-bit values in the element type of V (RNE both), and the P.V MFMA of that type
   auto pack_p = [&](const v2f two) __attribute__((always_inline)) -> v2h {
     if constexpr (V_BF16) return __builtin_bit_cast(v2h, __builtin_convertvector(two, v2bf));  // v_cvt_pk_bf16_f32
@@ -770,7 +801,31 @@
       dma_k(SPARSE ? bw4 : min(j + RING, last_tile), K_WR);
       load_v(SPARSE ? bw3 : min(j + RING - 1, last_tile), V_WR);
     }
-    if constexpr (PV_FP8) {
+    bool skip = false;
+    if constexpr (PVSKIP) skip = pv_skip(j, mx_cur);
+    if (skip) {
+      // PVSKIP, a negligible tile: only what S(j+1) needs -- its K fragments, its MFMAs, the sequence-end mask and the row
+      // maximum.  No V fragment read, no exponential, no P.V MFMA; m_run, the row sums and O stay as they are.  The copies
+      // above and the wait and barrier below are those of a computing wave.
+      if constexpr (PVSKIP) {
+        ++n_skipped;
+        if constexpr (NEXT != 2) {
+          constexpr int NS = 2 * KS;
+          const int kb = DYN ? 0 : K_RD * KBYTES;
+          v4i kf = kf_early;
+#pragma unroll
+          for (int i = 0; i < NS; ++i) {
+            const int mt = i / KS, ks = i % KS;
+            v4i kn = kf;
+            if (i + 1 < NS) kn = *reinterpret_cast<const v4i*>(k_rd[(i + 1) % KS] + (kb + ((i + 1) / KS) * 32 * D));
+            sb[mt] = ks == 0 ? mfma_s_first(kf, qf[ks]) : __builtin_amdgcn_mfma_i32_32x32x32_i8(kf, qf[ks], sb[mt], 0, 0, 0);
+            kf = kn;
+          }
+          if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(SPARSE ? bw1 : j + 1, sb); }
+          mx_cur = row_max(sb, b0, b1);
+        }
+      }
+    } else if constexpr (PV_FP8) {
       // Hand-placed stream, FP8 PV.  The K = 64 MFMA consumes the P of the whole tile, so all of P(j) precedes the P.V
       // MFMAs; left alone hipcc emits ~110 softmax VALU instructions with the matrix pipe idle and then the 12 MFMAs in
       // one cluster.  Here: the S(j+1) MFMAs are spread through the computation of the eight P words (4 keys each:
@@ -1097,7 +1152,11 @@
         qk((j + 1) % RING, s_nxt);
         if (j + 1 >= n_plain) mask_limit(jt, s_nxt);  // a plain last tile (N % 64 == 0, no diagonal) needs none
       }
-      softmax_pv(j, j % RING, s_cur, sc0, sc1, std::true_type{});
+      if constexpr (PVSKIP) {
+        if (pv_skip(j, mx_cur)) ++n_skipped; else softmax_pv(j, j % RING, s_cur, sc0, sc1, std::true_type{});
+      } else {
+        softmax_pv(j, j % RING, s_cur, sc0, sc1, std::true_type{});
+      }
       if (has_next) mx_cur = row_max(s_nxt, nsc0, nsc1);
       dma_wait_all();
       __syncthreads();
@@ -1185,4 +1244,9 @@
       float* const slot = p.lse + ((int64_t)b * p.Hq + h) * M_ + row_l;
       *slot = p.q_f16 ? lse2 / 1.44269504f + *slot * p.sm_scale : lse2;
     }
+  }
+  // PVSKIP: the wave's count of skipped tiles, one ordinary store by one lane (a wave without a row < M reports 0)
+  if constexpr (PVSKIP) {
+    if (p.pv_skipped && row_l == q0 && hh_l == 0)
+      p.pv_skipped[((int64_t)bh * p.nqb + qb) * 4 + wave] = pv_rows ? n_skipped : 0;
   }

@@ -37,7 +37,11 @@ struct AttnParams {
   // bs_lists / bs_row: the tile lists of sage_block_map_compact, one row of bs_row int32 per (b, h_q, 128-row q-block):
   // [count, tile_0 < tile_1 < ..., kBlockListPad copies of the last tile]
   union { const uint8_t* mask; const int* bs_lists; };
-  int64_t msb, msh, msm, msn;
+  // (the P.V skip of the block-sparse form -- attn_i8_blocksparse_pvskip_kernel -- keeps its two pointers in the first two
+  //  mask strides: pv_thresh fp32 [Hq], pv_skipped int32 [B,Hq,nqb,4] or null)
+  union { int64_t msb; const float* pv_thresh; };
+  union { int64_t msh; int32_t* pv_skipped; };
+  int64_t msm, msn;
   union { int mask_kind; int bs_row; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
   // (b, h_kv) in k8 and in v (always set by run_attn; the dense defaults are 64 rows), and the strides of k_scale
@@ -49,6 +53,16 @@ struct AttnParams {
   int kv_tiled;  // non-default tile strides
   int o_vec16;   // every output row starts on a 16-byte boundary (all strides multiples of 8 elements): 16-byte stores
 };
+
+// K/V slots of the LDS tile ring (see the kernel): 4 for the FP8-PV loop where every wave copies a full share of each tile
+constexpr int attn_ring_slots(int D, int nwaves, bool pv_fp8) { return (pv_fp8 && nwaves * 64 <= 4 * D) ? 4 : 2; }
+
+// dynamic LDS above the 48 KiB default needs the function attribute; its status is part of the launch status
+__host__ inline bool allow_lds(const void* kern, size_t bytes) {
+  launch_begin();
+  return bytes <= 48 * 1024 ||
+         hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
 
 // entries a list row holds beyond its tiles: the deepest read-ahead of the attention loop (the four-slot ring copies K four
 // positions ahead and requests that entry one iteration earlier)

@@ -108,6 +108,9 @@ struct AttnOptions {
   bool block_sparse = false;  // block-sparse form: the tile lists of sage_block_map_compact and the size of their buffer
   const int32_t* block_lists = nullptr;
   int64_t block_lists_bytes = 0;
+  bool pv_skip = false;       // ... with the P.V skip: per-head thresholds (fp32 [Hq]) and the skip counters (or null)
+  const float* pv_thresh = nullptr;
+  int32_t* pv_skipped = nullptr;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -116,12 +119,15 @@ struct AttnCall {
   int D, nwaves;
   bool pv_fp8, causal, kthread, v_bf16;
   bool sparse;  // attn_i8_blocksparse_kernel (always 4 waves)
+  bool pvskip;  // ... its twin attn_i8_blocksparse_pvskip_kernel
 };
 int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
                const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
                const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
                int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt = AttnOptions());
 int attn_launch(const AttnCall& c, hipStream_t st);
+// the attention launch of a block-sparse call with the P.V skip (c.pvskip; sage_attn_pvskip.hip): attn_launch goes through it
+int launch_blocksparse_pvskip(const AttnCall& c, hipStream_t st);
 
 // ---- block-sparse tile lists (sage_misc.hip) ---------------------------------------------------------------------------
 // bytes of the lists of one call: a row of block_list_row(N) int32 per (b, h_q, 128-row q-block)

@@ -11,6 +11,10 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_sparge_select(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layout,
                                                    sm_scale, pv, qk_quant_gran) -> o      (rule "cdf" | "topk", kept key blocks)
     torch.ops.sageattention_amd.attn_sparge_select_lse(...) -> (o, lse)
+    torch.ops.sageattention_amd.attn_block_sparse_pv(q, k, v, block_map, pvthreshd, ...) -> (o, skipped)   (the P.V skip: the
+    torch.ops.sageattention_amd.attn_block_sparse_plan_pv(q, k, v, block_lists, plan_shape, pvthreshd, ...)  per-head threshold
+    torch.ops.sageattention_amd.attn_sparge_pv(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, ...)
+    torch.ops.sageattention_amd.attn_sparge_pv_lse(...) -> (o, lse, skipped)        tensor in, the skip counters out)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -90,14 +94,68 @@ def _(q, k, v, block_lists, plan_shape, tensor_layout, sm_scale, pv, qk_quant_gr
     return q.new_empty(q.shape)
 
 
+def _skipped_like(q, tensor_layout):
+    """the skip counters of a call on q: int32 [B, Hq, ceil(M/128), 4]"""
+    B, H, M = (q.shape[0], q.shape[1], q.shape[2]) if tensor_layout == "HND" else (q.shape[0], q.shape[2], q.shape[1])
+    return q.new_empty((B, H, (M + 127) // 128, 4), dtype=torch.int32)
+
+
+def _lse_like(q, tensor_layout):
+    B, H, M = (q.shape[0], q.shape[1], q.shape[2]) if tensor_layout == "HND" else (q.shape[0], q.shape[2], q.shape[1])
+    return q.new_empty((B, H, M), dtype=torch.float32)
+
+
+# ... with the P.V skip (core.sageattn_block_sparse, pvthreshd): ops of their own, so that the schemas above stay as they
+# are.  The threshold travels as an fp32 [Hq] tensor and the skip counters are always returned.
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_pv", mutates_args=())
+def attn_block_sparse_pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, pvthreshd: torch.Tensor,
+                         tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, skipped = core.sageattn_block_sparse(q, k, v, block_map, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                            qk_quant_gran=qk_quant_gran, pvthreshd=pvthreshd, return_skipped=True)
+    return o.contiguous(), skipped
+
+
+@attn_block_sparse_pv.register_fake
+def _(q, k, v, block_map, pvthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_plan_pv", mutates_args=())
+def attn_block_sparse_plan_pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_lists: torch.Tensor,
+                              plan_shape: Sequence[int], pvthreshd: torch.Tensor, tensor_layout: str, sm_scale: float,
+                              pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    plan = core.BlockSparsePlan(block_lists, *(int(x) for x in plan_shape))
+    o, skipped = core.sageattn_block_sparse(q, k, v, plan, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                            qk_quant_gran=qk_quant_gran, pvthreshd=pvthreshd, return_skipped=True)
+    return o.contiguous(), skipped
+
+
+@attn_block_sparse_plan_pv.register_fake
+def _(q, k, v, block_lists, plan_shape, pvthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
 def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map,
                                      tensor_layout: str = "HND", sm_scale: Optional[float] = None, pv: str = "fp16",
-                                     qk_quant_gran: str = "per_thread"):
-    """``sageattn_block_sparse`` (core.py) as a traceable custom op; ``block_map`` is the map tensor or a plan."""
+                                     qk_quant_gran: str = "per_thread", pvthreshd=None, return_skipped: bool = False):
+    """``sageattn_block_sparse`` (core.py) as a traceable custom op; ``block_map`` is the map tensor or a plan.  With
+    ``pvthreshd`` (a float > 0 or an fp32 tensor [Hq]) it calls the ``_pv`` ops, and ``return_skipped`` appends the skip
+    counters; without it the ops it has always called."""
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    core._check_pvskip_args(pvthreshd, return_skipped)
     if sm_scale is None:
         sm_scale = q.size(-1) ** -0.5
+    if pvthreshd is not None:
+        thr = _as_per_head(pvthreshd, q, tensor_layout)
+        if isinstance(block_map, core.BlockSparsePlan):
+            p = block_map
+            o, skipped = torch.ops.sageattention_amd.attn_block_sparse_plan_pv(
+                q, k, v, p.lists, [p.B, p.Hq, p.M, p.N], thr, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+        else:
+            o, skipped = torch.ops.sageattention_amd.attn_block_sparse_pv(q, k, v, block_map, thr, tensor_layout,
+                                                                          float(sm_scale), pv, qk_quant_gran)
+        return (o, skipped) if return_skipped else o
     if isinstance(block_map, core.BlockSparsePlan):
         p = block_map
         return torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, p.lists, [p.B, p.Hq, p.M, p.N], tensor_layout,
@@ -134,6 +192,14 @@ def _(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gr
     else:
         B, M, H = q.shape[0], q.shape[1], q.shape[2]
     return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+
+
+def _as_per_head(value, q, tensor_layout):
+    """a per-head parameter as the fp32 [Hq] tensor the ops take: a float is broadcast, a tensor passed on"""
+    if isinstance(value, torch.Tensor):
+        return value
+    Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
+    return torch.full((Hq,), float(value), dtype=torch.float32, device=q.device)
 
 
 def _select_kwargs(rule_param: torch.Tensor, rule: str):
@@ -176,23 +242,63 @@ def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layo
     return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
 
 
+@torch.library.custom_op("sageattention_amd::attn_sparge_pv", mutates_args=())
+def attn_sparge_pv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, rule_param: torch.Tensor,
+                   rule: str, keep_first: int, keep_last: int, pvthreshd: torch.Tensor, tensor_layout: str, sm_scale: float,
+                   pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    # attn_sparge_select with the P.V skip on the predicted tiles: the threshold tensor in, the skip counters out
+    o, skipped = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran, keep_first=keep_first, keep_last=keep_last,
+                                      pvthreshd=pvthreshd, return_skipped=True, **_select_kwargs(rule_param, rule))
+    return o.contiguous(), skipped
+
+
+@attn_sparge_pv.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_pv_lse", mutates_args=())
+def attn_sparge_pv_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, rule_param: torch.Tensor,
+                       rule: str, keep_first: int, keep_last: int, pvthreshd: torch.Tensor, tensor_layout: str,
+                       sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    o, lse, skipped = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale,
+                                           pv=pv, qk_quant_gran=qk_quant_gran, return_lse=True, keep_first=keep_first,
+                                           keep_last=keep_last, pvthreshd=pvthreshd, return_skipped=True,
+                                           **_select_kwargs(rule_param, rule))
+    return o.contiguous(), lse, skipped
+
+
+@attn_sparge_pv_lse.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout), _skipped_like(q, tensor_layout)
+
+
 def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
                                simthreshd1=0.6, cdfthreshd=0.98, sm_scale: Optional[float] = None, pv: str = "fp16",
                                qk_quant_gran: str = "per_thread", return_lse: bool = False, topk=None,
-                               keep_first: int = 0, keep_last: int = 0):
+                               keep_first: int = 0, keep_last: int = 0, pvthreshd=None, return_skipped: bool = False):
     """``sageattn_sparge`` (core.py) as a traceable custom op; thresholds and ``topk`` are floats or fp32 tensors [Hq].
     With ``topk`` the budget rule is used and ``cdfthreshd`` is not read; ``keep_first`` / ``keep_last`` pin key blocks on.
     Without any of the three it calls ``attn_sparge`` / ``attn_sparge_lse`` as before, otherwise the ``attn_sparge_select``
-    pair."""
+    pair.  With ``pvthreshd`` (a float > 0 or an fp32 tensor [Hq]) it calls the ``attn_sparge_pv`` pair, and
+    ``return_skipped`` appends the skip counters: o, lse, skipped."""
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
     core._check_select_args(topk, keep_first, keep_last)
+    core._check_pvskip_args(pvthreshd, return_skipped)
     if sm_scale is None:
         sm_scale = q.size(-1) ** -0.5
     Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
     rule, par = ("cdf", cdfthreshd) if topk is None else ("topk", topk)
     thr, par = (t if isinstance(t, torch.Tensor) else torch.full((Hq,), float(t), dtype=torch.float32, device=q.device)
                 for t in (simthreshd1, par))
+    if pvthreshd is not None:
+        pvt = _as_per_head(pvthreshd, q, tensor_layout)
+        op = torch.ops.sageattention_amd.attn_sparge_pv_lse if return_lse else torch.ops.sageattention_amd.attn_sparge_pv
+        out = op(q, k, v, thr, par, rule, keep_first, keep_last, pvt, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+        out = out if return_skipped else out[:-1]
+        return out if len(out) > 1 else out[0]
     if topk is None and keep_first == 0 and keep_last == 0:
         op = torch.ops.sageattention_amd.attn_sparge_lse if return_lse else torch.ops.sageattention_amd.attn_sparge
         return op(q, k, v, thr, par, tensor_layout, float(sm_scale), pv, qk_quant_gran)

@@ -12,7 +12,17 @@ and the time of sage_block_map_compact.  The map is [1,1,ceil(M/128),ceil(N/64)]
 pattern), so that the expanded mask of (c) stays small enough to build.  Patterns: seeded random tiles, and a band of constant
 width around the diagonal (both with the exact density printed, at least one tile per q-block).
 
-usage: blocksparse_bench.py [--launches 300] [--shapes c3,d64,wan,short] [--pv fp16,fp8] [--commit HASH] [--out table.md]"""
+With --pvthreshd T the tool measures the P.V skip instead (sage_attn_qk_int8_pv_{f16,f8}_blocksparse_pvskip) and writes
+profiles/pvskip_sweep.md unless --out says otherwise:
+  cost   the skip kernel at threshold 1e30 (it never skips) against the block-sparse kernel without the skip, random maps of
+         density 1 and 1/4, windows alternating, `--repeats` windows each; the yardstick is the spread of the repeated
+         windows of the kernel without the skip
+  gain   all tiles kept, keys built so that about 1/4, 1/2 and 3/4 of the wave-tiles lie 30 below the row maximum
+         (tests/pvskip_util.py's generator at these shapes), threshold T: time and the skipped share read from the
+         counters, beside the same call without the skip
+
+usage: blocksparse_bench.py [--launches 300] [--shapes c3,d64,wan,short] [--pv fp16,fp8] [--commit HASH] [--out table.md]
+       blocksparse_bench.py --pvthreshd 16 [--shapes c3,d64] [--repeats 4] ..."""
 import argparse
 import ctypes
 import os
@@ -33,6 +43,8 @@ ap.add_argument("--pv", default="fp16,fp8")
 ap.add_argument("--densities", default="1,0.5,0.25,0.125")
 ap.add_argument("--patterns", default="random,band")
 ap.add_argument("--no-masked", action="store_true")
+ap.add_argument("--pvthreshd", type=float, default=None)
+ap.add_argument("--repeats", type=int, default=4)
 ap.add_argument("--commit", default="")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
@@ -75,6 +87,122 @@ def window(fn, n):
     e1.synchronize()
     return e0.elapsed_time(e1) / n  # ms per launch
 
+
+def write_out(default=""):
+    out = a.out or default
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def pvskip_sweep():
+    thr_v = a.pvthreshd
+    emit("# P.V skip of block-sparse attention: kernel times on MI355X")
+    emit()
+    emit(f"commit {a.commit or 'unknown'}; tools/blocksparse_bench.py --pvthreshd {thr_v:g}, {a.launches} launches per window, HIP")
+    emit(f"events, one process, the variants of a row alternating, {a.repeats} windows each (medians).  per-thread scales, fp16")
+    emit("tensors, int8-Q entry points.  plain = sage_attn_qk_int8_pv_*_blocksparse, skip = its _pvskip twin with counters.")
+    shapes = [x for x in a.shapes.split(",") if x in ("c3", "d64")] or ["c3", "d64"]
+    for sname in shapes:
+        B, H, N, D = SHAPES[sname]
+        M = N
+        nqb, ntk = (M + 127) // 128, (N + 63) // 64
+        nbytes = lib.sage_block_sparse_workspace_bytes(B, H, M, N)
+        lists = torch.empty(nbytes // 4, dtype=torch.int32, device="cuda")
+        skipped = torch.empty(B, H, nqb, 4, dtype=torch.int32, device="cuda")
+        thr = torch.empty(H, dtype=torch.float32, device="cuda")
+        o = torch.empty(B, H, N, D, dtype=torch.float16, device="cuda")
+        tail = (None, None, B, H, H, M, N, D, 0, 3, 128, 32, D ** -0.5, 0)
+
+        def operands(q, k, v):
+            k8, ks, km = core._prep_k(k, "HND", "per_thread", True)
+            q8, qs, _ = core._quant_q(q, km, "HND", "per_thread", D ** -0.5, 32, False, H, H)
+            v8, vs, _ = sa.quant.per_channel_fp8(v, tensor_layout="HND", smooth_v=False)
+            v8d = L.SageTensor(v8.data_ptr(), v8.stride(0), v8.stride(1), v8.stride(2))
+            dq, dk, dv, do = (L.desc(t, "HND") for t in (q8, k8, v, o))
+            keep = (q8, qs, k8, ks, v8, vs, v)
+            return {"fp16": ((dq, dk, dv, 0, do, 0, qs.data_ptr(), ks.data_ptr()), "sage_attn_qk_int8_pv_f16_blocksparse"),
+                    "fp8": ((dq, dk, v8d, do, 0, qs.data_ptr(), ks.data_ptr(), vs.data_ptr()),
+                            "sage_attn_qk_int8_pv_f8_blocksparse")}, keep
+
+        def compact(bm):
+            bmv = bm.view(1, 1, nqb, ntk).expand(B, H, nqb, ntk)
+            L.check(lib.sage_block_map_compact(bmv.data_ptr(), (ctypes.c_int64 * 4)(*bmv.stride()), B, H, M, N,
+                                               lists.data_ptr(), nbytes, st), "compact")
+
+        def pair(head, name):
+            def plain():
+                L.check(getattr(lib, name)(*head, *tail, lists.data_ptr(), nbytes, st), name)
+
+            def skip():
+                L.check(getattr(lib, name + "_pvskip")(*head, *tail, lists.data_ptr(), nbytes, thr.data_ptr(),
+                                                       skipped.data_ptr(), st), name + "_pvskip")
+            return plain, skip
+
+        def alternate(plain, skip):
+            tp, ts = [], []
+            for _ in range(a.repeats):
+                tp.append(window(plain, a.launches))
+                ts.append(window(skip, a.launches))
+            return tp, ts
+
+        # ---- cost of the check: random data, the skip kernel never skips
+        torch.manual_seed(0)
+        q, k, v = (torch.randn(B, H, N, D, dtype=torch.float16, device="cuda") for _ in range(3))
+        ops, keep = operands(q, k, v)
+        thr.fill_(1e30)
+        emit()
+        emit(f"## {sname} (B, H, N, D) = {(B, H, N, D)}: cost of the check (threshold 1e30, nothing skipped)")
+        emit()
+        emit("| PV | density | t_plain ms (median) | plain spread % | t_skip ms (median) | t_skip / t_plain | difference vs spread |")
+        emit("|---|---|---|---|---|---|---|")
+        for pv in a.pv.split(","):
+            for dens in (1.0, 0.25):
+                bm = make_map("random", nqb, ntk, dens, seed=int(dens * 1000) + N).cuda()
+                compact(bm)
+                tp, ts = alternate(*pair(*ops[pv]))
+                assert int(skipped.abs().sum()) == 0
+                mp, ms = statistics.median(tp), statistics.median(ts)
+                spread = 100 * (max(tp) - min(tp)) / mp
+                diff = 100 * (ms - mp) / mp
+                verdict = "inside" if abs(diff) <= spread else f"outside by {abs(diff) - spread:.2f} points"
+                emit(f"| {pv} | {float(bm.float().mean()):.3f} | {mp:.4f} | {spread:.2f} | {ms:.4f} | {ms / mp:.4f} | "
+                     f"{diff:+.2f} % ({verdict}) |")
+        del q, k, ops, keep
+        # ---- gain: every tile kept, a share of them 30 below the row maximum
+        emit()
+        emit(f"## {sname}: gain at pvthreshd = {thr_v:g} (all tiles kept; keys of the marked tiles 30 below the best)")
+        emit()
+        emit("| PV | tiles marked | skipped share (counters) | t_plain ms | t_skip ms | t_skip / t_plain |")
+        emit("|---|---|---|---|---|---|")
+        compact(torch.ones(nqb, ntk, dtype=torch.bool, device="cuda"))
+        thr.fill_(thr_v)
+        for share in (0.25, 0.5, 0.75):
+            g = torch.Generator().manual_seed(int(share * 100) + N)
+            low = torch.rand(ntk, generator=g) < share
+            low[0] = False  # the first tile sets the maximum
+            qq = 0.05 * torch.randn(B, H, N, D, generator=g)
+            qq[..., 0] += 0.5 * D ** 0.5
+            kk = 0.05 * torch.randn(B, H, N, D, generator=g)
+            kk[..., 0] += (-60.0 * low.float()).repeat_interleave(64)[:N]
+            ops, keep = operands(qq.half().cuda(), kk.half().cuda(), v)
+            for pv in a.pv.split(","):
+                tp, ts = alternate(*pair(*ops[pv]))
+                got = float(skipped.sum()) / (B * H * nqb * 4 * ntk)
+                mp, ms = statistics.median(tp), statistics.median(ts)
+                emit(f"| {pv} | {float(low.float().mean()):.3f} | {got:.3f} | {mp:.4f} | {ms:.4f} | {ms / mp:.3f} |")
+            del ops, keep
+        del v, o, lists
+        torch.cuda.empty_cache()
+    write_out("profiles/pvskip_sweep.md")
+
+
+if a.pvthreshd is not None:
+    if not a.pvthreshd > 0:
+        sys.exit("--pvthreshd must be > 0")
+    pvskip_sweep()
+    sys.exit(0)
 
 emit("# Block-sparse attention: kernel times on MI355X")
 emit()
@@ -156,7 +284,4 @@ for sname in a.shapes.split(","):
              f"max {max(dense_all):.4f} (spread {100 * (max(dense_all) - min(dense_all)) / med:.2f} % of the median)")
     del q, k, v, q8, k8, v8, o
     torch.cuda.empty_cache()
-if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+write_out()

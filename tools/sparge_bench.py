@@ -8,7 +8,9 @@ block pure noise, K shifted by +3 on every channel).
      bytes of the shape.  `--mode kernels` only launches those kernels a few times, for `rocprofv3 --kernel-trace --stats`.
   2. the predictor (pool Q + pool K + select) as a share of the dense sageattn call and of the resulting sparse call.
   3. at cdfthreshd 0.9 / 0.95 / 0.98: density of the predicted map, end-to-end sageattn_sparge against dense sageattn, and
-     calc_diff (1 - 2<x,y>/(|x|^2+|y|^2)) of its output against dense sageattn's.
+     calc_diff (1 - 2<x,y>/(|x|^2+|y|^2)) of its output against dense sageattn's.  With `--pvthreshd T` two more columns:
+     the share of the kept wave-tiles whose softmax and P.V the second stage skipped at that threshold (from the counters of
+     return_skipped) and calc_diff of that output against dense.
   4. the selection launch alone (sage_block_select on ready statistics) under both rules, in alternating windows; with
      `--parent-lib` also sage_block_select_cdf of that library (a build of the parent commit) in the same rotation, with the
      spread of its repeated windows as the margin and a bit-for-bit comparison of the lists.
@@ -17,7 +19,7 @@ block pure noise, K shifted by +3 on every channel).
 SYNTHETIC data: the densities and errors say nothing about a real model.
 
 usage: sparge_bench.py [--launches 300] [--shapes c3,wan] [--pv fp16] [--mode all|kernels] [--topks 0.125,0.25,0.5]
-                       [--parent-lib parent.so] [--commit HASH] [--out table.md]"""
+                       [--pvthreshd T] [--parent-lib parent.so] [--commit HASH] [--out table.md]"""
 import argparse
 import ctypes
 import os
@@ -38,6 +40,7 @@ ap.add_argument("--mode", default="all", choices=("all", "kernels"))
 ap.add_argument("--simthreshd1", type=float, default=0.6)
 ap.add_argument("--cdfs", default="0.9,0.95,0.98")
 ap.add_argument("--topks", default="0.125,0.25,0.5")
+ap.add_argument("--pvthreshd", type=float, default=None, help="second stage: skip negligible wave-tiles at this threshold")
 ap.add_argument("--parent-lib", default="", help="a build of the parent commit: its sage_block_select_cdf is the yardstick")
 ap.add_argument("--commit", default="")
 ap.add_argument("--out", default="")
@@ -145,8 +148,9 @@ for sname in a.shapes.split(","):
         emit(f"| {n} | {spread(ts[n])} | {med:.4f} | {nbytes / med / 1e6:.0f} |")
     emit()
     emit("| cdfthreshd | density | tiles per q-block min / mean / max | predictor ms | dense sageattn ms | sparse call ms | predictor / dense | "
-         "predictor / sparse | sageattn_sparge ms | speed-up over dense | calc_diff vs dense |")
-    emit("|---|---|---|---|---|---|---|---|---|---|---|")
+         "predictor / sparse | sageattn_sparge ms | speed-up over dense | calc_diff vs dense |"
+         + (f" pvthreshd {a.pvthreshd:g}: skipped share of kept wave-tiles | ... calc_diff vs dense |" if a.pvthreshd else ""))
+    emit("|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|" if a.pvthreshd else ""))
     dense_fn = sa.sageattn_qk_int8_pv_fp16_cuda if a.pv == "fp16" else sa.sageattn_qk_int8_pv_fp8_cuda
     o_dense = dense_fn(q, k, v)
     dense_all, cdf_runs = [], []
@@ -161,8 +165,13 @@ for sname in a.shapes.split(","):
         dense_all.append(t_d)
         cdf_runs.append((cdf, dens, t_s))
         o = sa.sageattn_sparge(q, k, v, simthreshd1=a.simthreshd1, cdfthreshd=cdf, pv=a.pv)
+        extra = ""
+        if a.pvthreshd:
+            o_pv, skipped = sa.sageattn_sparge(q, k, v, simthreshd1=a.simthreshd1, cdfthreshd=cdf, pv=a.pv,
+                                               pvthreshd=a.pvthreshd, return_skipped=True)
+            extra = f" {float(skipped.sum()) / (4.0 * float(bmap.sum())):.3f} | {calc_diff(o_pv, o_dense):.3e} |"
         emit(f"| {cdf} | {dens:.3f} | {int(cnt.min())} / {float(cnt.mean()):.1f} / {int(cnt.max())} | {t_p:.4f} | {t_d:.4f} | {t_s:.4f} | "
-             f"{t_p / t_d:.4f} | {t_p / t_s:.4f} | {t_e:.4f} | {t_d / t_e:.2f} | {calc_diff(o, o_dense):.3e} |")
+             f"{t_p / t_d:.4f} | {t_p / t_s:.4f} | {t_e:.4f} | {t_d / t_e:.2f} | {calc_diff(o, o_dense):.3e} |" + extra)
     emit()
     emit(f"dense sageattn, {len(dense_all)} repeated windows: {spread(dense_all)}")
 
