@@ -189,6 +189,14 @@ def desc(t: torch.Tensor, tensor_layout: str) -> SageTensor:
     raise ValueError(f"Unknown tensor layout: {tensor_layout}")
 
 
+def desc_vt(v8: torch.Tensor, tensor_layout: str) -> SageTensor:
+    """Descriptor of the FP8 V^T of ``per_channel_fp8`` / ``kv_prepare_fp8``, [B,Hk,D,Npad] (HND) or [B,D,Hk,Npad] (NHD):
+    stride_n is the stride of the d index."""
+    if tensor_layout == "HND":
+        return SageTensor(v8.data_ptr(), v8.stride(0), v8.stride(1), v8.stride(2))
+    return SageTensor(v8.data_ptr(), v8.stride(0), v8.stride(2), v8.stride(1))
+
+
 def dims(t: torch.Tensor, tensor_layout: str):
     """-> (B, H, N, D)"""
     if tensor_layout == "HND":

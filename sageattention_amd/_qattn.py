@@ -90,15 +90,10 @@ def _attn_f8(query, key, value, output, query_scale, key_scale, value_scale, val
     blkq, warpq = _blkq_warpq(query_scale, query, tensor_layout, qk_quant_gran)
     lse = torch.empty((B, Hq, M), dtype=torch.float32, device=query.device) if return_lse else \
         torch.empty((0,), dtype=torch.float32, device=query.device)
-    # value: [B,Hk,D,Npad] (HND) or [B,D,Hk,Npad] (NHD) -> descriptor with stride_n := stride of the d index
-    if layout == "HND":
-        vd = L.SageTensor(value.data_ptr(), value.stride(0), value.stride(1), value.stride(2))
-    else:
-        vd = L.SageTensor(value.data_ptr(), value.stride(0), value.stride(2), value.stride(1))
     vm = value_mean.to(torch.float32).contiguous() if value_mean is not None else None
     st = L.lib().sage_attn_qk_int8_pv_f8(
-        L.desc(query, layout), L.desc(key, layout), vd, L.desc(output, layout), L.dtype_code(output.dtype),
-        query_scale.contiguous().data_ptr(), key_scale.contiguous().data_ptr(),
+        L.desc(query, layout), L.desc(key, layout), L.desc_vt(value, layout), L.desc(output, layout),
+        L.dtype_code(output.dtype), query_scale.contiguous().data_ptr(), key_scale.contiguous().data_ptr(),
         value_scale.contiguous().data_ptr(), L.ptr(vm), lse.data_ptr() if return_lse else None,
         B, Hq, Hk, M, N, D, int(is_causal), int(qk_quant_gran), blkq, warpq, float(sm_scale), 0,
         L.stream_ptr(query.device))

@@ -7,6 +7,7 @@ argument handling runs as hand-written HIP through the C ABI (include/sageattn_h
 (with the LSE correction fused), V fp16/fp8 preparation and the fused attention kernel.  No Triton, no
 rocWMMA, no debug dumps (the fork's torch.save side effects, core.py:320-352,845-881, are not reproduced)."""
 import ctypes
+import functools
 import warnings
 from typing import Any, Optional
 
@@ -121,9 +122,8 @@ def _prep_k(k, tensor_layout, qk_quant_gran, smooth_k):
     gran, rnd = _k_pairing(qk_quant_gran)
     if smooth_k:
         return k_smooth_quant(k, tensor_layout, gran, rnd)
-    km = None
-    k8, ks, _ = _quant(k, tensor_layout, gran, True, 64, 64, 1.0, rnd, mean=km, dense_heads=True)
-    return k8, ks, km
+    k8, ks, _ = _quant(k, tensor_layout, gran, True, 64, 64, 1.0, rnd, mean=None, dense_heads=True)
+    return k8, ks, None
 
 
 def _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr, Hq, Hk):
@@ -136,40 +136,56 @@ def _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr
     return _quant(q, tensor_layout, gran, False, 128, WARPQ, 1.0, rnd, dot_vec=dot_vec, dot_group=Hq // Hk, dense_heads=True)
 
 
-def _fused_attn(q, k8, ks, v, o, km, v_scale, v_mean, tensor_layout, is_causal, qk_quant_gran, warpq, sm_scale, return_lse,
-                pv_fp8, plan=None, pv_thresh=None, skipped=None):
-    """sage_attn_fusedq_pv_{f16,f8}; with ``plan`` (a BlockSparsePlan) their block-sparse twins, and with ``pv_thresh``
-    (fp32 [Hq]) on top of it the twins with the P.V skip, which fill ``skipped`` (int32 [B,Hq,ceil(M/128),4] or None)."""
+def _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv_fp8, smooth_v):
+    """The K pre-pass of the multi-call operators, and for FP8 P.V the V pre-pass -> (k8, ks, km, v or v8, v_scale, vm).  ``km``
+    is None without ``smooth_k``, ``v_scale`` None for FP16 P.V (v is passed through), ``vm`` None without ``smooth_v``."""
+    # K and V by ONE call (sage_kv_prepare_fp8: it smooths K, does not smooth V and wants V in K's shape).  This is what each
+    # caller spelled out before: sageattn_qk_int8_pv_fp8_cuda `smooth_k and not smooth_v and k.shape == v.shape and k.dtype ==
+    # v.dtype` (pv_fp8 True; equal dtypes are asserted by _common_checks), sageattn_block_sparse `pv == "fp8" and smooth_k and
+    # k.shape == v.shape` (smooth_v False), sageattn_sparge `pv == "fp8" and k.shape == v.shape` (smooth_k True, smooth_v False)
+    if pv_fp8 and smooth_k and not smooth_v and k.shape == v.shape:
+        gran, rnd = _k_pairing(qk_quant_gran)
+        return kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0) + (None,)
+    k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
+    if not pv_fp8:
+        return k8, ks, km, v, None, None
+    return (k8, ks, km) + per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=smooth_v)
+
+
+def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, sparse=None):
+    """sage_attn_fusedq_pv_{f16,f8} on the operands ``kv`` of ``_prepass`` (FP8 P.V where it has a v_scale); ``q_quant`` is
+    (qk_quant_gran, rows per Q scale group).  With ``sparse`` = (plan, pv_thresh, skipped) their block-sparse twins, and with
+    a ``pv_thresh`` (fp32 [Hq]) in it the twins with the P.V skip, which fill ``skipped`` (int32 [B,Hq,ceil(M/128),4] or
+    None).  -> (o, lse or None)"""
+    k8, ks, km, v, v_scale, v_mean = kv
+    qk_quant_gran, warpq = q_quant
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k8, tensor_layout)
     if Hq % Hk != 0:
         raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
+    o = torch.empty(q.size(), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, M), dtype=torch.float32, device=q.device) if return_lse else None
-    lib, st = L.lib(), L.stream_ptr(q.device)
     vm = v_mean.to(torch.float32).contiguous() if v_mean is not None else None
-    if pv_fp8:
-        vd = (L.SageTensor(v.data_ptr(), v.stride(0), v.stride(1), v.stride(2)) if tensor_layout == "HND"
-              else L.SageTensor(v.data_ptr(), v.stride(0), v.stride(2), v.stride(1)))
-        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), vd,
-                L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km),
-                v_scale.data_ptr(), L.ptr(vm), L.ptr(lse), B, Hq, Hk, M, N, D, int(is_causal),
-                _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
+    shape = (B, Hq, Hk, M, N, D, int(is_causal), _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
+    if v_scale is not None:
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc_vt(v, tensor_layout),
+                L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km), v_scale.data_ptr(), L.ptr(vm),
+                L.ptr(lse)) + shape
         name = "sage_attn_fusedq_pv_f8"
     else:
-        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout),
-                L.desc(v, tensor_layout), L.dtype_code(v.dtype), L.desc(o, tensor_layout),
-                L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km), L.ptr(vm), L.ptr(lse),
-                B, Hq, Hk, M, N, D, int(is_causal), _GRAN_CODE[qk_quant_gran], warpq,
-                float(sm_scale))
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc(v, tensor_layout),
+                L.dtype_code(v.dtype), L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), L.ptr(km), L.ptr(vm),
+                L.ptr(lse)) + shape
         name = "sage_attn_fusedq_pv_f16"
-    if plan is not None:
+    if sparse is not None:
+        plan, pv_thresh, skipped = sparse
         name += "_blocksparse"
         args += (plan.lists.data_ptr(), plan.lists.numel() * 4)
         if pv_thresh is not None:
             name += "_pvskip"
             args += (pv_thresh.data_ptr(), L.ptr(skipped))
-    L.check(getattr(lib, name)(*args, st), name)
-    return lse
+    L.check(getattr(L.lib(), name)(*args, L.stream_ptr(q.device)), name)
+    return o, lse
 
 
 # One ctypes crossing and two allocations (output + workspace) per call: sage_sageattn_pv_{f16,f8} (csrc/sage_op.hip)
@@ -209,26 +225,22 @@ def _sage_fp16(q, k, v, tensor_layout, is_causal, qk_quant_gran, sm_scale, smoot
         _, Hk, _, _ = L.dims(k, tensor_layout)
         if ONE_CALL and smooth_k and not smooth_v and qk_quant_gran in ("per_warp", "per_thread"):
             o, lse = _one_call(q, k, v, tensor_layout, is_causal, qk_quant_gran, WARPQ, sm_scale, return_lse, False)
-            o = o[..., :head_dim_og]
-            return (o, lse) if return_lse else o
+            return _pack(o[..., :head_dim_og], lse, None, None)
         k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
-        o = torch.empty(q.size(), dtype=dtype, device=q.device)
         vm = None
         if smooth_v:
             v, vm = sub_mean(v, tensor_layout)
         if FUSE_Q_QUANT and not qk_quant_gran.startswith("per_block") and L.dims(q, tensor_layout)[2] <= FUSE_Q_MAX_SEQ:
-            lse = _fused_attn(q, k8, ks, v, o, km, None, vm, tensor_layout, is_causal, qk_quant_gran, WARPQ, sm_scale,
-                              return_lse, False)
-            o = o[..., :head_dim_og]
-            return (o, lse) if return_lse else o
+            o, lse = _fused_attn(q, (k8, ks, km, v, None, vm), tensor_layout, is_causal, (qk_quant_gran, WARPQ), sm_scale,
+                                 return_lse)
+            return _pack(o[..., :head_dim_og], lse, None, None)
+        o = torch.empty(q.size(), dtype=dtype, device=q.device)
         q8, qs, corr = _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, return_lse, Hq, Hk)
         lse2 = _qattn._attn_f16(q8, k8, v, o, qs, ks, vm, 0 if tensor_layout == "NHD" else 1, int(is_causal),
                                 _GRAN_CODE[qk_quant_gran], sm_scale, int(return_lse),
                                 logit_mult_is_one=qk_quant_gran.startswith("per_block"))
-        o = o[..., :head_dim_og]
-        if return_lse:
-            return o, _finish_lse(lse2, corr if smooth_k else None, sm_scale)
-        return o
+        lse = _finish_lse(lse2, corr if smooth_k else None, sm_scale) if return_lse else None
+        return _pack(o[..., :head_dim_og], lse, None, None)
 
 
 @torch.compiler.disable
@@ -327,10 +339,8 @@ def sageattn_qk_int8_pv_fp16_triton(
             L.desc(o, tensor_layout), L.dtype_code(dtype), qs.data_ptr(), ks.data_ptr(), attn_mask.data_ptr(), kind, strides,
             L.ptr(lse2), B, Hq, Hk, M, N, D, _GRAN_CODE[gran], 128, 128 if per_block else 32, float(sm_scale),
             1 if per_block else 0, L.stream_ptr(q.device)), "sage_attn_qk_int8_pv_f16_masked")
-        o = o[..., :head_dim_og]
-        if return_lse:
-            return o, _finish_lse(lse2, corr if smooth_k else None, sm_scale)
-        return o
+        lse = _finish_lse(lse2, corr if smooth_k else None, sm_scale) if return_lse else None
+        return _pack(o[..., :head_dim_og], lse, None, None)
 
 
 @torch.compiler.disable
@@ -366,29 +376,18 @@ def sageattn_qk_int8_pv_fp8_cuda(
         _, Hk, _, _ = L.dims(k, tensor_layout)
         if ONE_CALL and smooth_k and not smooth_v and k.shape == v.shape:
             o, lse = _one_call(q, k, v, tensor_layout, is_causal, qk_quant_gran, 32, sm_scale, return_lse, True)
-            o = o[..., :head_dim_og]
-            return (o, lse) if return_lse else o
-        o = torch.empty(q.size(), dtype=dtype, device=q.device)
-        if smooth_k and not smooth_v and k.shape == v.shape and k.dtype == v.dtype:
-            # the default configuration: K and V prepared by one call (two launches at every length)
-            gran, rnd = _k_pairing(qk_quant_gran)
-            k8, ks, km, v8, v_scale = kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0)
-            vm = None
-        else:
-            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
-            v8, v_scale, vm = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=smooth_v)
+            return _pack(o[..., :head_dim_og], lse, None, None)
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, True, smooth_v)
         if FUSE_Q_QUANT and L.dims(q, tensor_layout)[2] <= FUSE_Q_MAX_SEQ:
-            lse = _fused_attn(q, k8, ks, v8, o, km, v_scale, vm, tensor_layout, is_causal, qk_quant_gran, 32, sm_scale,
-                              return_lse, True)
-            o = o[..., :head_dim_og]
-            return (o, lse) if return_lse else o
+            o, lse = _fused_attn(q, kv, tensor_layout, is_causal, (qk_quant_gran, 32), sm_scale, return_lse)
+            return _pack(o[..., :head_dim_og], lse, None, None)
+        k8, ks, km, v8, v_scale, vm = kv
+        o = torch.empty(q.size(), dtype=dtype, device=q.device)
         q8, qs, corr = _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, 32, return_lse, Hq, Hk)
         lse2 = _qattn._attn_f8(q8, k8, v8, o, qs, ks, v_scale, vm, 0 if tensor_layout == "NHD" else 1, int(is_causal),
                                _GRAN_CODE[qk_quant_gran], sm_scale, int(return_lse))
-        o = o[..., :head_dim_og]
-        if return_lse:
-            return o, _finish_lse(lse2, corr if smooth_k else None, sm_scale)
-        return o
+        lse = _finish_lse(lse2, corr if smooth_k else None, sm_scale) if return_lse else None
+        return _pack(o[..., :head_dim_og], lse, None, None)
 
 
 @torch.compiler.disable
@@ -507,6 +506,12 @@ class BlockSparsePlan:
         self.lists, self.B, self.Hq, self.M, self.N = lists, B, Hq, M, N
 
 
+@functools.lru_cache(maxsize=64)
+def _plan_ints(B, Hq, M, N):
+    """int32 entries of the lists of a plan: the library's own sizing, so that the row layout is written down once"""
+    return L.lib().sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4
+
+
 def _check_block_map(block_map, B, Hq, M, N):
     """[B|1, Hq|1, ceil(M/128), ceil(N/64)] bool / uint8 -> the [B,Hq,..] view (0 strides where it broadcasts)"""
     if not isinstance(block_map, torch.Tensor):
@@ -531,10 +536,9 @@ def block_sparse_plan(block_map: torch.Tensor, M: int, N: int, B: Optional[int] 
     m = _check_block_map(block_map, B, Hq, M, N)
     if not m.is_cuda:
         raise ValueError("block_map must be on the GPU")
-    lib = L.lib()
-    lists = torch.empty(lib.sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4, dtype=torch.int32, device=m.device)
+    lists = torch.empty(_plan_ints(B, Hq, M, N), dtype=torch.int32, device=m.device)
     with torch.cuda.device(m.device):
-        L.check(lib.sage_block_map_compact(m.data_ptr(), (ctypes.c_int64 * 4)(*m.stride()), B, Hq, M, N, lists.data_ptr(),
+        L.check(L.lib().sage_block_map_compact(m.data_ptr(), (ctypes.c_int64 * 4)(*m.stride()), B, Hq, M, N, lists.data_ptr(),
                                            lists.numel() * 4, L.stream_ptr(m.device)), "sage_block_map_compact")
     return BlockSparsePlan(lists, B, Hq, M, N)
 
@@ -570,17 +574,14 @@ def sageattn_block_sparse(
     _check_pvskip_args(pvthreshd, return_skipped)
     if is_causal:  # accepted only to be refused by name: unknown keywords are a TypeError
         raise ValueError("sageattn_block_sparse is non-causal: express the causal structure in the block map")
-    if pv not in ("fp16", "fp8"):
-        raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
-    if qk_quant_gran not in ("per_warp", "per_thread"):
-        raise ValueError("qk_quant_gran must be either 'per_warp' or 'per_thread'.")
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
     B, Hq, M, _ = L.dims(q, tensor_layout)
     N = L.dims(k, tensor_layout)[2]
     if isinstance(block_map, BlockSparsePlan):
         if (block_map.B, block_map.Hq, block_map.M, block_map.N) != (B, Hq, M, N):
             raise ValueError(f"the plan was made for (B, Hq, M, N) = {(block_map.B, block_map.Hq, block_map.M, block_map.N)}, "
                              f"the call has {(B, Hq, M, N)}")
-        need = (B * Hq * ((M + 127) // 128) * (((1 + (N + 63) // 64 + 5) + 3) // 4 * 4))
+        need = _plan_ints(B, Hq, M, N)
         if block_map.lists.dtype != torch.int32 or block_map.lists.numel() != need or not block_map.lists.is_contiguous():
             raise ValueError(f"the plan's lists must be {need} contiguous int32, as block_sparse_plan makes them")
         map_dev = block_map.lists.device
@@ -589,26 +590,45 @@ def sageattn_block_sparse(
         map_dev = block_map.device
     if map_dev != q.device:
         raise ValueError(f"block_map is on {map_dev}, q on {q.device}")
-    dtype = _common_checks(q, k, v)
+
+    def plan_from(q, k, km, sm_scale):
+        return block_map if isinstance(block_map, BlockSparsePlan) else block_sparse_plan(block_map, M, N)
+    return _block_sparse_tail(q, k, v, tensor_layout, sm_scale, (pv, qk_quant_gran, smooth_k), plan_from,
+                              (return_lse, False, pvthreshd, return_skipped))
+
+
+def _check_sparse_args(pv, qk_quant_gran, tensor_layout):
+    if pv not in ("fp16", "fp8"):
+        raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
+    if qk_quant_gran not in ("per_warp", "per_thread"):
+        raise ValueError("qk_quant_gran must be either 'per_warp' or 'per_thread'.")
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+
+
+def _pack(o, lse, plan, skipped):
+    """The return value of an operator: o, then lse, plan and skipped in this order, each unless None."""
+    out = tuple(x for x in (o, lse, plan, skipped) if x is not None)
+    return out if len(out) > 1 else out[0]
+
+
+def _block_sparse_tail(q, k, v, tensor_layout, sm_scale, quant, plan_from, want):
+    """What ``sageattn_block_sparse`` and ``sageattn_sparge`` do below their argument checks: pad, the K (or K + V)
+    pre-pass, the plan -- ``plan_from(q, k, km, sm_scale)`` on the padded views and the smoothing mean --, the block-sparse
+    attention kernel and the return tuple.  ``quant`` = (pv, qk_quant_gran, smooth_k), ``want`` = (return_lse, return_plan,
+    pvthreshd, return_skipped)."""
+    pv, qk_quant_gran, smooth_k = quant
+    return_lse, return_plan, pvthreshd, return_skipped = want
+    _common_checks(q, k, v)
     with torch.cuda.device(q.device):
         q, k, v, head_dim_og = _pad_head_dim(q, k, v)
         if sm_scale is None:
             sm_scale = head_dim_og ** -0.5
-        plan = block_map if isinstance(block_map, BlockSparsePlan) else block_sparse_plan(block_map, M, N)
-        v_scale = None
-        if pv == "fp8" and smooth_k and k.shape == v.shape:
-            gran, rnd = _k_pairing(qk_quant_gran)
-            k8, ks, km, v, v_scale = kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0)
-        else:
-            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
-            if pv == "fp8":
-                v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
-        o = torch.empty(q.size(), dtype=dtype, device=q.device)
-        thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, B, Hq, M, q.device)
-        lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
-                          pv == "fp8", plan=plan, pv_thresh=thr, skipped=skipped)
-        out = (o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((skipped,) if return_skipped else ())
-        return out if len(out) > 1 else out[0]
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv == "fp8", False)
+        plan = plan_from(q, k, kv[2], sm_scale)
+        thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, plan.B, plan.Hq, plan.M, q.device)
+        o, lse = _fused_attn(q, kv, tensor_layout, False, (qk_quant_gran, 32), sm_scale, return_lse, (plan, thr, skipped))
+        return _pack(o[..., :head_dim_og], lse, plan if return_plan else None, skipped)
 
 
 # ---- block-map predictor -----------------------------------------------------------------------------------------------------
@@ -650,10 +670,11 @@ def _check_select_args(topk, keep_first, keep_last):
             raise ValueError(f"{name} must be an int >= 0 (a number of 64-key blocks), got {value!r}")
 
 
-def _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, want_map, topk=None, keep_first=0,
-                    keep_last=0):
-    """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select (rule TOPK when
-    ``topk`` is given, else CDF) -> (plan, uint8 map or None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
+def _sparge_predict(q, k, km, tensor_layout, sm_scale, want_map, select):
+    """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select with ``select`` =
+    (simthreshd1, cdfthreshd, topk, keep_first, keep_last): rule TOPK when ``topk`` is given, else CDF -> (plan, uint8 map or
+    None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
+    simthreshd1, cdfthreshd, topk, keep_first, keep_last = select
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k, tensor_layout)
     if Hq % Hk != 0:
@@ -665,11 +686,10 @@ def _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, 
         rule, par = L.SELECT_TOPK, _per_head(topk, Hq, q.device, "topk")
     pq, sq = block_pool_sim(q, 128, tensor_layout)
     pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
-    lib = L.lib()
-    lists = torch.empty(lib.sage_block_sparse_workspace_bytes(B, Hq, M, N) // 4, dtype=torch.int32, device=q.device)
+    lists = torch.empty(_plan_ints(B, Hq, M, N), dtype=torch.int32, device=q.device)
     bmap = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.uint8, device=q.device) if want_map else None
     ntk = (N + 63) // 64  # keeps beyond it act as ntk
-    L.check(lib.sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
+    L.check(L.lib().sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
                                   float(sm_scale), thr.data_ptr(), rule, par.data_ptr(), min(keep_first, ntk),
                                   min(keep_last, ntk), lists.data_ptr(), lists.numel() * 4, L.ptr(bmap),
                                   L.stream_ptr(q.device)), "sage_block_select")
@@ -702,8 +722,8 @@ def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", si
             km = k_mean(k, tensor_layout)
         else:
             km = torch.nn.functional.pad(km, (0, k.size(-1) - km.size(-1))).to(k.dtype).contiguous()
-        plan, bmap = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, return_map, topk,
-                                     keep_first, keep_last)
+        plan, bmap = _sparge_predict(q, k, km, tensor_layout, sm_scale, return_map,
+                                     (simthreshd1, cdfthreshd, topk, keep_first, keep_last))
     return (plan, bmap.view(torch.bool)) if return_map else plan
 
 
@@ -735,31 +755,11 @@ def sageattn_sparge(
     tiles); the counters come last: o, lse, plan, skipped."""
     _check_select_args(topk, keep_first, keep_last)
     _check_pvskip_args(pvthreshd, return_skipped)
-    if pv not in ("fp16", "fp8"):
-        raise ValueError(f"pv must be 'fp16' or 'fp8', got {pv}")
-    if qk_quant_gran not in ("per_warp", "per_thread"):
-        raise ValueError("qk_quant_gran must be either 'per_warp' or 'per_thread'.")
-    if tensor_layout not in ("HND", "NHD"):
-        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
-    dtype = _common_checks(q, k, v)
-    with torch.cuda.device(q.device):
-        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
-        if sm_scale is None:
-            sm_scale = head_dim_og ** -0.5
-        v_scale = None
-        if pv == "fp8" and k.shape == v.shape:
-            gran, rnd = _k_pairing(qk_quant_gran)
-            k8, ks, km, v, v_scale = kv_prepare_fp8(k, v, tensor_layout, gran, rnd, scale_max=448.0)
-        else:
-            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
-            if pv == "fp8":
-                v, v_scale, _ = per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=False)
-        plan, _ = _sparge_predict(q, k, km, tensor_layout, simthreshd1, cdfthreshd, sm_scale, False, topk, keep_first,
-                                  keep_last)
-        o = torch.empty(q.size(), dtype=dtype, device=q.device)
-        thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, plan.B, plan.Hq, plan.M, q.device)
-        lse = _fused_attn(q, k8, ks, v, o, km, v_scale, None, tensor_layout, False, qk_quant_gran, 32, sm_scale, return_lse,
-                          pv == "fp8", plan=plan, pv_thresh=thr, skipped=skipped)
-        out = ((o[..., :head_dim_og],) + ((lse,) if return_lse else ()) + ((plan,) if return_plan else ())
-               + ((skipped,) if return_skipped else ()))
-        return out if len(out) > 1 else out[0]
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+
+    select = (simthreshd1, cdfthreshd, topk, keep_first, keep_last)
+
+    def plan_from(q, k, km, sm_scale):
+        return _sparge_predict(q, k, km, tensor_layout, sm_scale, False, select)[0]
+    return _block_sparse_tail(q, k, v, tensor_layout, sm_scale, (pv, qk_quant_gran, True), plan_from,
+                              (return_lse, return_plan, pvthreshd, return_skipped))

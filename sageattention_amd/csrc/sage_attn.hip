@@ -18,7 +18,7 @@
 //
 // Roofline: MFMA (4*M*N*D flop per (b,h); half int8 at 2x the fp16 rate), VALU/exp2 co-limited.
 // Algorithmic HBM bytes per (b,h): M*D (Q) + N*D (K) + 2*N*D (V fp16) + 2*M*D (O) + scales.
-#include "sage_entry.h"
+#include "sage_attn_launch.h"
 
 namespace sage {
 
@@ -87,29 +87,14 @@ static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
   return launch_status();
 }
 
-// block-sparse form: 4 waves, non-causal, no attn_mask
-template <int D>
+// block-sparse form: the kernel, or its twin with the P.V skip (sage_attn_pvskip.hip), then the rows of the empty q-blocks
 static int launch_blocksparse(const AttnCall& c, hipStream_t st) {
-  const AttnParams& p = c.p;
-  if (c.pvskip) {  // the twin with the P.V skip, then the same empty-row launch (which also zeroes the counters of its rows)
-    if (const int s = launch_blocksparse_pvskip(c, st)) return s;
-    hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(p.nqb * p.Hq * p.B), dim3(256), 0, st, p, c.D);
-    return launch_status();
-  }
-  return by_flag(c.pv_fp8, [&](auto fp8) {
-    constexpr bool PV_FP8 = decltype(fp8)::value;
-    const size_t smem = (size_t)attn_ring_slots(D, 4, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));
-    return by_flag(c.kthread, [&](auto k) {
-      return by_flag(!PV_FP8 && c.v_bf16, [&](auto v) {
-        constexpr bool V_BF16 = !PV_FP8 && decltype(v)::value;
-        auto kern = attn_i8_blocksparse_kernel<D, decltype(k)::value, V_BF16, PV_FP8>;
-        if (!allow_lds((const void*)kern, smem)) return (int)SAGE_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(p.nqb * p.Hq * p.B), dim3(256), smem, st, p);
-        hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(p.nqb * p.Hq * p.B), dim3(256), 0, st, p, D);
-        return launch_status();
-      });
-    });
+  const int s = c.pvskip ? launch_blocksparse_pvskip(c, st) : launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
+    return attn_i8_blocksparse_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
   });
+  if (s) return s;
+  hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(c.p.nqb * c.p.Hq * c.p.B), dim3(256), 0, st, c.p, c.D);
+  return launch_status();
 }
 
 template <int D, int NWAVES>
@@ -121,7 +106,7 @@ static int launch_attn(const AttnCall& c, hipStream_t st) {
     auto by_v = [&](auto f) { if constexpr (PV_FP8) return f(std::false_type{}); else return by_flag(c.v_bf16, f); };
     if constexpr (!PV_FP8) {
       if (p.mask) {  // attn_mask variant (non-causal, fp16 V: checked by attn_check)
-        const size_t smem = 2 * 64 * D + 2 * 64 * D * 2;
+        const size_t smem = attn_lds_bytes(D, NWAVES, false);
         return by_flag(c.kthread, [&](auto k) {
           return by_v([&](auto v) {
             return launch_kernel<D, NWAVES, false, decltype(k)::value, decltype(v)::value, false, true>(p, smem, st);
@@ -129,7 +114,7 @@ static int launch_attn(const AttnCall& c, hipStream_t st) {
         });
       }
     }
-    const size_t smem = (size_t)attn_ring_slots(D, NWAVES, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));  // RING x (K tile + V tile)
+    const size_t smem = attn_lds_bytes(D, NWAVES, PV_FP8);
     return by_flag(c.causal, [&](auto ca) {
       return by_flag(c.kthread, [&](auto k) {
         return by_v([&](auto v) {
@@ -145,135 +130,140 @@ static int launch_attn(const AttnCall& c, hipStream_t st) {
 static thread_local int g_nwaves_override = 0;
 
 // argument checks of the attention entry points; fills the kernel parameters and the geometry
-int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
-               const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
-               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
-               int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt) {
-  const int* const cu_q = opt.cu_q;
-  const int* const cu_k = opt.cu_k;
-  const int q_dtype = opt.q_dtype;
-  const void* const km = opt.km;
-  const void* const mask = opt.mask;
-  const sage_kv_layout* const kvl = opt.kvl;
-  const bool sparse = opt.block_sparse;
+int attn_check(AttnCall& c, const AttnArgs& a) {
+  const float* q_scale = a.q_scale;
+  int warpq = a.warpq;
+  const bool sparse = a.block_sparse;
   if (sparse) {  // a block map combines with none of the other forms; its lists are read 16 bytes aligned rows
-    if (!opt.block_lists || !aligned16(opt.block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
-    if (opt.pv_skip && (!opt.pv_thresh || ((uintptr_t)opt.pv_thresh & 3) || ((uintptr_t)opt.pv_skipped & 3)))
+    if (!a.block_lists || !aligned16(a.block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
+    if (a.pv_skip && (!a.pv_thresh || ((uintptr_t)a.pv_thresh & 3) || ((uintptr_t)a.pv_skipped & 3)))
       return SAGE_ERR_INVALID_ARGUMENT;
-    if (is_causal || cu_q || cu_k || mask || kvl || v_mean) return SAGE_ERR_UNSUPPORTED;
+    if (a.is_causal || a.cu_q || a.cu_k || a.mask || a.kvl || a.v_mean) return SAGE_ERR_UNSUPPORTED;
   }
-  if (mask && (opt.mask_kind < 1 || opt.mask_kind > 3 || !opt.mask_strides || is_causal || pv_fp8 || cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
-  const bool fusedq = q_dtype >= 0;  // q8 is then the fp16/bf16 query tensor
-  if ((cu_q == nullptr) != (cu_k == nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.mask && (a.mask_kind < 1 || a.mask_kind > 3 || !a.mask_strides || a.is_causal || a.pv_fp8 || a.cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
+  const bool fusedq = a.q_dtype >= 0;  // a.q is then the fp16/bf16 query tensor
+  if ((a.cu_q == nullptr) != (a.cu_k == nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
   if (fusedq) {
-    if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-    if (qk_gran == SAGE_GRAN_PER_BLOCK || cu_q || (km && !aligned16(km))) return SAGE_ERR_UNSUPPORTED;
-    if (!tensor_ok(q8, 8) || !k_scale) return SAGE_ERR_INVALID_ARGUMENT;
-    q_scale = k_scale;  // unused placeholder so the shared checks below pass
+    if (a.q_dtype != SAGE_F16 && a.q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+    if (a.qk_gran == SAGE_GRAN_PER_BLOCK || a.cu_q || (a.km && !aligned16(a.km))) return SAGE_ERR_UNSUPPORTED;
+    if (!tensor_ok(a.q, 8) || !a.k_scale) return SAGE_ERR_INVALID_ARGUMENT;
+    q_scale = a.k_scale;  // unused placeholder so the shared checks below pass
   }
-  if (cu_q && (pv_fp8 || lse)) return SAGE_ERR_UNSUPPORTED;  // packed sequences: fp16 PV, no LSE (as the reference)
-  if (!tensor_ok(q8, fusedq ? 8 : 16) || !tensor_ok(k8, 16) || !tensor_ok(v, pv_fp8 ? 16 : 8) || !tensor_ok(o, 4) || !q_scale ||
-      !k_scale)
+  if (a.cu_q && (a.pv_fp8 || a.lse)) return SAGE_ERR_UNSUPPORTED;  // packed sequences: fp16 PV, no LSE (as the reference)
+  if (!tensor_ok(a.q, fusedq ? 8 : 16) || !tensor_ok(a.k8, 16) || !tensor_ok(a.v, a.pv_fp8 ? 16 : 8) || !tensor_ok(a.o, 4) || !q_scale ||
+      !a.k_scale)
     return SAGE_ERR_INVALID_ARGUMENT;
-  if (pv_fp8 && !v_scale) return SAGE_ERR_INVALID_ARGUMENT;
-  if (B <= 0 || Hq <= 0 || Hk <= 0 || M <= 0 || N <= 0 || Hq % Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if (sparse && opt.block_lists_bytes < block_sparse_bytes(B, Hq, M, N)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.pv_fp8 && !a.v_scale) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.B <= 0 || a.Hq <= 0 || a.Hk <= 0 || a.M <= 0 || a.N <= 0 || a.Hq % a.Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if (sparse && a.block_lists_bytes < block_sparse_bytes(a.B, a.Hq, a.M, a.N)) return SAGE_ERR_INVALID_ARGUMENT;
   // the integer row max and the -inf mask pattern rely on a positive, finite dequantisation scale
-  if (!logit_mult_is_one && !(sm_scale > 0.f && sm_scale < 1.0e30f)) return SAGE_ERR_INVALID_ARGUMENT;
-  if (const int s = dim_dtype_status(D, v_dtype)) return s;
-  if (o_dtype != SAGE_F16 && o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  if (qk_gran < SAGE_GRAN_PER_BLOCK || qk_gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
-  if (blkq != 64 && blkq != 128) return SAGE_ERR_INVALID_ARGUMENT;
-  if (qk_gran == SAGE_GRAN_PER_BLOCK) warpq = blkq;
-  if ((warpq != 16 && warpq != 32 && warpq != 64 && warpq != 128) || blkq % warpq != 0) return SAGE_ERR_INVALID_ARGUMENT;
-  if ((v_mean && !aligned16(v_mean)) || (v_scale && !aligned16(v_scale))) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!a.logit_mult_is_one && !(a.sm_scale > 0.f && a.sm_scale < 1.0e30f)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (const int s = dim_dtype_status(a.D, a.v_dtype)) return s;
+  if (a.o_dtype != SAGE_F16 && a.o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.qk_gran < SAGE_GRAN_PER_BLOCK || a.qk_gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.blkq != 64 && a.blkq != 128) return SAGE_ERR_INVALID_ARGUMENT;
+  if (a.qk_gran == SAGE_GRAN_PER_BLOCK) warpq = a.blkq;
+  if ((warpq != 16 && warpq != 32 && warpq != 64 && warpq != 128) || a.blkq % warpq != 0) return SAGE_ERR_INVALID_ARGUMENT;
+  if ((a.v_mean && !aligned16(a.v_mean)) || (a.v_scale && !aligned16(a.v_scale))) return SAGE_ERR_INVALID_ARGUMENT;
   // KV tile layout: dense by default (a tile = 64 consecutive rows of the sage_tensor), explicit for tile-major buffers
-  const int64_t ntile = ((int64_t)N + 63) >> 6;
-  int64_t k_tile = 64 * k8->stride_n, v_tile = pv_fp8 ? 64 : 128 * v->stride_n;  // bytes
-  const int per_tile = qk_gran == SAGE_GRAN_PER_THREAD ? 4 : 1;
-  int64_t ks_h = ntile * per_tile, ks_b = ks_h * Hk, ks_t = per_tile;
+  const int64_t ntile = ((int64_t)a.N + 63) >> 6;
+  int64_t k_tile = 64 * a.k8->stride_n, v_tile = a.pv_fp8 ? 64 : 128 * a.v->stride_n;  // bytes
+  const int per_tile = a.qk_gran == SAGE_GRAN_PER_THREAD ? 4 : 1;
+  int64_t ks_h = ntile * per_tile, ks_b = ks_h * a.Hk, ks_t = per_tile;
   bool tiled = false;
-  if (kvl) {
-    if (cu_q || mask || kvl->k_tile_stride < 0 || kvl->v_tile_stride < 0) return SAGE_ERR_INVALID_ARGUMENT;
-    if (kvl->k_tile_stride) { k_tile = kvl->k_tile_stride; tiled = true; }
-    if (kvl->v_tile_stride) { v_tile = pv_fp8 ? kvl->v_tile_stride : 2 * kvl->v_tile_stride; tiled = true; }
-    if (kvl->ks_stride_b || kvl->ks_stride_h || kvl->ks_stride_tile) {
-      if (kvl->ks_stride_tile < per_tile || kvl->ks_stride_h < 0 || kvl->ks_stride_b < 0) return SAGE_ERR_INVALID_ARGUMENT;
-      ks_b = kvl->ks_stride_b; ks_h = kvl->ks_stride_h; ks_t = kvl->ks_stride_tile;
+  if (a.kvl) {
+    if (a.cu_q || a.mask || a.kvl->k_tile_stride < 0 || a.kvl->v_tile_stride < 0) return SAGE_ERR_INVALID_ARGUMENT;
+    if (a.kvl->k_tile_stride) { k_tile = a.kvl->k_tile_stride; tiled = true; }
+    if (a.kvl->v_tile_stride) { v_tile = a.pv_fp8 ? a.kvl->v_tile_stride : 2 * a.kvl->v_tile_stride; tiled = true; }
+    if (a.kvl->ks_stride_b || a.kvl->ks_stride_h || a.kvl->ks_stride_tile) {
+      if (a.kvl->ks_stride_tile < per_tile || a.kvl->ks_stride_h < 0 || a.kvl->ks_stride_b < 0) return SAGE_ERR_INVALID_ARGUMENT;
+      ks_b = a.kvl->ks_stride_b; ks_h = a.kvl->ks_stride_h; ks_t = a.kvl->ks_stride_tile;
       if (per_tile == 4 && ((ks_b | ks_h | ks_t) & 3)) return SAGE_ERR_INVALID_ARGUMENT;  // 16-B scalar loads
     }
     if ((k_tile & 15) || (v_tile & 15)) return SAGE_ERR_INVALID_ARGUMENT;
   }
   // the K/V slices of one (b, h_kv) are addressed with 32-bit buffer offsets
   const int64_t lim = (int64_t)1 << 31;
-  if (ntile * k_tile + 64 * k8->stride_n + D >= lim) return SAGE_ERR_TOO_LARGE;
-  if (pv_fp8 ? (ntile * v_tile + (int64_t)D * v->stride_n + 64 >= lim) : (ntile * v_tile + (64 * v->stride_n + D) * 2 >= lim)) return SAGE_ERR_TOO_LARGE;
+  if (ntile * k_tile + 64 * a.k8->stride_n + a.D >= lim) return SAGE_ERR_TOO_LARGE;
+  if (a.pv_fp8 ? (ntile * v_tile + (int64_t)a.D * a.v->stride_n + 64 >= lim) : (ntile * v_tile + (64 * a.v->stride_n + a.D) * 2 >= lim)) return SAGE_ERR_TOO_LARGE;
   if (ks_t * ntile >= lim) return SAGE_ERR_TOO_LARGE;
   AttnParams& p = c.p;
-  p.q = (const int8_t*)q8->data; p.qsb = q8->stride_b; p.qsh = q8->stride_h; p.qsn = q8->stride_n;
-  p.k = (const int8_t*)k8->data; p.ksb = k8->stride_b; p.ksh = k8->stride_h; p.ksn = k8->stride_n;
-  p.v = (const uint8_t*)v->data; p.vsb = v->stride_b; p.vsh = v->stride_h; p.vsn = v->stride_n;
-  p.o = (uint16_t*)o->data; p.osb = o->stride_b; p.osh = o->stride_h; p.osn = o->stride_n;
-  p.q_scale = q_scale; p.k_scale = k_scale; p.v_scale = v_scale; p.v_mean = v_mean; p.lse = lse;
-  p.B = B; p.Hq = Hq; p.Hk = Hk; p.M = M; p.N = N;
-  const int nblkq = (M + blkq - 1) / blkq;
-  p.gq = qk_gran == SAGE_GRAN_PER_BLOCK ? nblkq : qk_gran == SAGE_GRAN_PER_WARP ? nblkq * (blkq / warpq) : nblkq * (blkq / warpq) * 8;
-  const int nblkk = (N + 63) / 64;
-  p.gk = qk_gran == SAGE_GRAN_PER_THREAD ? nblkk * 4 : nblkk;
-  p.qgran = qk_gran; p.blkq = blkq; p.warpq = warpq;
-  p.logit_mult = logit_mult_is_one ? 1.0f : sm_scale * kLog2e;
-  p.out_bf16 = o_dtype == SAGE_BF16;
-  p.cu_q = cu_q; p.cu_k = cu_k;
-  p.mask = (const uint8_t*)mask; p.mask_kind = mask ? opt.mask_kind : 0;
-  const int64_t* const ms = opt.mask_strides;
-  p.msb = mask ? ms[0] : 0; p.msh = mask ? ms[1] : 0; p.msm = mask ? ms[2] : 0; p.msn = mask ? ms[3] : 0;
+  p.q = (const int8_t*)a.q->data; p.qsb = a.q->stride_b; p.qsh = a.q->stride_h; p.qsn = a.q->stride_n;
+  p.k = (const int8_t*)a.k8->data; p.ksb = a.k8->stride_b; p.ksh = a.k8->stride_h; p.ksn = a.k8->stride_n;
+  p.v = (const uint8_t*)a.v->data; p.vsb = a.v->stride_b; p.vsh = a.v->stride_h; p.vsn = a.v->stride_n;
+  p.o = (uint16_t*)a.o->data; p.osb = a.o->stride_b; p.osh = a.o->stride_h; p.osn = a.o->stride_n;
+  p.q_scale = q_scale; p.k_scale = a.k_scale; p.v_scale = a.v_scale; p.v_mean = a.v_mean; p.lse = a.lse;
+  p.B = a.B; p.Hq = a.Hq; p.Hk = a.Hk; p.M = a.M; p.N = a.N;
+  const int nblkq = (a.M + a.blkq - 1) / a.blkq;
+  p.gq = a.qk_gran == SAGE_GRAN_PER_BLOCK ? nblkq : a.qk_gran == SAGE_GRAN_PER_WARP ? nblkq * (a.blkq / warpq) : nblkq * (a.blkq / warpq) * 8;
+  const int nblkk = (a.N + 63) / 64;
+  p.gk = a.qk_gran == SAGE_GRAN_PER_THREAD ? nblkk * 4 : nblkk;
+  p.qgran = a.qk_gran; p.blkq = a.blkq; p.warpq = warpq;
+  p.logit_mult = a.logit_mult_is_one ? 1.0f : a.sm_scale * kLog2e;
+  p.out_bf16 = a.o_dtype == SAGE_BF16;
+  p.cu_q = a.cu_q; p.cu_k = a.cu_k;
+  p.mask = (const uint8_t*)a.mask; p.mask_kind = a.mask ? a.mask_kind : 0;
+  const int64_t* const ms = a.mask_strides;
+  p.msb = a.mask ? ms[0] : 0; p.msh = a.mask ? ms[1] : 0; p.msm = a.mask ? ms[2] : 0; p.msn = a.mask ? ms[3] : 0;
   p.k_tile_bytes = (int)k_tile; p.v_tile_bytes = (int)v_tile; p.ks_b = ks_b; p.ks_h = ks_h; p.ks_t = (int)ks_t;
   p.kv_tiled = tiled ? 1 : 0;
-  p.o_vec16 = (o->stride_b % 8 == 0 && o->stride_h % 8 == 0 && o->stride_n % 8 == 0) ? 1 : 0;  // 16-byte aligned output rows
-  p.q_f16 = fusedq ? (const uint16_t*)q8->data : nullptr;
-  p.km = (const uint16_t*)km; p.q_bf16 = q_dtype == SAGE_BF16; p.sm_scale = sm_scale;
+  p.o_vec16 = (a.o->stride_b % 8 == 0 && a.o->stride_h % 8 == 0 && a.o->stride_n % 8 == 0) ? 1 : 0;  // 16-byte aligned output rows
+  p.q_f16 = fusedq ? (const uint16_t*)a.q->data : nullptr;
+  p.km = (const uint16_t*)a.km; p.q_bf16 = a.q_dtype == SAGE_BF16; p.sm_scale = a.sm_scale;
   // measured on MI355X: D=128 fp16 PV -> one 8-wave workgroup per CU (4-wave: -3 %); D=128 fp8 PV -> two 4-wave
   // workgroups per CU (+3.6 % non-causal, +5.7 % causal); D=64 (<= 168 VGPRs) -> 4-wave workgroups, 3 per CU
   // ... except for short key sequences (few tiles per workgroup, so prologue and epilogue weigh more and two smaller
   // workgroups per CU overlap them better): end to end, 4-wave 0.959x the 8-wave time at 2048 keys, 0.979x at 3072, 0.998x
   // at 4096, 1.02x from 6144; causal 0.993x at 8192 (4096 keys per row on average) -> 4 waves up to 3072 keys per row
   // (profiles/r03_ab/geometry_end_to_end.log).
-  const int keys_per_row = is_causal ? N / 2 : N;
+  const int keys_per_row = a.is_causal ? a.N / 2 : a.N;
   // FP8 PV at head_dim 128: 4-wave workgroups +2.2 % at 8K keys, +0.7 % at 16K, -1.1 % at 32K, -1.3 % at 64K.  The two
   // co-resident 4-wave workgroups of a CU drift apart on a long stream until they no longer share K/V tiles in L2 (1.90x the
   // algorithmic HBM-side bytes with 4 waves, 1.00x with 8: profiles/r03_ab/fetch_by_geometry.md) -> 8 waves beyond 24K keys per row.
   // (block-sparse: always 4 waves -- a workgroup is one block row of the map; the tuning knobs do not apply)
   const int nw = sparse                ? 4
-                 : opt.nwaves          ? opt.nwaves
+                 : a.nwaves            ? a.nwaves
                  : g_nwaves_override ? g_nwaves_override
-                                     : ((D == 64 || (pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
-  p.nqb = (M + nw * 32 - 1) / (nw * 32);
-  if (sparse) { p.bs_lists = opt.block_lists; p.bs_row = (int)block_list_row(N); }  // (share the words of mask / mask_kind)
-  c.pvskip = sparse && opt.pv_skip;
-  if (c.pvskip) { p.pv_thresh = opt.pv_thresh; p.pv_skipped = opt.pv_skipped; }  // (... and those of two mask strides)
-  c.D = D; c.nwaves = nw; c.sparse = sparse;
-  c.pv_fp8 = pv_fp8; c.causal = is_causal != 0; c.kthread = qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = v_dtype == SAGE_BF16;
+                                     : ((a.D == 64 || (a.pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
+  p.nqb = (a.M + nw * 32 - 1) / (nw * 32);
+  if (sparse) { p.bs_lists = a.block_lists; p.bs_row = (int)block_list_row(a.N); }  // (share the words of mask / mask_kind)
+  c.pvskip = sparse && a.pv_skip;
+  if (c.pvskip) { p.pv_thresh = a.pv_thresh; p.pv_skipped = a.pv_skipped; }  // (... and those of two mask strides)
+  c.D = a.D; c.nwaves = nw; c.sparse = sparse;
+  c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;
 }
 
 int attn_launch(const AttnCall& c, hipStream_t st) {
+  if (c.sparse) return launch_blocksparse(c, st);
   return by_dim(c.D, [&](auto d) {
-    if (c.sparse) return launch_blocksparse<decltype(d)::value>(c, st);
     return c.nwaves == 8 ? launch_attn<decltype(d)::value, 8>(c, st) : launch_attn<decltype(d)::value, 4>(c, st);
   });
 }
 
 // the public entry points: check, then launch
-static int run_attn(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
-                    const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
-                    const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
-                    int blkq, int warpq, float sm_scale, int logit_mult_is_one, sage_stream_t stream,
-                    const AttnOptions& opt = AttnOptions()) {
+static int run_attn(const AttnArgs& a, sage_stream_t stream) {
   AttnCall c;
-  if (const int s = attn_check(c, q8, k8, v, pv_fp8, v_dtype, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M,
-                               N, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, opt))
-    return s;
+  if (const int s = attn_check(c, a)) return s;
   return attn_launch(c, (hipStream_t)stream);
+}
+
+// the fused-Q forms: q is the fp16 / bf16 query tensor, km the k_mean of the LSE correction; 128-row q-blocks, and the
+// kernel applies sm_scale
+static int fused_q(AttnArgs& a, int q_dtype, const void* km) {
+  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
+  a.q_dtype = q_dtype; a.km = km; a.blkq = 128; a.logit_mult_is_one = 0;
+  return SAGE_OK;
+}
+
+// the block-sparse forms: the tile lists of sage_block_map_compact
+static void block_sparse(AttnArgs& a, const int32_t* block_lists, int64_t block_lists_bytes) {
+  a.block_sparse = true; a.block_lists = block_lists; a.block_lists_bytes = block_lists_bytes;
+}
+
+// ... with the P.V skip: the per-head thresholds and the skip counters
+static void pv_skip(AttnArgs& a, const float* pv_thresh, int32_t* skipped) {
+  a.pv_skip = true; a.pv_thresh = pv_thresh; a.pv_skipped = skipped;
 }
 
 }  // namespace sage
@@ -286,7 +276,6 @@ extern "C" int sage_set_tuning(int key, int value) {
     g_nwaves_override = value;
     return SAGE_OK;
   }
-
   return SAGE_ERR_INVALID_ARGUMENT;
 }
 
@@ -300,8 +289,11 @@ extern "C" int sage_attn_qk_int8_pv_f16(const sage_tensor* q8, const sage_tensor
                                         const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                         int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                         int logit_mult_is_one, sage_stream_t stream) {
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -309,8 +301,12 @@ extern "C" int sage_attn_qk_int8_pv_f8(const sage_tensor* q8, const sage_tensor*
                                        const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                        int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                        int logit_mult_is_one, sage_stream_t stream) {
-  return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -319,24 +315,24 @@ extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage
                                                int max_seqlen_q, int max_seqlen_k, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!cu_seqlens_q || !cu_seqlens_k) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.cu_q = cu_seqlens_q;
-  opt.cu_k = cu_seqlens_k;
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, nullptr, num_seqs, Hq, Hk,
-                  max_seqlen_q, max_seqlen_k, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one,
-                  stream, opt);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.B = num_seqs; a.Hq = Hq; a.Hk = Hk; a.M = max_seqlen_q; a.N = max_seqlen_k;
+  a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
                                        const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
                                        const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                        int is_causal, int qk_gran, int warpq, float sm_scale, sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.warpq = warpq; a.sm_scale = sm_scale;
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -344,12 +340,12 @@ extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const s
                                       const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                       int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                       sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -358,12 +354,12 @@ extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage
                                                int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
                                                float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!attn_mask) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.mask = attn_mask;
-  opt.mask_kind = mask_kind;
-  opt.mask_strides = mask_strides;
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, 0, qk_gran,
-                  blkq, warpq, sm_scale, logit_mult_is_one, stream, opt);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq;
+  a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one; a.mask = attn_mask; a.mask_kind = mask_kind;
+  a.mask_strides = mask_strides;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
@@ -372,10 +368,11 @@ extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sag
                                                 int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                                 sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.kvl = kv_layout;
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, nullptr, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.kvl = kv_layout;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -384,21 +381,14 @@ extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage
                                                int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt;
-  opt.kvl = kv_layout;
-  return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, nullptr, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.kvl = kv_layout;
+  return run_attn(a, stream);
 }
 
 // ---- block-sparse forms: the dense twins' arguments plus the tile lists of sage_block_map_compact
-static AttnOptions blocksparse_options(const int32_t* block_lists, int64_t block_lists_bytes) {
-  AttnOptions opt;
-  opt.block_sparse = true;
-  opt.block_lists = block_lists;
-  opt.block_lists_bytes = block_lists_bytes;
-  return opt;
-}
-
 extern "C" int sage_attn_qk_int8_pv_f16_blocksparse(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
                                                     int v_dtype, const sage_tensor* o, int o_dtype, const float* q_scale,
                                                     const float* k_scale, const float* v_mean, float* lse, int B, int Hq,
@@ -406,8 +396,12 @@ extern "C" int sage_attn_qk_int8_pv_f16_blocksparse(const sage_tensor* q8, const
                                                     int warpq, float sm_scale, int logit_mult_is_one,
                                                     const int32_t* block_lists, int64_t block_lists_bytes,
                                                     sage_stream_t stream) {
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream, blocksparse_options(block_lists, block_lists_bytes));
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse(a, block_lists, block_lists_bytes);
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8_blocksparse(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
@@ -417,9 +411,13 @@ extern "C" int sage_attn_qk_int8_pv_f8_blocksparse(const sage_tensor* q8, const 
                                                    int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
                                                    const int32_t* block_lists, int64_t block_lists_bytes,
                                                    sage_stream_t stream) {
-  return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream,
-                  blocksparse_options(block_lists, block_lists_bytes));
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse(a, block_lists, block_lists_bytes);
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f16_blocksparse(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
@@ -428,12 +426,13 @@ extern "C" int sage_attn_fusedq_pv_f16_blocksparse(const sage_tensor* q, int q_d
                                                    int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
                                                    int warpq, float sm_scale, const int32_t* block_lists,
                                                    int64_t block_lists_bytes, sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt = blocksparse_options(block_lists, block_lists_bytes);
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse(a, block_lists, block_lists_bytes);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
@@ -443,24 +442,16 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dt
                                                   int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                                   const int32_t* block_lists, int64_t block_lists_bytes,
                                                   sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt = blocksparse_options(block_lists, block_lists_bytes);
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse(a, block_lists, block_lists_bytes);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }
 
 // ---- ... with the P.V skip: the block-sparse twins' arguments, then the per-head thresholds and the skip counters
-static AttnOptions pvskip_options(const int32_t* block_lists, int64_t block_lists_bytes, const float* pv_thresh,
-                                  int32_t* skipped) {
-  AttnOptions opt = blocksparse_options(block_lists, block_lists_bytes);
-  opt.pv_skip = true;
-  opt.pv_thresh = pv_thresh;
-  opt.pv_skipped = skipped;
-  return opt;
-}
-
 extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
                                                            int v_dtype, const sage_tensor* o, int o_dtype,
                                                            const float* q_scale, const float* k_scale, const float* v_mean,
@@ -469,9 +460,13 @@ extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_pvskip(const sage_tensor* q8
                                                            int logit_mult_is_one, const int32_t* block_lists,
                                                            int64_t block_lists_bytes, const float* pv_thresh,
                                                            int32_t* skipped, sage_stream_t stream) {
-  return run_attn(q8, k8, v, false, v_dtype, o, o_dtype, q_scale, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream,
-                  pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped));
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse(a, block_lists, block_lists_bytes);
+  pv_skip(a, pv_thresh, skipped);
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_pvskip(const sage_tensor* q8, const sage_tensor* k8,
@@ -482,9 +477,14 @@ extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_pvskip(const sage_tensor* q8,
                                                           float sm_scale, int logit_mult_is_one, const int32_t* block_lists,
                                                           int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                           sage_stream_t stream) {
-  return run_attn(q8, k8, v_fp8, true, SAGE_F16, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, stream,
-                  pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped));
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse(a, block_lists, block_lists_bytes);
+  pv_skip(a, pv_thresh, skipped);
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f16_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
@@ -495,12 +495,14 @@ extern "C" int sage_attn_fusedq_pv_f16_blocksparse_pvskip(const sage_tensor* q, 
                                                           float sm_scale, const int32_t* block_lists,
                                                           int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                           sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt = pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped);
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v, false, v_dtype, o, o_dtype, nullptr, k_scale, nullptr, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
-                  qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse(a, block_lists, block_lists_bytes);
+  pv_skip(a, pv_thresh, skipped);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }
 
 extern "C" int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
@@ -511,10 +513,12 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, i
                                                          float sm_scale, const int32_t* block_lists,
                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                          sage_stream_t stream) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnOptions opt = pvskip_options(block_lists, block_lists_bytes, pv_thresh, skipped);
-  opt.q_dtype = q_dtype;
-  opt.km = km;
-  return run_attn(q, k8, v_fp8, true, SAGE_F16, o, o_dtype, nullptr, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
-                  is_causal, qk_gran, 128, warpq, sm_scale, 0, stream, opt);
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse(a, block_lists, block_lists_bytes);
+  pv_skip(a, pv_thresh, skipped);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
 }

@@ -44,7 +44,7 @@ struct AttnParams {
   int64_t msm, msn;
   union { int mask_kind; int bs_row; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
-  // (b, h_kv) in k8 and in v (always set by run_attn; the dense defaults are 64 rows), and the strides of k_scale
+  // (b, h_kv) in k8 and in v (always set by attn_check; the dense defaults are 64 rows), and the strides of k_scale
   // (floats) per batch, kv head and 64-key tile.  Sequence-parallel exchange buffers are tile-major: tile j of every
   // (b, h) is a contiguous block and the tiles of all ranks form one sequence.
   int k_tile_bytes, v_tile_bytes;
@@ -56,6 +56,10 @@ struct AttnParams {
 
 // K/V slots of the LDS tile ring (see the kernel): 4 for the FP8-PV loop where every wave copies a full share of each tile
 constexpr int attn_ring_slots(int D, int nwaves, bool pv_fp8) { return (pv_fp8 && nwaves * 64 <= 4 * D) ? 4 : 2; }
+// dynamic LDS of a launch in bytes: ring slots x (K tile + V tile); a tile is 64 keys of int8 K and of fp8 or 16-bit V
+constexpr size_t attn_lds_bytes(int D, int nwaves, bool pv_fp8) {
+  return (size_t)attn_ring_slots(D, nwaves, pv_fp8) * (64 * D + (pv_fp8 ? 64 * D : 64 * D * 2));
+}
 
 // dynamic LDS above the 48 KiB default needs the function attribute; its status is part of the launch status
 __host__ inline bool allow_lds(const void* kern, size_t bytes) {

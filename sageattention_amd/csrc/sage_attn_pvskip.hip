@@ -12,7 +12,7 @@
 // registers, i.e. two waves per SIMD at head_dim 64 and scratch at head_dim 128.  With the option the branch stays a
 // scalar branch and every variant needs no more registers than its twin without the skip.  Regions with a divergent
 // branch are structurized as before.
-#include "sage_entry.h"
+#include "sage_attn_launch.h"
 
 namespace sage {
 
@@ -29,26 +29,10 @@ void attn_i8_blocksparse_pvskip_kernel(const AttnParams p) {
 #undef SAGE_ATTN_BODY_OF_KERNEL
 }
 
-template <int D>
-static int launch_pvskip(const AttnCall& c, hipStream_t st) {
-  const AttnParams& p = c.p;
-  return by_flag(c.pv_fp8, [&](auto fp8) {
-    constexpr bool PV_FP8 = decltype(fp8)::value;
-    const size_t smem = (size_t)attn_ring_slots(D, 4, PV_FP8) * (64 * D + (PV_FP8 ? 64 * D : 64 * D * 2));
-    return by_flag(c.kthread, [&](auto k) {
-      return by_flag(!PV_FP8 && c.v_bf16, [&](auto v) {
-        constexpr bool V_BF16 = !PV_FP8 && decltype(v)::value;
-        auto kern = attn_i8_blocksparse_pvskip_kernel<D, decltype(k)::value, V_BF16, PV_FP8>;
-        if (!allow_lds((const void*)kern, smem)) return (int)SAGE_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(p.nqb * p.Hq * p.B), dim3(256), smem, st, p);
-        return launch_status();
-      });
-    });
-  });
-}
-
 int launch_blocksparse_pvskip(const AttnCall& c, hipStream_t st) {
-  return by_dim(c.D, [&](auto d) { return launch_pvskip<decltype(d)::value>(c, st); });
+  return launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
+    return attn_i8_blocksparse_pvskip_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
+  });
 }
 
 }  // namespace sage

@@ -94,11 +94,19 @@ int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, 
 int kv_prepare_launch(const KVPrepCall& c, hipStream_t st);
 
 // ---- attention (sage_attn.hip) ----------------------------------------------------------------------------------------
-// the inputs of attn_check that only some entry points have
-struct AttnOptions {
-  const int* cu_q = nullptr;  // packed sequences: cumulative query / key lengths
-  const int* cu_k = nullptr;
-  int q_dtype = -1;           // >= 0: q8 is the fp16 / bf16 query tensor, quantized in the kernel's prologue
+// the arguments of an attention entry point: each one names the fields it has and leaves the others at these defaults
+struct AttnArgs {
+  const sage_tensor *q = nullptr, *k8 = nullptr, *v = nullptr, *o = nullptr;  // q: INT8, or with q_dtype >= 0 fp16 / bf16
+  bool pv_fp8 = false;                                                        // v is the FP8 V^T, else fp16 / bf16 (v_dtype)
+  int v_dtype = SAGE_F16, o_dtype = SAGE_F16;
+  const float *q_scale = nullptr, *k_scale = nullptr, *v_scale = nullptr, *v_mean = nullptr;
+  float* lse = nullptr;
+  int B = 0, Hq = 0, Hk = 0, M = 0, N = 0, D = 0;
+  int is_causal = 0, qk_gran = 0, blkq = 0, warpq = 0;
+  float sm_scale = 0.f;
+  int logit_mult_is_one = 0;
+  const int *cu_q = nullptr, *cu_k = nullptr;  // packed sequences: cumulative query / key lengths
+  int q_dtype = -1;           // >= 0: q is the fp16 / bf16 query tensor, quantized in the kernel's prologue
   const void* km = nullptr;   // fused Q: k_mean of the LSE correction
   const void* mask = nullptr; // attn_mask, its kind and its four strides
   int mask_kind = 0;
@@ -121,10 +129,7 @@ struct AttnCall {
   bool sparse;  // attn_i8_blocksparse_kernel (always 4 waves)
   bool pvskip;  // ... its twin attn_i8_blocksparse_pvskip_kernel
 };
-int attn_check(AttnCall& c, const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, bool pv_fp8, int v_dtype,
-               const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale,
-               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
-               int blkq, int warpq, float sm_scale, int logit_mult_is_one, const AttnOptions& opt = AttnOptions());
+int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
 // the attention launch of a block-sparse call with the P.V skip (c.pvskip; sage_attn_pvskip.hip): attn_launch goes through it
 int launch_blocksparse_pvskip(const AttnCall& c, hipStream_t st);

@@ -18,7 +18,9 @@ struct Plan {
   int gk, gq, npad;
 };
 
-bool make_plan(Plan& pl, int pv_fp8, int B, int Hq, int Hk, int M, int N, int D, int want_lse, const sage_op_opts* o) {
+// `a`: pv_fp8 and the shape
+bool make_plan(Plan& pl, const sage::AttnArgs& a, bool want_lse, const sage_op_opts* o) {
+  const int B = a.B, Hq = a.Hq, Hk = a.Hk, M = a.M, N = a.N, D = a.D;
   if (B <= 0 || Hq <= 0 || Hk <= 0 || M <= 0 || N <= 0 || (D != 64 && D != 128) || !o) return false;
   const int gran = o->qk_gran, warpq = o->warpq ? o->warpq : 32;
   if (gran != SAGE_GRAN_PER_WARP && gran != SAGE_GRAN_PER_THREAD) return false;
@@ -33,10 +35,10 @@ bool make_plan(Plan& pl, int pv_fp8, int B, int Hq, int Hk, int M, int N, int D,
   pl.k8 = take((size_t)B * Hk * N * D);
   pl.ks = take((size_t)B * Hk * pl.gk * 4);
   pl.km = take((size_t)B * Hk * D * 2);
-  const size_t pre = pv_fp8 ? sage_kv_prepare_fp8_workspace_bytes(B, Hk, N, D) : sage_k_mean_workspace_bytes(B, Hk, N, D);
+  const size_t pre = a.pv_fp8 ? sage_kv_prepare_fp8_workspace_bytes(B, Hk, N, D) : sage_k_mean_workspace_bytes(B, Hk, N, D);
   pl.pre_ws = take(pre > 4 ? pre : 4);
   pl.v8 = pl.v_scale = 0;
-  if (pv_fp8) {
+  if (a.pv_fp8) {
     pl.v8 = take((size_t)B * Hk * D * pl.npad);
     pl.v_scale = take((size_t)B * Hk * D * 4);
   }
@@ -53,16 +55,20 @@ bool make_plan(Plan& pl, int pv_fp8, int B, int Hq, int Hk, int M, int N, int D,
   return true;
 }
 
-int run(int pv_fp8, const sage_tensor* q, const sage_tensor* k, const sage_tensor* v, int dtype, const sage_tensor* o, float* lse,
-        int B, int Hq, int Hk, int M, int N, int D, int is_causal, float sm_scale, float scale_max, const sage_op_opts* opts,
-        void* workspace, size_t workspace_bytes, sage_stream_t stream) {
-  if (!q || !k || !v || !o || !opts || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
+// `aa` arrives with what the caller gave -- q, v and o in `dtype`, pv_fp8, lse, the shape, is_causal, sm_scale -- and leaves as
+// the arguments of the attention step
+int run(sage::AttnArgs aa, const sage_tensor* k, int dtype, float scale_max, const sage_op_opts* opts, void* workspace,
+        size_t workspace_bytes, sage_stream_t stream) {
+  const sage_tensor *const q = aa.q, *const v = aa.v;
+  float* const lse = aa.lse;
+  const int pv_fp8 = aa.pv_fp8, B = aa.B, Hq = aa.Hq, Hk = aa.Hk, M = aa.M, N = aa.N, D = aa.D;
+  if (!q || !k || !v || !aa.o || !opts || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
   if (const int s = sage::dim_dtype_status(D, dtype)) return s;
   if (Hk <= 0 || Hq % Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (!opts->smooth_k) return SAGE_ERR_UNSUPPORTED;  // the un-smoothed variant goes through the separate entry points
   if (opts->nwaves != 0 && opts->nwaves != 4 && opts->nwaves != 8) return SAGE_ERR_INVALID_ARGUMENT;
   Plan pl;
-  if (!make_plan(pl, pv_fp8, B, Hq, Hk, M, N, D, lse != nullptr, opts)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!make_plan(pl, aa, lse != nullptr, opts)) return SAGE_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < pl.total || !sage::aligned16(workspace)) return SAGE_ERR_INVALID_ARGUMENT;
   char* const ws = static_cast<char*>(workspace);
   const int gran = opts->qk_gran, warpq = opts->warpq ? opts->warpq : 32;
@@ -88,27 +94,26 @@ int run(int pv_fp8, const sage_tensor* q, const sage_tensor* k, const sage_tenso
     st = sage::k_smooth_quant_check(kc, k, dtype, B, Hk, N, D, &k8, ks, km, k_gran, rounding, ws + pl.pre_ws);
   }
   if (st != SAGE_OK) return st;
-  sage::AttnOptions ao;
-  ao.nwaves = opts->nwaves;
+  // the attention step reads the pre-pass results; Q: the fp16 / bf16 tensor (fused), or q8 and its scales
+  aa.k8 = &k8; aa.k_scale = ks; aa.v_scale = v_scale; aa.v_dtype = pv_fp8 ? SAGE_F16 : dtype; aa.o_dtype = dtype;
+  if (pv_fp8) aa.v = &v8;
+  aa.qk_gran = gran; aa.blkq = 128; aa.warpq = warpq; aa.nwaves = opts->nwaves;
   sage::AttnCall ac;
   sage::QuantCall qc;
   sage::FinishLseCall fc;
+  const sage_tensor q8{ws + pl.q8, (int64_t)Hq * M * D, (int64_t)M * D, D};
   if (pl.fuse_q) {
-    ao.q_dtype = dtype;
-    ao.km = km;
-    st = sage::attn_check(ac, q, &k8, pv_fp8 ? &v8 : v, pv_fp8, pv_fp8 ? SAGE_F16 : dtype, o, dtype, nullptr, ks, v_scale, nullptr,
-                          lse, B, Hq, Hk, M, N, D, is_causal, gran, 128, warpq, sm_scale, 0, ao);
+    aa.q_dtype = dtype; aa.km = km;
+    st = sage::attn_check(ac, aa);
   } else {
-    const sage_tensor q8{ws + pl.q8, (int64_t)Hq * M * D, (int64_t)M * D, D};
     float* const qs = reinterpret_cast<float*>(ws + pl.qs);
     float* const corr = lse ? reinterpret_cast<float*>(ws + pl.corr) : nullptr;
     float* const lse2 = lse ? reinterpret_cast<float*>(ws + pl.lse2) : nullptr;
     st = sage::quant_check(qc, q, dtype, B, Hq, M, D, nullptr, &q8, qs, gran, 0, 128, warpq, 1.0f, rounding, lse ? km : nullptr,
                            Hq / Hk, corr);
-    if (st == SAGE_OK)
-      st = sage::attn_check(ac, &q8, &k8, pv_fp8 ? &v8 : v, pv_fp8, pv_fp8 ? SAGE_F16 : dtype, o, dtype, qs, ks, v_scale, nullptr,
-                            lse2, B, Hq, Hk, M, N, D, is_causal, gran, 128, warpq, sm_scale, 0, ao);
-    if (st == SAGE_OK && lse) st = sage::finish_lse_check(fc, lse2, corr, sm_scale, lse, (int64_t)B * Hq * M);
+    aa.q = &q8; aa.q_scale = qs; aa.lse = lse2;
+    if (st == SAGE_OK) st = sage::attn_check(ac, aa);
+    if (st == SAGE_OK && lse) st = sage::finish_lse_check(fc, lse2, corr, aa.sm_scale, lse, (int64_t)B * Hq * M);
   }
   if (st != SAGE_OK) return st;
   const hipStream_t s = (hipStream_t)stream;
@@ -123,15 +128,20 @@ int run(int pv_fp8, const sage_tensor* q, const sage_tensor* k, const sage_tenso
 
 extern "C" size_t sage_sageattn_workspace_bytes(int pv_fp8, int B, int Hq, int Hk, int M, int N, int D, int want_lse,
                                                 const sage_op_opts* opts) {
+  sage::AttnArgs a;
+  a.pv_fp8 = pv_fp8 != 0; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
   Plan pl;
-  return make_plan(pl, pv_fp8, B, Hq, Hk, M, N, D, want_lse, opts) ? pl.total : 0;
+  return make_plan(pl, a, want_lse != 0, opts) ? pl.total : 0;
 }
 
 extern "C" int sage_sageattn_pv_f16(const sage_tensor* q, const sage_tensor* k, const sage_tensor* v, int dtype,
                                     const sage_tensor* o, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
                                     float sm_scale, const sage_op_opts* opts, void* workspace, size_t workspace_bytes,
                                     sage_stream_t stream) {
-  return run(0, q, k, v, dtype, o, lse, B, Hq, Hk, M, N, D, is_causal, sm_scale, 0.f, opts, workspace, workspace_bytes, stream);
+  sage::AttnArgs a;
+  a.q = q; a.v = v; a.o = o; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.sm_scale = sm_scale;
+  return run(a, k, dtype, 0.f, opts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sage_sageattn_pv_f8(const sage_tensor* q, const sage_tensor* k, const sage_tensor* v, int dtype,
@@ -139,5 +149,8 @@ extern "C" int sage_sageattn_pv_f8(const sage_tensor* q, const sage_tensor* k, c
                                    float sm_scale, float scale_max, const sage_op_opts* opts, void* workspace,
                                    size_t workspace_bytes, sage_stream_t stream) {
   if (!(scale_max > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
-  return run(1, q, k, v, dtype, o, lse, B, Hq, Hk, M, N, D, is_causal, sm_scale, scale_max, opts, workspace, workspace_bytes, stream);
+  sage::AttnArgs a;
+  a.q = q; a.v = v; a.pv_fp8 = true; a.o = o; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.sm_scale = sm_scale;
+  return run(a, k, dtype, scale_max, opts, workspace, workspace_bytes, stream);
 }

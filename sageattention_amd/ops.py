@@ -36,6 +36,34 @@ def _entry(pv: str):
     raise ValueError(f"Unknown pv: {pv}")
 
 
+def _bhm(q, tensor_layout):
+    """(B, Hq, M) of q in either layout"""
+    return (q.shape[0], q.shape[1], q.shape[2]) if tensor_layout == "HND" else (q.shape[0], q.shape[2], q.shape[1])
+
+
+def _lse_like(q, tensor_layout):
+    return q.new_empty(_bhm(q, tensor_layout), dtype=torch.float32)
+
+
+def _skipped_like(q, tensor_layout):
+    """the skip counters of a call on q: int32 [B, Hq, ceil(M/128), 4]"""
+    B, H, M = _bhm(q, tensor_layout)
+    return q.new_empty((B, H, (M + 127) // 128, 4), dtype=torch.int32)
+
+
+def _as_per_head(value, q, tensor_layout):
+    """a per-head parameter as the fp32 [Hq] tensor the ops take: a float is broadcast, a tensor passed on"""
+    if isinstance(value, torch.Tensor):
+        return value
+    return torch.full((_bhm(q, tensor_layout)[1],), float(value), dtype=torch.float32, device=q.device)
+
+
+def _plan_args(plan):
+    """a plan as it travels through an op: its lists and the (B, Hq, M, N) it was compacted for, which the operator checks
+    against the call"""
+    return plan.lists, [plan.B, plan.Hq, plan.M, plan.N]
+
+
 @torch.library.custom_op("sageattention_amd::attn", mutates_args=())
 def attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str, is_causal: bool, sm_scale: float,
          pv: str, qk_quant_gran: str) -> torch.Tensor:
@@ -60,11 +88,7 @@ def attn_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: s
 
 @attn_lse.register_fake
 def _(q, k, v, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran):
-    if tensor_layout == "HND":
-        B, H, M = q.shape[0], q.shape[1], q.shape[2]
-    else:
-        B, M, H = q.shape[0], q.shape[1], q.shape[2]
-    return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
 
 
 @torch.library.custom_op("sageattention_amd::attn_block_sparse", mutates_args=())
@@ -83,7 +107,6 @@ def _(q, k, v, block_map, tensor_layout, sm_scale, pv, qk_quant_gran):
 def attn_block_sparse_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_lists: torch.Tensor,
                            plan_shape: Sequence[int], tensor_layout: str, sm_scale: float, pv: str,
                            qk_quant_gran: str) -> torch.Tensor:
-    # a plan travels as its lists and the (B, Hq, M, N) it was compacted for, which the operator checks against the call
     plan = core.BlockSparsePlan(block_lists, *(int(x) for x in plan_shape))
     return core.sageattn_block_sparse(q, k, v, plan, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
                                       qk_quant_gran=qk_quant_gran).contiguous()
@@ -92,17 +115,6 @@ def attn_block_sparse_plan(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
 @attn_block_sparse_plan.register_fake
 def _(q, k, v, block_lists, plan_shape, tensor_layout, sm_scale, pv, qk_quant_gran):
     return q.new_empty(q.shape)
-
-
-def _skipped_like(q, tensor_layout):
-    """the skip counters of a call on q: int32 [B, Hq, ceil(M/128), 4]"""
-    B, H, M = (q.shape[0], q.shape[1], q.shape[2]) if tensor_layout == "HND" else (q.shape[0], q.shape[2], q.shape[1])
-    return q.new_empty((B, H, (M + 127) // 128, 4), dtype=torch.int32)
-
-
-def _lse_like(q, tensor_layout):
-    B, H, M = (q.shape[0], q.shape[1], q.shape[2]) if tensor_layout == "HND" else (q.shape[0], q.shape[2], q.shape[1])
-    return q.new_empty((B, H, M), dtype=torch.float32)
 
 
 # ... with the P.V skip (core.sageattn_block_sparse, pvthreshd): ops of their own, so that the schemas above stay as they
@@ -146,22 +158,18 @@ def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.
     core._check_pvskip_args(pvthreshd, return_skipped)
     if sm_scale is None:
         sm_scale = q.size(-1) ** -0.5
+    ns, tail = torch.ops.sageattention_amd, (tensor_layout, float(sm_scale), pv, qk_quant_gran)
+    is_plan = isinstance(block_map, core.BlockSparsePlan)
     if pvthreshd is not None:
         thr = _as_per_head(pvthreshd, q, tensor_layout)
-        if isinstance(block_map, core.BlockSparsePlan):
-            p = block_map
-            o, skipped = torch.ops.sageattention_amd.attn_block_sparse_plan_pv(
-                q, k, v, p.lists, [p.B, p.Hq, p.M, p.N], thr, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+        if is_plan:
+            o, skipped = ns.attn_block_sparse_plan_pv(q, k, v, *_plan_args(block_map), thr, *tail)
         else:
-            o, skipped = torch.ops.sageattention_amd.attn_block_sparse_pv(q, k, v, block_map, thr, tensor_layout,
-                                                                          float(sm_scale), pv, qk_quant_gran)
+            o, skipped = ns.attn_block_sparse_pv(q, k, v, block_map, thr, *tail)
         return (o, skipped) if return_skipped else o
-    if isinstance(block_map, core.BlockSparsePlan):
-        p = block_map
-        return torch.ops.sageattention_amd.attn_block_sparse_plan(q, k, v, p.lists, [p.B, p.Hq, p.M, p.N], tensor_layout,
-                                                                  float(sm_scale), pv, qk_quant_gran)
-    return torch.ops.sageattention_amd.attn_block_sparse(q, k, v, block_map, tensor_layout, float(sm_scale), pv,
-                                                         qk_quant_gran)
+    if is_plan:
+        return ns.attn_block_sparse_plan(q, k, v, *_plan_args(block_map), *tail)
+    return ns.attn_block_sparse(q, k, v, block_map, *tail)
 
 
 @torch.library.custom_op("sageattention_amd::attn_sparge", mutates_args=())
@@ -187,19 +195,7 @@ def attn_sparge_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthresh
 
 @attn_sparge_lse.register_fake
 def _(q, k, v, simthreshd1, cdfthreshd, tensor_layout, sm_scale, pv, qk_quant_gran):
-    if tensor_layout == "HND":
-        B, H, M = q.shape[0], q.shape[1], q.shape[2]
-    else:
-        B, M, H = q.shape[0], q.shape[1], q.shape[2]
-    return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
-
-
-def _as_per_head(value, q, tensor_layout):
-    """a per-head parameter as the fp32 [Hq] tensor the ops take: a float is broadcast, a tensor passed on"""
-    if isinstance(value, torch.Tensor):
-        return value
-    Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
-    return torch.full((Hq,), float(value), dtype=torch.float32, device=q.device)
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
 
 
 def _select_kwargs(rule_param: torch.Tensor, rule: str):
@@ -235,11 +231,7 @@ def attn_sparge_select_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, si
 
 @attn_sparge_select_lse.register_fake
 def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, tensor_layout, sm_scale, pv, qk_quant_gran):
-    if tensor_layout == "HND":
-        B, H, M = q.shape[0], q.shape[1], q.shape[2]
-    else:
-        B, M, H = q.shape[0], q.shape[1], q.shape[2]
-    return q.new_empty(q.shape), q.new_empty((B, H, M), dtype=torch.float32)
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
 
 
 @torch.library.custom_op("sageattention_amd::attn_sparge_pv", mutates_args=())
@@ -289,10 +281,8 @@ def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     core._check_pvskip_args(pvthreshd, return_skipped)
     if sm_scale is None:
         sm_scale = q.size(-1) ** -0.5
-    Hq = q.size(1) if tensor_layout == "HND" else q.size(2)
     rule, par = ("cdf", cdfthreshd) if topk is None else ("topk", topk)
-    thr, par = (t if isinstance(t, torch.Tensor) else torch.full((Hq,), float(t), dtype=torch.float32, device=q.device)
-                for t in (simthreshd1, par))
+    thr, par = _as_per_head(simthreshd1, q, tensor_layout), _as_per_head(par, q, tensor_layout)
     if pvthreshd is not None:
         pvt = _as_per_head(pvthreshd, q, tensor_layout)
         op = torch.ops.sageattention_amd.attn_sparge_pv_lse if return_lse else torch.ops.sageattention_amd.attn_sparge_pv

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""End-to-end operator time by workgroup geometry (4 or 8 waves) -- the kernel-only crossover of sage_attn.hip::run_attn was
+"""End-to-end operator time by workgroup geometry (4 or 8 waves) -- the kernel-only crossover of sage_attn.hip::attn_check was
 measured on pre-quantized operands; with the Q quantizer folded into the prologue the prologue weighs more."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -126,7 +126,7 @@ for sname in a.shapes.split(","):
         quant.k_mean(k)
 
     def predict(cdf=0.98, topk=None):
-        return core._sparge_predict(q, k, km, "HND", a.simthreshd1, cdf, D ** -0.5, False, topk)[0]
+        return core._sparge_predict(q, k, km, "HND", D ** -0.5, False, (a.simthreshd1, cdf, topk, 0, 0))[0]
 
     if a.mode == "kernels":
         for _ in range(20):
