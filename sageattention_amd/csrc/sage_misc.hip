@@ -91,9 +91,15 @@ __global__ __launch_bounds__(256) void finish_lse_kernel(const float* __restrict
                                                          float sm_scale, float* __restrict__ out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  float v = lse2[i] / 1.44269504f;  // core.py:651
-  if (corr) v += corr[i] * sm_scale;
-  out[i] = v;
+  // product and sum rounded separately, as torch evaluates core.py:651 and as the fused-Q epilogue of the attention kernel
+  // does (sage_attn.hip is built with -ffp-contract=off): contracted to an fma, this kernel and that epilogue differed in the
+  // last bit whenever sm_scale is not a power of two (head_dim 128), although both are documented as bit-identical
+  {
+#pragma clang fp contract(off)
+    float v = lse2[i] / 1.44269504f;  // core.py:651
+    if (corr) v += corr[i] * sm_scale;
+    out[i] = v;
+  }
 }
 
 // Block map -> per-(b, h, q-block) lists of active 64-key tiles (the operand of the block-sparse attention kernels).  One
