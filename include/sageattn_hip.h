@@ -544,6 +544,39 @@ int sage_block_select(const float* pooled_q, const float* sim_q, const float* po
                       int keep_first, int keep_last, int32_t* block_lists, int64_t block_lists_bytes,
                       uint8_t* block_map, sage_stream_t stream);
 
+/* ==== calibration of the predictor (new: what a block map loses, measured on the operands of the attention kernels; the
+ * instrument behind a threshold search such as SpargeAttn's tuning mode.  The reference has no counterpart.) ====
+ *
+ * Exact tile mass.  For b, query head h, q-block i (rows [128 i, 128 i + 128), of which c_i = min(128, M - 128 i) are valid)
+ * and key tile j (keys [64 j, 64 j + 64), only keys < N):
+ *   mass[b,h,i,j] = (1 / c_i) * sum over the valid rows r of the q-block, sum over the keys n of the tile, of P[r, n]
+ * where P[r, :] is the softmax over ALL keys < N of the logits the attention kernels exponentiate,
+ *   S[r,n] * q_scale(r) * k_scale(n) * logit_mult,   S = q8 . k8 in int32,
+ * logit_mult as logit_mult_is_one / sm_scale of sage_attn_qk_int8_pv_f16 select it, the scales indexed as that call indexes
+ * them for SAGE_GRAN_PER_WARP and SAGE_GRAN_PER_THREAD (blkk = warpk = 64).  Non-causal, no mask.  mass is fp32
+ * [B,Hq,ceil(M/128),ceil(N/64)] contiguous, 4-byte aligned; every entry is written by every call, each mass[b,h,i,:] sums
+ * to 1 up to rounding, and rows >= M contribute nothing.  Deterministic: no atomics, two calls give the same bits.
+ * q8, k8, q_scale, k_scale, B .. logit_mult_is_one: as for sage_attn_qk_int8_pv_f16 (D in {64,128}, Hq a multiple of Hk, any
+ * M, N >= 1, any strides that call takes).  Checked before the launch: a null or misaligned pointer (k_scale: 16 bytes for
+ * SAGE_GRAN_PER_THREAD) and inconsistent sizes SAGE_ERR_INVALID_ARGUMENT, another head_dim SAGE_ERR_UNSUPPORTED_HEAD_DIM,
+ * SAGE_GRAN_PER_BLOCK SAGE_ERR_UNSUPPORTED (the block-sparse operators do not take it either).  Q and K are addressed with
+ * 64-bit offsets, so there is no 2 GiB slice window and no SAGE_ERR_TOO_LARGE short of 2^31 q-blocks.
+ * Two passes over the key tiles (row maximum and row sum; then the probabilities), QK^T only: twice the MFMA work of
+ * the dense call's QK^T, two exponentials per score, no P.V. */
+int sage_attn_tile_mass(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale, const float* k_scale,
+                        int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
+                        float sm_scale, int logit_mult_is_one, float* mass, sage_stream_t stream);
+
+/* Recall of a plan: per list row (b, h_q, q-block i) of block_lists (as sage_block_map_compact / sage_block_select write them
+ * for the same B, Hq, M, N)
+ *   recall[b,h,i] = sum of mass[b,h,i,j] over the listed tiles j,   kept[b,h,i] = the row's count;
+ * an empty row gives 0 and 0.  recall fp32 and kept int32 [B,Hq,ceil(M/128)] contiguous, 4-byte aligned.  One wave per list
+ * row; the sum runs in tile slots (lane j % 64 adds its listed tiles in ascending order, then one fixed tree over the lanes),
+ * so it is deterministic and a list that keeps a superset of tiles never gets a smaller recall, in fp32 too (mass >= 0).
+ * The lists are trusted as by the attention kernels.  Argument checks as sage_block_map_compact. */
+int sage_block_plan_recall(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq, int M,
+                           int N, float* recall, int32_t* kept, sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ SOURCES = [
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
     ("sage_sparge.hip", []),
+    # calibration of the predictor: exact tile mass (QK^T only, plain loads: no lds_dma16, so no M0 check) and plan recall
+    ("sage_calib.hip", []),
 ]
 # -Wno-inline-asm: lds_dma16 names M0 in its clobber list, which clang reports as "reserved register" (see the function)
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",

@@ -138,6 +138,11 @@ SIGNATURES = {
     # ... with (rule, rule_param, keep_first, keep_last) in the place of cdfthreshd
     "sage_block_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    # the Q / K arguments of sage_attn_qk_int8_pv_f16, then mass
+    "sage_attn_tile_mass": (c_int, [_P, _P, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_float, c_int, c_void_p, c_void_p]),
+    "sage_block_plan_recall": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p]),
 }
 
 

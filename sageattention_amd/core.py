@@ -21,7 +21,8 @@ from .quant import _quant, block_pool_sim, k_mean, k_smooth_quant, kv_prepare_fp
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
-           "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan"]
+           "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan",
+           "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning"]
 
 
 def _common_checks(q, k, v):
@@ -763,3 +764,177 @@ def sageattn_sparge(
         return _sparge_predict(q, k, km, tensor_layout, sm_scale, False, select)[0]
     return _block_sparse_tail(q, k, v, tensor_layout, sm_scale, (pv, qk_quant_gran, True), plan_from,
                               (return_lse, return_plan, pvthreshd, return_skipped))
+
+
+# ---- calibration of the predictor ------------------------------------------------------------------------------------------------
+def _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale):
+    """sage_attn_tile_mass on the padded query view ``q`` and the K operands of ``_prep_k`` -> fp32 [B,Hq,nqb,ntk]"""
+    B, Hq, M, D = L.dims(q, tensor_layout)
+    _, Hk, N, _ = L.dims(k8, tensor_layout)
+    if Hq % Hk != 0:
+        raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
+    q8, qs, _ = _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, 32, False, Hq, Hk)
+    mass = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.float32, device=q.device)
+    L.check(L.lib().sage_attn_tile_mass(L.desc(q8, tensor_layout), L.desc(k8, tensor_layout), qs.data_ptr(), ks.data_ptr(),
+                                        B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], 128, 32, float(sm_scale), 0,
+                                        mass.data_ptr(), L.stream_ptr(q.device)), "sage_attn_tile_mass")
+    return mass
+
+
+def sageattn_tile_mass(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", sm_scale: Optional[float] = None,
+                       qk_quant_gran: str = "per_thread", smooth_k: bool = True):
+    """The exact softmax mass of every 128x64 tile of ``sageattn_block_sparse(q, k, ...)`` with the same ``qk_quant_gran`` and
+    ``smooth_k``: fp32 [B,Hq,ceil(M/128),ceil(N/64)], per q-block the probabilities of the dense operator summed over the
+    tile's keys and averaged over the block's valid rows (the definition: include/sageattn_hip.h, sage_attn_tile_mass).  It
+    is computed from the INT8 Q and K and the scales that operator multiplies -- same head-dim padding, K pre-pass and Q
+    quantizer -- so each row of the last axis sums to 1 and ``plan_recall`` of a map is the share of the probability that the
+    map keeps.  Costs about one dense attention call.  Non-causal."""
+    _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
+    assert q.is_cuda, "Input tensors must be on cuda."
+    assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
+    assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
+    with torch.cuda.device(q.device):
+        q, k, _, head_dim_og = _pad_head_dim(q, k, k)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
+        return _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale)
+
+
+def _plan_recall(plan, mass):
+    recall = torch.empty(mass.shape[:3], dtype=torch.float32, device=mass.device)
+    kept = torch.empty(mass.shape[:3], dtype=torch.int32, device=mass.device)
+    L.check(L.lib().sage_block_plan_recall(plan.lists.data_ptr(), plan.lists.numel() * 4, mass.data_ptr(), plan.B, plan.Hq,
+                                           plan.M, plan.N, recall.data_ptr(), kept.data_ptr(), L.stream_ptr(mass.device)),
+            "sage_block_plan_recall")
+    return recall, kept
+
+
+def plan_recall(plan_or_map, mass: torch.Tensor):
+    """What a plan keeps of ``mass`` (``sageattn_tile_mass``): (recall fp32 [B,Hq,nqb], kept int32 [B,Hq,nqb]) -- per q-block
+    the summed mass of its active tiles and their number (sage_block_plan_recall: deterministic, and never smaller for a
+    superset of tiles).  ``plan_or_map`` is a ``BlockSparsePlan`` or a bool / uint8 map [B|1, Hq|1, nqb, ntk], which is
+    compacted with ``block_sparse_plan`` first.  An empty q-block has recall 0."""
+    if not isinstance(mass, torch.Tensor) or mass.dim() != 4 or mass.dtype != torch.float32:
+        raise ValueError("mass must be the fp32 [B,Hq,ceil(M/128),ceil(N/64)] tensor of sageattn_tile_mass")
+    B, Hq, nqb, ntk = mass.shape
+    if isinstance(plan_or_map, BlockSparsePlan):
+        plan = plan_or_map
+        if (plan.B, plan.Hq, (plan.M + 127) // 128, (plan.N + 63) // 64) != (B, Hq, nqb, ntk):
+            raise ValueError(f"the plan was made for (B, Hq, M, N) = {(plan.B, plan.Hq, plan.M, plan.N)}, mass has the shape "
+                             f"{tuple(mass.shape)}")
+        if plan.lists.dtype != torch.int32 or plan.lists.numel() != _plan_ints(plan.B, plan.Hq, plan.M, plan.N):
+            raise ValueError("the plan's lists must be as block_sparse_plan makes them")
+    else:
+        if not isinstance(plan_or_map, torch.Tensor):
+            raise TypeError("plan_or_map must be a BlockSparsePlan or a bool/uint8 block map")
+        if plan_or_map.dim() != 4 or tuple(plan_or_map.shape[2:]) != (nqb, ntk):
+            raise ValueError(f"block map shape {tuple(plan_or_map.shape)} does not match the mass {tuple(mass.shape)}")
+        plan = block_sparse_plan(plan_or_map, nqb * 128, ntk * 64, B, Hq)  # whole blocks: the lists depend on the counts only
+    if plan.lists.device != mass.device:
+        raise ValueError(f"the plan is on {plan.lists.device}, mass on {mass.device}")
+    with torch.cuda.device(mass.device):
+        return _plan_recall(plan, mass.contiguous())
+
+
+class SpargeTuning:
+    """The result of ``sparge_tune``; every tensor has shape [Hq] and lives on the device.
+    ``rule`` "cdf" | "topk";  ``param`` fp32, the tuned ``cdfthreshd`` / ``topk`` -- pass it to ``sageattn_sparge`` as it is;
+    ``met`` bool, False where even 1.0 misses the target (``param`` is then 1.0);  ``recall`` the head recall at ``param``;
+    ``recall_below`` that at ``param - 2^-steps`` (-inf where that is 0);  ``density`` kept tiles over all tiles at ``param``."""
+    __slots__ = ("rule", "param", "met", "recall", "recall_below", "density")
+
+    def __init__(self, rule, param, met, recall, recall_below, density):
+        self.rule, self.param, self.met = rule, param, met
+        self.recall, self.recall_below, self.density = recall, recall_below, density
+
+    def __repr__(self):
+        return (f"SpargeTuning(rule={self.rule!r}, param={self.param}, met={self.met}, recall={self.recall}, "
+                f"recall_below={self.recall_below}, density={self.density})")
+
+
+def sparge_tune(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", target: float = 0.95, rule: str = "cdf",
+                simthreshd1=0.6, keep_first: int = 0, keep_last: int = 0, steps: int = 8, reduce: str = "mean",
+                sm_scale: Optional[float] = None, qk_quant_gran: str = "per_thread", mass: Optional[torch.Tensor] = None):
+    """Tune the predictor on data: per query head the smallest ``cdfthreshd`` (``rule="cdf"``) or ``topk`` (``rule="topk"``)
+    on the grid g / 2^steps, g = 1 .. 2^steps, at which the predicted map keeps at least ``target`` of the exact softmax mass
+    (``sageattn_tile_mass``; pass ``mass`` to reuse one).  The head recall is, with ``reduce="mean"``, the mean over batches
+    and q-blocks of ``plan_recall`` weighted by the blocks' valid rows -- the mean captured probability per query row --
+    and with ``"min"`` the minimum.  ``simthreshd1``, ``keep_first`` and ``keep_last`` are fixed inputs, as for
+    ``sparge_plan``.  Returns a ``SpargeTuning``.
+
+    Cost: Q and K are pooled once, the mass is computed once, and the search is one selection at 1.0 and then ``steps``
+    bisection steps, each one sage_block_select with the per-head candidates, one sage_block_plan_recall and a few
+    reductions on [Hq] tensors -- never a run of sparse attention.  Nothing is read back to the host: no synchronisation, and
+    the function captures into a HIP graph.
+
+    Why bisection finds the smallest grid value exactly: under both rules the tiles a q-block keeps at a larger parameter
+    are a superset of those at a smaller one -- either rule takes a prefix of one ranking of the candidates, and the tiles of
+    blocks that are not self-similar or are pinned on do not depend on the parameter.  sage_block_plan_recall adds the
+    non-negative mass in fixed tile slots and a fixed tree, so a superset never sums to less, and the reductions over batches
+    and q-blocks are fixed-order sums or minima of these.  Head recall is therefore monotone in the parameter, in fp32 as
+    well as in exact arithmetic, and the grid splits into a failing part below ``param`` and a passing part from it on."""
+    if rule not in ("cdf", "topk"):
+        raise ValueError(f"rule must be 'cdf' or 'topk', got {rule!r}")
+    if reduce not in ("mean", "min"):
+        raise ValueError(f"reduce must be 'mean' or 'min', got {reduce!r}")
+    if isinstance(target, bool) or not (0.0 < float(target) <= 1.0):
+        raise ValueError(f"target must lie in (0, 1], got {target!r}")
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= 16:
+        raise ValueError(f"steps must be an int in 1..16, got {steps!r}")
+    _check_select_args(None, keep_first, keep_last)
+    _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
+    assert q.is_cuda, "Input tensors must be on cuda."
+    assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
+    assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
+    dev = q.device
+    with torch.cuda.device(dev):
+        q, k, _, head_dim_og = _pad_head_dim(q, k, k)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        B, Hq, M, D = L.dims(q, tensor_layout)
+        _, Hk, N, _ = L.dims(k, tensor_layout)
+        if Hq % Hk != 0:
+            raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
+        nqb, ntk = (M + 127) // 128, (N + 63) // 64
+        if mass is None:
+            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
+            mass = _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale)
+        else:
+            if tuple(mass.shape) != (B, Hq, nqb, ntk) or mass.dtype != torch.float32 or mass.device != dev:
+                raise ValueError(f"mass must be an fp32 tensor of shape {(B, Hq, nqb, ntk)} on {dev}")
+            mass = mass.contiguous()
+            km = k_mean(k, tensor_layout)
+        thr = _per_head(simthreshd1, Hq, dev, "simthreshd1")
+        pq, sq = block_pool_sim(q, 128, tensor_layout)
+        pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
+        plan = BlockSparsePlan(torch.empty(_plan_ints(B, Hq, M, N), dtype=torch.int32, device=dev), B, Hq, M, N)
+        code = L.SELECT_CDF if rule == "cdf" else L.SELECT_TOPK
+        weight = (torch.arange(nqb, device=dev) * -128 + M).clamp(max=128).to(torch.float32).view(1, 1, nqb)  # c_i
+        unit = 2.0 ** -steps
+
+        def evaluate(par):
+            """-> (head recall, density) [Hq] of the selection with the per-head parameters ``par``"""
+            L.check(L.lib().sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
+                                              float(sm_scale), thr.data_ptr(), code, par.data_ptr(), min(keep_first, ntk),
+                                              min(keep_last, ntk), plan.lists.data_ptr(), plan.lists.numel() * 4, None,
+                                              L.stream_ptr(dev)), "sage_block_select")
+            rec, kept = _plan_recall(plan, mass)
+            if reduce == "mean":
+                head = (rec * weight).sum(dim=(0, 2)) / float(B * M)
+            else:
+                head = rec.amin(dim=(0, 2))
+            return head, kept.sum(dim=(0, 2)).to(torch.float32) / float(B * nqb * ntk)
+
+        hi = torch.full((Hq,), 1 << steps, dtype=torch.int32, device=dev)  # passes (or nothing does)
+        lo = torch.zeros_like(hi)                                          # fails: the empty parameter is never evaluated
+        r_hi, d_hi = evaluate(hi.to(torch.float32) * unit)
+        met = r_hi >= target
+        r_lo = torch.full_like(r_hi, float("-inf"))
+        for _ in range(steps):
+            mid = (lo + hi) // 2
+            r, d = evaluate(mid.to(torch.float32) * unit)
+            ok = r >= target
+            hi, r_hi, d_hi = torch.where(ok, mid, hi), torch.where(ok, r, r_hi), torch.where(ok, d, d_hi)
+            lo, r_lo = torch.where(ok, lo, mid), torch.where(ok, r_lo, r)
+        return SpargeTuning(rule, hi.to(torch.float32) * unit, met, r_hi, r_lo, d_hi)
