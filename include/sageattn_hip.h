@@ -482,6 +482,68 @@ int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, int q_dtype,
                                               const int32_t* block_lists, int64_t block_lists_bytes,
                                               const float* pv_thresh, int32_t* skipped, sage_stream_t stream);
 
+/* ==== per-batch key lengths on the dense padded layout (new: batches whose rows have different numbers of valid keys --
+ * cross-attention over padded prompts, joint video + text attention, batched prompt sets.  The reference's routes are an
+ * attn_mask, core.py:249-251, or repacking for sageattn_varlen, core.py:363-477) ====
+ * kv_lens: device, int32 [B], 4-byte aligned.  len_b = clamp(kv_lens[b], 0, N).  The rule:
+ *   - For every b with len_b > 0 the rows of batch b in o (and lse) are BIT-IDENTICAL to the twin without kv_lens called on
+ *     the slices q[b:b+1], k[b:b+1, :, :len_b], v[b:b+1, :, :len_b] with every other argument equal.  For the attention entry
+ *     points "k" and "v" are their quantized operands; the pre-pass twins below produce exactly those: km[b], the INT8 rows
+ *     < len_b with their scales, v_scale[b] and the V^T columns < len_b equal the results of the twin on the slice.
+ *   - Nothing in rows >= len_b of K or V influences any output: not their values, NaN and Inf included.  The pre-pass takes
+ *     every statistic (smoothing mean, block and per-thread scales, per-channel max|v|) over the rows < len_b only and never
+ *     loads the others; the attention kernels end their K / V buffer descriptors with row len_b - 1.
+ *   - is_causal is top-left aligned, as in the dense operator: query row i sees keys 0 .. min(i, len_b - 1).
+ *   - len_b == 0: o = 0, lse = -inf (the block-sparse convention), written by a second, tiny launch; the smoothing mean of
+ *     that batch is 0, not 0/0, so that the LSE correction of the fused-Q forms stays -inf.  Its scales and v_scale are
+ *     unspecified and never read.
+ *   - The lengths are read on the device only: no host synchronisation; a call captures into a HIP graph, and a replay
+ *     reads the lengths the buffer holds then.
+ * Grids, scale arrays ([B,H,ceil(N/64)(*4)]), the V^T row length (64*ceil(N/64)) and the workgroup geometry are those of N;
+ * the bits do not depend on the geometry.  Scales of blocks wholly beyond len_b, INT8 rows >= len_b and V^T columns
+ * >= 64*ceil(len_b/64) are unspecified and never read.
+ * Not built, SAGE_ERR_UNSUPPORTED from the argument check: kv_lens together with a block map, an attn_mask, cu_seqlens or a
+ * kv_layout (the entry points below have none of those arguments).  kv_lens NULL or misaligned: SAGE_ERR_INVALID_ARGUMENT.
+ * All checks run before any launch. */
+
+/* sage_k_smooth_quant with kv_lens: the mean of batch b is the sum over its rows < len_b, chunked as a call on len_b rows
+ * chunks them and added in the same order, divided by len_b.  The K quantizer treats rows >= len_b as absent for the block
+ * and per-thread scales.  km: 16-byte aligned.  workspace as sage_k_smooth_quant (for N rows).  Two launches. */
+int sage_k_smooth_quant_kvlen(const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
+                              float* scale, void* km, int gran, int rounding, void* workspace, const int32_t* kv_lens,
+                              sage_stream_t stream);
+/* sage_kv_prepare_fp8 with kv_lens: the K half as above; the per-channel max|v| of batch b over its rows < len_b only; the V^T
+ * image gets zero bytes in columns [len_b, 64*ceil(len_b/64)) (the attention kernel's descriptor covers the whole last tile,
+ * and an e4m3 NaN byte times P = 0 is NaN).  workspace as sage_kv_prepare_fp8 (for N rows).  Two launches. */
+int sage_kv_prepare_fp8_kvlen(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                              const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding,
+                              const sage_tensor* v_fp8, float* v_scale, float scale_max, void* workspace,
+                              const int32_t* kv_lens, sage_stream_t stream);
+
+/* sage_attn_qk_int8_pv_{f16,f8} and sage_attn_fusedq_pv_{f16,f8} with kv_lens: the arguments of the twin, then kv_lens.  The
+ * same pipelined loop, per-thread and per-warp scales, the fused Q quantizer, FP16 / BF16 / FP8 PV, LSE, GQA, both head dims
+ * and both workgroup geometries (SAGE_TUNE_NWAVES applies). */
+int sage_attn_qk_int8_pv_f16_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
+                                   const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale,
+                                   const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                   int is_causal, int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
+                                   const int32_t* kv_lens, sage_stream_t stream);
+int sage_attn_qk_int8_pv_f8_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                  const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale,
+                                  const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                  int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
+                                  int logit_mult_is_one, const int32_t* kv_lens, sage_stream_t stream);
+int sage_attn_fusedq_pv_f16_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                  int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                  const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                  int is_causal, int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens,
+                                  sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                 const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                 const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                 int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                 const int32_t* kv_lens, sage_stream_t stream);
+
 /* ==== block-map predictor (new: makes the tile lists above from Q and K at run time, after SpargeAttn's first stage --
  * pooled scores gated by the self-similarity of the blocks.  The reference has no counterpart; the rule below is this
  * library's own statement).  Non-causal.  All arithmetic is fp32; inputs are finite. ====

@@ -19,6 +19,8 @@ SOURCES = [
     # the block-sparse kernels with the P.V skip: the same body and flags, and the wave-uniform skip branch is left a
     # scalar if / else instead of being structurized (see the file: +40 registers otherwise)
     ("sage_attn_pvskip.hip", ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-structurizecfg-skip-uniform-regions"]),
+    # the dense kernels with per-batch key lengths: the same body and flags as sage_attn.hip
+    ("sage_attn_kvlen.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -59,6 +61,7 @@ def _check_occupancy(src, compiler_output):
         m = re.search(r" VGPRs: (\d+)", line)
         guarded = name and (re.search(r"attn_i8_kernelILi64ELi4E(Lb[01]E){4}Lb0EEE", name) or
                             re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name) or  # the block-sparse twins
+                            re.search(r"attn_i8_kvlen_kernelILi64ELi4E(Lb[01]E){4}EE", name) or     # ... with key lengths
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
                             re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name))
         if m and guarded and int(m.group(1)) > 168:
@@ -160,6 +163,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # s_sendmsg) would not be caught -- none of them occurs in code hipcc emits for these sources.
     _check_m0_private(os.path.join(CSRC, "sage_attn.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_pvskip.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_kvlen.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

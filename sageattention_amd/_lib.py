@@ -132,6 +132,23 @@ SIGNATURES = {
                                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                                           c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
                                                           c_void_p, c_void_p]),
+    # per-batch key lengths: the twins' arguments, then kv_lens in front of the stream
+    "sage_k_smooth_quant_kvlen": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p]),
+    "sage_kv_prepare_fp8_kvlen": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, _P,
+                                          c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "sage_attn_qk_int8_pv_f16_kvlen": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_float, c_int, c_void_p, c_void_p]),
+    "sage_attn_qk_int8_pv_f8_kvlen": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              c_float, c_int, c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f16_kvlen": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                              c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f8_kvlen": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                             c_void_p, c_void_p]),
     "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

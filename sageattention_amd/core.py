@@ -17,12 +17,13 @@ import torch
 
 from . import _lib as L
 from . import _qattn
-from .quant import _quant, block_pool_sim, k_mean, k_smooth_quant, kv_prepare_fp8, per_channel_fp8, sub_mean
+from .quant import (_quant, block_pool_sim, k_mean, k_smooth_quant, k_smooth_quant_kvlen, kv_prepare_fp8, kv_prepare_fp8_kvlen,
+                    per_channel_fp8, sub_mean)
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
            "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan",
-           "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning"]
+           "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen"]
 
 
 def _common_checks(q, k, v):
@@ -137,9 +138,16 @@ def _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, WARPQ, want_lse_corr
     return _quant(q, tensor_layout, gran, False, 128, WARPQ, 1.0, rnd, dot_vec=dot_vec, dot_group=Hq // Hk, dense_heads=True)
 
 
-def _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv_fp8, smooth_v):
+def _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv_fp8, smooth_v, kv_lens=None):
     """The K pre-pass of the multi-call operators, and for FP8 P.V the V pre-pass -> (k8, ks, km, v or v8, v_scale, vm).  ``km``
-    is None without ``smooth_k``, ``v_scale`` None for FP16 P.V (v is passed through), ``vm`` None without ``smooth_v``."""
+    is None without ``smooth_k``, ``v_scale`` None for FP16 P.V (v is passed through), ``vm`` None without ``smooth_v``.
+    With ``kv_lens`` (``sageattn_kvlen``: K smoothing on, no V smoothing, for FP8 P.V k and v of one shape) the length-aware
+    twins: every statistic over the rows < len_b of a batch only."""
+    if kv_lens is not None:
+        gran, rnd = _k_pairing(qk_quant_gran)
+        if pv_fp8:
+            return kv_prepare_fp8_kvlen(k, v, kv_lens, tensor_layout, gran, rnd, scale_max=448.0) + (None,)
+        return k_smooth_quant_kvlen(k, kv_lens, tensor_layout, gran, rnd) + (v, None, None)
     # K and V by ONE call (sage_kv_prepare_fp8: it smooths K, does not smooth V and wants V in K's shape).  This is what each
     # caller spelled out before: sageattn_qk_int8_pv_fp8_cuda `smooth_k and not smooth_v and k.shape == v.shape and k.dtype ==
     # v.dtype` (pv_fp8 True; equal dtypes are asserted by _common_checks), sageattn_block_sparse `pv == "fp8" and smooth_k and
@@ -153,11 +161,11 @@ def _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv_fp8, smooth_v):
     return (k8, ks, km) + per_channel_fp8(v, tensor_layout=tensor_layout, scale_max=448.0, smooth_v=smooth_v)
 
 
-def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, sparse=None):
+def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, sparse=None, kv_lens=None):
     """sage_attn_fusedq_pv_{f16,f8} on the operands ``kv`` of ``_prepass`` (FP8 P.V where it has a v_scale); ``q_quant`` is
     (qk_quant_gran, rows per Q scale group).  With ``sparse`` = (plan, pv_thresh, skipped) their block-sparse twins, and with
     a ``pv_thresh`` (fp32 [Hq]) in it the twins with the P.V skip, which fill ``skipped`` (int32 [B,Hq,ceil(M/128),4] or
-    None).  -> (o, lse or None)"""
+    None).  With ``kv_lens`` (int32 [B]; not with ``sparse``) the twins with per-batch key lengths.  -> (o, lse or None)"""
     k8, ks, km, v, v_scale, v_mean = kv
     qk_quant_gran, warpq = q_quant
     B, Hq, M, D = L.dims(q, tensor_layout)
@@ -185,6 +193,9 @@ def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, 
         if pv_thresh is not None:
             name += "_pvskip"
             args += (pv_thresh.data_ptr(), L.ptr(skipped))
+    elif kv_lens is not None:
+        name += "_kvlen"
+        args += (kv_lens.data_ptr(),)
     L.check(getattr(L.lib(), name)(*args, L.stream_ptr(q.device)), name)
     return o, lse
 
@@ -494,6 +505,58 @@ def sageattn_varlen(
                                                     int(max_seqlen_q), int(max_seqlen_k), D, int(is_causal), L.GRAN_PER_BLOCK,
                                                     128, 128, float(sm_scale), 1, st), "sage_attn_qk_int8_pv_f16_varlen")
         return o[..., :head_dim_og]
+
+
+# ---- per-batch key lengths -------------------------------------------------------------------------------------------------
+def _check_kv_lens(kv_lens, B, device):
+    """``kv_lens`` as the kernels read it: an int32 [B] tensor on q's device (its values stay on the device)"""
+    if not isinstance(kv_lens, torch.Tensor):
+        raise TypeError("kv_lens must be an int32 tensor of shape [B]")
+    if kv_lens.dtype != torch.int32:
+        raise TypeError(f"kv_lens must be of dtype int32, got {kv_lens.dtype}")
+    if tuple(kv_lens.shape) != (B,):
+        raise ValueError(f"kv_lens shape {tuple(kv_lens.shape)} does not match [B={B}]")
+    if kv_lens.device != device:
+        raise ValueError(f"kv_lens is on {kv_lens.device}, q on {device}")
+    return kv_lens.contiguous()
+
+
+@torch.compiler.disable
+def sageattn_kvlen(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    kv_lens: torch.Tensor,
+    tensor_layout: str = "HND",
+    is_causal: bool = False,
+    sm_scale: Optional[float] = None,
+    pv: str = "fp16",
+    qk_quant_gran: str = "per_thread",
+    return_lse: bool = False,
+):
+    """SageAttention on the ordinary padded layout with a per-batch number of valid keys: batch b attends its keys
+    [0, len_b), ``len_b = clamp(kv_lens[b], 0, N)``; ``kv_lens`` is an int32 [B] tensor on q's device, read on the device
+    only (no host synchronisation; the call captures into a HIP graph and a replay reads the lengths the tensor holds then).
+
+    For every b with len_b > 0, ``o[b]`` (and ``lse[b]``) are bit-identical to ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` -- by
+    ``pv`` ("fp16" | "fp8", explicit) -- called on ``q[b:b+1]`` and the first len_b keys of ``k[b:b+1]``, ``v[b:b+1]`` with the
+    same ``qk_quant_gran``.  Nothing in rows >= len_b of k or v influences any output, NaN and Inf included: the K smoothing
+    mean, the K scales and the FP8 V scale are taken over the valid rows only, and the kernel neither copies nor multiplies
+    tiles beyond them.  A batch without keys gives o = 0, lse = -inf.  ``is_causal`` is top-left aligned as in the dense
+    operator.  K smoothing is always on, V is not smoothed; ``pv="fp8"`` wants k and v of one shape.  The rule:
+    include/sageattn_hip.h, per-batch key lengths."""
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+    kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+    if pv == "fp8" and k.shape != v.shape:
+        raise ValueError(f"pv='fp8' needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
+        o, lse = _fused_attn(q, kv, tensor_layout, is_causal, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens=kv_lens)
+        return _pack(o[..., :head_dim_og], lse, None, None)
 
 
 # ---- block-sparse attention ------------------------------------------------------------------------------------------------

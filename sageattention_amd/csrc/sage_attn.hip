@@ -43,7 +43,7 @@ template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8
 //  without scratch, but left alone hipcc settles a few registers above the line)
 __global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kernel(const AttnParams p) {
-  constexpr bool SPARSE = false, PVSKIP = false;
+  constexpr bool SPARSE = false, PVSKIP = false, KVLEN = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -55,7 +55,7 @@ template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(256, (D == 64 && PV_FP8) ? 3 : 2)
 void attn_i8_blocksparse_kernel(const AttnParams p) {
   constexpr int NWAVES = 4;
-  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false;
+  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false, KVLEN = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -63,6 +63,8 @@ void attn_i8_blocksparse_kernel(const AttnParams p) {
 
 // (attn_i8_blocksparse_pvskip_kernel, the twin with SpargeAttn's second stage -- PVSKIP = true -- is built from the same body
 //  in sage_attn_pvskip.hip: a file of its own because it needs a compiler option of its own, see there)
+// (attn_i8_kvlen_kernel, the dense kernel with per-batch key lengths -- KVLEN = true -- is built from the same body in
+//  sage_attn_kvlen.hip: as many instantiations again as attn_i8_kernel has without attn_mask, compiled beside this file)
 
 // The rows of the empty q-blocks of a block-sparse call (no active tile: the attention kernel returns at once): o = 0,
 // lse = -inf, and with skip counters (pv_skipped, else null) the four counters of the q-block = 0.  One workgroup per list
@@ -139,6 +141,10 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     if (a.pv_skip && (!a.pv_thresh || ((uintptr_t)a.pv_thresh & 3) || ((uintptr_t)a.pv_skipped & 3)))
       return SAGE_ERR_INVALID_ARGUMENT;
     if (a.is_causal || a.cu_q || a.cu_k || a.mask || a.kvl || a.v_mean) return SAGE_ERR_UNSUPPORTED;
+  }
+  if (a.key_lens) {  // per-batch key lengths: the dense padded layout only; read on the device as aligned int32
+    if (!a.kv_lens || ((uintptr_t)a.kv_lens & 3)) return SAGE_ERR_INVALID_ARGUMENT;
+    if (sparse || a.mask || a.cu_q || a.cu_k || a.kvl) return SAGE_ERR_UNSUPPORTED;
   }
   if (a.mask && (a.mask_kind < 1 || a.mask_kind > 3 || !a.mask_strides || a.is_causal || a.pv_fp8 || a.cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
   const bool fusedq = a.q_dtype >= 0;  // a.q is then the fp16/bf16 query tensor
@@ -229,6 +235,8 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   if (sparse) { p.bs_lists = a.block_lists; p.bs_row = (int)block_list_row(a.N); }  // (share the words of mask / mask_kind)
   c.pvskip = sparse && a.pv_skip;
   if (c.pvskip) { p.pv_thresh = a.pv_thresh; p.pv_skipped = a.pv_skipped; }  // (... and those of two mask strides)
+  c.kvlen = a.key_lens;
+  if (c.kvlen) p.kv_lens = a.kv_lens;  // (shares the word of cu_k, null here)
   c.D = a.D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;
@@ -236,6 +244,7 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
 
 int attn_launch(const AttnCall& c, hipStream_t st) {
   if (c.sparse) return launch_blocksparse(c, st);
+  if (c.kvlen) return launch_kvlen(c, st);
   return by_dim(c.D, [&](auto d) {
     return c.nwaves == 8 ? launch_attn<decltype(d)::value, 8>(c, st) : launch_attn<decltype(d)::value, 4>(c, st);
   });
@@ -264,6 +273,11 @@ static void block_sparse(AttnArgs& a, const int32_t* block_lists, int64_t block_
 // ... with the P.V skip: the per-head thresholds and the skip counters
 static void pv_skip(AttnArgs& a, const float* pv_thresh, int32_t* skipped) {
   a.pv_skip = true; a.pv_thresh = pv_thresh; a.pv_skipped = skipped;
+}
+
+// the forms with per-batch key lengths: batch b attends its keys [0, clamp(kv_lens[b], 0, N))
+static void key_lens(AttnArgs& a, const int32_t* kv_lens) {
+  a.key_lens = true; a.kv_lens = kv_lens;
 }
 
 }  // namespace sage
@@ -519,6 +533,63 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, i
   a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
   block_sparse(a, block_lists, block_lists_bytes);
   pv_skip(a, pv_thresh, skipped);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
+}
+
+// ---- per-batch key lengths: the dense twins' arguments, then kv_lens
+extern "C" int sage_attn_qk_int8_pv_f16_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
+                                              const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale,
+                                              const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                              int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
+                                              int logit_mult_is_one, const int32_t* kv_lens, sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  key_lens(a, kv_lens);
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_qk_int8_pv_f8_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                             const sage_tensor* o, int o_dtype, const float* q_scale, const float* k_scale,
+                                             const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk,
+                                             int M, int N, int D, int is_causal, int qk_gran, int blkq, int warpq,
+                                             float sm_scale, int logit_mult_is_one, const int32_t* kv_lens,
+                                             sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  key_lens(a, kv_lens);
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_fusedq_pv_f16_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                             int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale,
+                                             const void* km, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                             int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                             const int32_t* kv_lens, sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.warpq = warpq; a.sm_scale = sm_scale;
+  key_lens(a, kv_lens);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                            const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                            const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk,
+                                            int M, int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                            const int32_t* kv_lens, sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  key_lens(a, kv_lens);
   if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }

@@ -1,14 +1,16 @@
-// The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip) and
-// attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip), not a header in the usual sense.  Expects in scope: the kernel
-// parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE, PVSKIP
-// (see those two files for what they select).
+// The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip),
+// attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip) and attn_i8_kvlen_kernel (sage_attn_kvlen.hip), not a header in the
+// usual sense.  Expects in scope: the kernel
+// parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE, PVSKIP, KVLEN
+// (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip).
 #ifndef SAGE_ATTN_BODY_OF_KERNEL
-#error "sage_attn_body.h is the body of the attention kernels (sage_attn.hip, sage_attn_pvskip.hip): included nowhere else"
+#error "sage_attn_body.h is the body of the attention kernels (sage_attn.hip, sage_attn_pvskip.hip, sage_attn_kvlen.hip): included nowhere else"
 #endif
   static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
   static_assert(!HAS_MASK || (!CAUSAL && !PV_FP8), "attn_mask: non-causal 16-bit-PV operator");
   static_assert(!SPARSE || (NWAVES == 4 && !CAUSAL && !HAS_MASK), "block-sparse: 4 waves = one block row of the map, non-causal");
   static_assert(!PVSKIP || SPARSE, "the P.V skip exists in the block-sparse form only");
+  static_assert(!KVLEN || (!SPARSE && !HAS_MASK), "per-batch key lengths: the dense kernel without attn_mask");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -43,7 +45,10 @@
   }
   int qb = lid % p.nqb;
   const int bh = lid / p.nqb;
-  const int h = bh % p.Hq, b = bh / p.Hq;
+  // (b, h) of the id: heads within a batch -- except with per-batch key lengths, where the batches alternate within a head.
+  // An XCD runs one contiguous range of logical ids; batch-major, an XCD would hold whole batches, and the one with the
+  // longest batch would finish last whatever the others save (lengths 8192 / 6144 / 4096 / 2048: 0.96x the dense time)
+  const int h = KVLEN ? bh / p.B : bh % p.Hq, b = KVLEN ? bh % p.B : bh / p.Hq;
   // Causal: heaviest q-blocks of a head first (load balance at the end of the grid).  An XCD holds fewer workgroups than
   // a long head has q-blocks, so a head runs in two generations and the second starts again at key 0 (C4 reads 2.06x its
   // K/V + Q bytes from the HBM side, 1.72x with 8-wave workgroups: profiles/r03_ab/fetch_by_geometry.md; at 0.35 TB/s).
@@ -67,6 +72,14 @@
         *reinterpret_cast<uint2*>(ob + (int64_t)(i / (D / 4)) * p.osn + (i % (D / 4)) * 4) = make_uint2(0u, 0u);
       return;
     }
+  }
+  if constexpr (KVLEN) {  // per-batch key lengths: wave-uniform, before any barrier.  Everything below follows N_ -- the tile
+                          // range, the tail mask and the K / V descriptors, which end with row N_ - 1 (rows beyond read as zeros)
+    N_ = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
+    // a batch without keys: nothing to do here.  Its rows are DEFINED, o = 0 as for a packed sequence without keys above and
+    // lse = -inf: attn_kvlen_empty_kernel writes them.  (Written here, the stores cost the head_dim-64 variants the registers
+    // that keep them at three waves per SIMD, and FP8 PV with per-thread scales spilled -- as in the block-sparse form below.)
+    if (N_ <= 0) return;
   }
   // block-sparse: the list row of this (b, h, q-block) = its count, then the ascending tile indices, padded with the last
   // valid one for kBlockListPad entries so that every read-ahead below is blind.  The first entries are requested together

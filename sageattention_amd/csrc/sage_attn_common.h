@@ -20,8 +20,10 @@ struct AttnParams {
   int out_bf16;
   // varlen (packed sequences, core.py:363-477): when cu_q/cu_k are set, "batch" b is sequence b, its rows are
   // [cu[b], cu[b+1]) of the packed [total, H, D] tensors (stride_b unused) and p.M / p.N are the maximum lengths
+  // (per-batch key lengths -- attn_i8_kvlen_kernel, sage_attn_kvlen.hip -- have no packed form: kv_lens, int32 [B], shares
+  //  the word of cu_k, which the other kernels read only behind a non-null cu_q)
   const int* cu_q;
-  const int* cu_k;
+  union { const int* cu_k; const int32_t* kv_lens; };
   // fused Q quantizer: when q_f16 is set, q/q_scale are ignored and every wave quantizes its own 32 query rows in the
   // prologue (per_warp: CUDA numerics, per_thread: Triton numerics -- the pairings of core.py:621-624); km (optional,
   // [B,Hk,D] in q's dtype) yields the LSE correction q.km and lse then receives the FINAL natural-log LSE (core.py:651)

@@ -73,9 +73,10 @@ struct KSmoothCall {
   sage_tensor k;
   float* part;
   int per_wg;  // 64-row blocks per workgroup of the quantizer
+  const int32_t* kv_lens = nullptr;  // sage_k_smooth_quant_kvlen: rows >= clamp(kv_lens[b], 0, N) of batch b are absent
 };
 int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
-                         float* scale, void* km, int gran, int rounding, void* workspace);
+                         float* scale, void* km, int gran, int rounding, void* workspace, const int32_t* kv_lens = nullptr);
 int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st);
 
 // sage_kv_prepare_fp8: K and V chunk statistics, then both quantizers in one launch
@@ -87,10 +88,12 @@ struct KVPrepCall {
   int nblk_k, nunit_v;  // K blocks, V units (VQuantGeom<D>::BLKS blocks each)
   int per_k, per_v;     // ... per workgroup of the streaming kernel
   bool streaming;       // kv_quant_stream_kernel, else kv_quant_kernel (one block / unit per workgroup)
+  const int32_t* kv_lens = nullptr;  // sage_kv_prepare_fp8_kvlen: rows >= clamp(kv_lens[b], 0, N) of batch b are absent
 };
 int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
                      const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding, const sage_tensor* v_fp8,
-                     float* v_scale, float scale_max, void* workspace);
+                     float* v_scale, float scale_max, void* workspace,
+                     const int32_t* kv_lens = nullptr);
 int kv_prepare_launch(const KVPrepCall& c, hipStream_t st);
 
 // ---- attention (sage_attn.hip) ----------------------------------------------------------------------------------------
@@ -119,6 +122,8 @@ struct AttnArgs {
   bool pv_skip = false;       // ... with the P.V skip: per-head thresholds (fp32 [Hq]) and the skip counters (or null)
   const float* pv_thresh = nullptr;
   int32_t* pv_skipped = nullptr;
+  bool key_lens = false;      // per-batch key lengths: batch b attends its keys [0, clamp(kv_lens[b], 0, N)) (device, int32 [B])
+  const int32_t* kv_lens = nullptr;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -128,11 +133,14 @@ struct AttnCall {
   bool pv_fp8, causal, kthread, v_bf16;
   bool sparse;  // attn_i8_blocksparse_kernel (always 4 waves)
   bool pvskip;  // ... its twin attn_i8_blocksparse_pvskip_kernel
+  bool kvlen;   // attn_i8_kvlen_kernel: the dense kernel with per-batch key lengths
 };
 int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
 // the attention launch of a block-sparse call with the P.V skip (c.pvskip; sage_attn_pvskip.hip): attn_launch goes through it
 int launch_blocksparse_pvskip(const AttnCall& c, hipStream_t st);
+// the attention launch of a call with per-batch key lengths (c.kvlen; sage_attn_kvlen.hip): attn_launch goes through it
+int launch_kvlen(const AttnCall& c, hipStream_t st);
 
 // ---- block-sparse tile lists (sage_misc.hip) ---------------------------------------------------------------------------
 // bytes of the lists of one call: a row of block_list_row(N) int32 per (b, h_q, 128-row q-block)

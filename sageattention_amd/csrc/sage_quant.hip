@@ -33,6 +33,20 @@ __host__ __device__ __forceinline__ int kmean_chunk_rows(int N) {
   return KMEAN_ROWS * ((c256 + 15) / 16 > 0 ? (c256 + 15) / 16 : 1);
 }
 
+// chunks of pass 1 (kmean_chunk_rows): at most 16
+__host__ __device__ __forceinline__ int kmean_chunks(int N) {
+  const int rows = kmean_chunk_rows(N);
+  return (N + rows - 1) / rows;
+}
+// Per-batch key lengths (the _kvlen entry points): batch b has the rows [0, len_b), len_b = clamp(kv_lens[b], 0, N), and is
+// chunked as a call on len_b rows would be.  The most chunks a batch of up to N rows can have (a shorter batch may have MORE
+// chunks than one of N rows -- 4096 rows are 16 chunks of 256, 4400 rows 9 of 512): the chunk slots per head of the workspace
+__host__ __device__ __forceinline__ int kmean_max_chunks(int N) {
+  const int c256 = (N + KMEAN_ROWS - 1) / KMEAN_ROWS;
+  return c256 < 16 ? c256 : 16;
+}
+__device__ __forceinline__ int kv_len_of(const int32_t* __restrict__ kv_lens, int b, int N) { return min(max(kv_lens[b], 0), N); }
+
 // chunk s (KMEAN_ROWS rows) of head (b, h) of H: column sums -> part[b][h][s][D]; `red`: 256/(D/8) x (D+1) floats of LDS
 template <int D, bool BF16>
 __device__ __forceinline__ void k_mean_partial_body(const uint16_t* __restrict__ k, int64_t sb, int64_t sh, int64_t sn, int N,
@@ -86,6 +100,18 @@ __global__ __launch_bounds__(256) void k_mean_partial_kernel(const uint16_t* __r
                                                              int64_t sn, int N, float* __restrict__ part, int S) {
   __shared__ float red[256 / (D / 8)][D + 1];
   k_mean_partial_body<D, BF16>(k, sb, sh, sn, N, part, S, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, red);
+}
+
+// ... with per-batch key lengths: the chunks of batch b are those of a call on its len_b rows, in the S chunk slots of its
+// heads; the grid is sized for S slots, and the workgroups of chunks a batch does not have leave before any barrier
+template <int D, bool BF16>
+__global__ __launch_bounds__(256) void k_mean_partial_kvlen_kernel(const uint16_t* __restrict__ k, int64_t sb, int64_t sh,
+                                                                   int64_t sn, int N, float* __restrict__ part, int S,
+                                                                   const int32_t* __restrict__ kv_lens) {
+  __shared__ float red[256 / (D / 8)][D + 1];
+  const int len = kv_len_of(kv_lens, blockIdx.z, N);
+  if ((int)blockIdx.x >= kmean_chunks(len)) return;  // (an empty batch has none)
+  k_mean_partial_body<D, BF16>(k, sb, sh, sn, len, part, S, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, red);
 }
 
 template <bool BF16>
@@ -550,6 +576,40 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kernel(co
   k_quant_stream_body<D, BF16, TRITON>(p, per_wg, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, gmax, mpart);
 }
 
+// The quantizer's parameters for batch b of a call with per-batch key lengths: N and the chunk count become those of its
+// len_b rows, so that the mean, the blocks and their scales are exactly those of a call on the first len_b rows (rows beyond
+// are never loaded: the ragged block clamps to row len_b - 1).  The quantizers address the chunk sums of head (b, h) at
+// (b H + h) S: S is count and head stride in one, but here every head has kmean_max_chunks(N) slots and the batch fills the
+// first S of them -- so the base moves by `part_shift` floats, and the unchanged address arithmetic lands on the head's slots
+// (the kernels without lengths keep their code).  Returns false when the workgroup, whose first 64-row block is blk0, has no
+// block of the batch: it leaves before any barrier.  An empty batch has no mean to take: km = 0, not 0 / 0, stored by the
+// first workgroup of the K half (k_half).
+template <int D>
+__device__ __forceinline__ bool kvlen_batch_params(QuantParams& p, int64_t& part_shift, const int32_t* __restrict__ kv_lens,
+                                                   const int blk0, const int h, const int b, const int H, const bool k_half) {
+  const int len = kv_len_of(kv_lens, b, p.N);
+  if (k_half && len == 0 && blk0 == 0 && threadIdx.x < D / 8)
+    *reinterpret_cast<uint4*>(p.km_out + ((int64_t)b * H + h) * D + threadIdx.x * 8) = make_uint4(0u, 0u, 0u, 0u);
+  const int slots = kmean_max_chunks(p.N);
+  p.N = len;
+  p.S = kmean_chunks(len);
+  part_shift = ((int64_t)b * H + h) * (slots - p.S) * D;
+  p.mean_part += part_shift;
+  return blk0 * 64 < len;
+}
+
+// k_quant_stream_kernel with per-batch key lengths (sage_k_smooth_quant_kvlen): the grid is sized for N rows
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kvlen_kernel(const QuantParams p, const int per_wg,
+                                                                                    const int32_t* __restrict__ kv_lens) {
+  __shared__ unsigned int gmax[3][64];
+  __shared__ __attribute__((aligned(16))) float mpart[16][D];
+  QuantParams pb = p;
+  int64_t part_shift;
+  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, blockIdx.x * per_wg, blockIdx.y, blockIdx.z, gridDim.y, true)) return;
+  k_quant_stream_body<D, BF16, TRITON>(pb, per_wg, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, gmax, mpart);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused K/V pre-pass of the FP8-PV operator, at every length (a sequence is at most 16 chunks, kmean_chunk_rows): TWO launches instead of five
 // (k_mean_partial, quantizer | v_stats_partial, v_stats_final, v_quant_transpose).  Every kernel below is bandwidth- or
@@ -613,18 +673,25 @@ __global__ __launch_bounds__(256) void kv_partial_kernel(const uint16_t* __restr
   else v_amax_partial_body<D, BF16>(v, vsb, vsh, vsn, N, vpart, S, x - S, blockIdx.y, blockIdx.z, gridDim.y, red);
 }
 
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(const QuantParams p, const VPrepParams q, const int nblk_k) {
+// ... with per-batch key lengths (see k_mean_partial_kvlen_kernel): max|v| over the rows < len_b only
+template <int D, bool BF16>
+__global__ __launch_bounds__(256) void kv_partial_kvlen_kernel(const uint16_t* __restrict__ k, int64_t ksb, int64_t ksh, int64_t ksn,
+                                                               const uint16_t* __restrict__ v, int64_t vsb, int64_t vsh, int64_t vsn,
+                                                               int N, float* __restrict__ kpart, float* __restrict__ vpart, int S,
+                                                               const int32_t* __restrict__ kv_lens) {
+  __shared__ float red[256 / (D / 8)][D + 1];
+  const int len = kv_len_of(kv_lens, blockIdx.z, N);
+  const int x = blockIdx.x, s = x < S ? x : x - S;
+  if (s >= kmean_chunks(len)) return;
+  if (x < S) k_mean_partial_body<D, BF16>(k, ksb, ksh, ksn, len, kpart, S, s, blockIdx.y, blockIdx.z, gridDim.y, red);
+  else v_amax_partial_body<D, BF16>(v, vsb, vsh, vsn, len, vpart, S, s, blockIdx.y, blockIdx.z, gridDim.y, red);
+}
+
+// V half of kv_quant_kernel: unit bx (BLKS x 64 tokens) of head (b, h) of H.  p: N and the chunk count S
+template <int D, bool BF16>
+__device__ __forceinline__ void v_quant_unit(const QuantParams& p, const VPrepParams& q, const int bx, const int h, const int b,
+                                             const int H, float (*exch)[D], uint32_t* tile) {
   using G = VQuantGeom<D>;
-  __shared__ unsigned int gmax[64];
-  __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
-  __shared__ __attribute__((aligned(16))) uint32_t tile[G::BLKS * G::IMG];
-  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  if ((int)blockIdx.x < nblk_k) {
-    quant_qk_int8_body<D, 64, BF16, TRITON>(p, blockIdx.x, h, b, H, gmax, exch);
-    return;
-  }
-  const int bx = blockIdx.x - nblk_k;
   const int tg = threadIdx.x / G::TPR, tc = threadIdx.x % G::TPR;
   // the unit's rows first: the statistics below overlap with this trip to HBM
   uint4 raw[4];
@@ -663,24 +730,52 @@ __global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(const Qu
   v_quant_store_image<D>(q.out, q.ob, q.oh, q.od, q.o_tile, p.N, bx, h, b, tile);
 }
 
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(const QuantParams p, const VPrepParams q, const int nblk_k) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[64];
+  __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
+  __shared__ __attribute__((aligned(16))) uint32_t tile[G::BLKS * G::IMG];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  if ((int)blockIdx.x < nblk_k) {
+    quant_qk_int8_body<D, 64, BF16, TRITON>(p, blockIdx.x, h, b, H, gmax, exch);
+    return;
+  }
+  v_quant_unit<D, BF16>(p, q, blockIdx.x - nblk_k, h, b, H, exch, tile);
+}
+
+// ... with per-batch key lengths (sage_kv_prepare_fp8_kvlen): the grid is sized for N rows; the V^T image of the batch's last
+// 64-token block is written whole, its columns >= len_b as zero bytes (v_quant_to_image)
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kvlen_kernel(const QuantParams p, const VPrepParams q, const int nblk_k,
+                                                                              const int32_t* __restrict__ kv_lens) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[64];
+  __shared__ __attribute__((aligned(16))) float exch[16][D];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[G::BLKS * G::IMG];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const bool k_half = (int)blockIdx.x < nblk_k;
+  const int unit = k_half ? blockIdx.x : blockIdx.x - nblk_k;  // K block, or V unit of BLKS blocks
+  QuantParams pb = p;
+  VPrepParams qb = q;
+  int64_t part_shift;
+  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, k_half ? unit : unit * G::BLKS, h, b, H, k_half)) return;
+  qb.part += part_shift;  // (the V partials have the layout of the K sums)
+  if (k_half) quant_qk_int8_body<D, 64, BF16, TRITON>(pb, unit, h, b, H, gmax, exch);
+  else v_quant_unit<D, BF16>(pb, qb, unit, h, b, H, exch, tile);
+}
+
 // Launch B as a STREAMING kernel for long sequences (sage_kv_prepare_fp8 picks by the units a workgroup would walk): workgroups [0, nwg_k) walk per_k consecutive K blocks
 // of their head (k_quant_stream_body), the others per_v consecutive V units (BLKS x 64 tokens), the next unit's rows
 // requested while this one is transposed, the image double-buffered in LDS (one barrier per unit), and the per-channel
 // scale -- S maxima and two IEEE divisions per channel -- finished ONCE per workgroup by its first token group instead of by
 // every thread for every unit (three quarters of the V half's vector work otherwise).  Same arithmetic: bit-identical.
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(const QuantParams p, const VPrepParams q, const int per_k,
-                                                                               const int nwg_k, const int per_v) {
+// V half of kv_quant_stream_kernel: workgroup wg of head (b, h) of H walks per_v units.  tile: two image buffers
+template <int D, bool BF16>
+__device__ __forceinline__ void v_quant_stream_walk(const QuantParams& p, const VPrepParams& q, const int per_v, const int wg,
+                                                    const int h, const int b, const int H, float (*exch)[D],
+                                                    uint32_t (*tile)[VQuantGeom<D>::BLKS * VQuantGeom<D>::IMG]) {
   using G = VQuantGeom<D>;
-  __shared__ unsigned int gmax[3][64];
-  __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
-  __shared__ __attribute__((aligned(16))) uint32_t tile[2][G::BLKS * G::IMG];
-  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  if ((int)blockIdx.x < nwg_k) {
-    k_quant_stream_body<D, BF16, TRITON>(p, per_k, blockIdx.x, h, b, H, gmax, exch);
-    return;
-  }
-  const int wg = blockIdx.x - nwg_k;
   const int nunits = ((p.N + 63) / 64 + G::BLKS - 1) / G::BLKS;
   const int u0 = wg * per_v, u1 = min(u0 + per_v, nunits);
   const uint16_t* vhead = q.v + b * q.sb + h * q.sh;
@@ -725,6 +820,42 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(c
   }
 }
 
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(const QuantParams p, const VPrepParams q, const int per_k,
+                                                                               const int nwg_k, const int per_v) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[3][64];
+  __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
+  __shared__ __attribute__((aligned(16))) uint32_t tile[2][G::BLKS * G::IMG];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  if ((int)blockIdx.x < nwg_k) {
+    k_quant_stream_body<D, BF16, TRITON>(p, per_k, blockIdx.x, h, b, H, gmax, exch);
+    return;
+  }
+  v_quant_stream_walk<D, BF16>(p, q, per_v, blockIdx.x - nwg_k, h, b, H, exch, tile);
+}
+
+// ... with per-batch key lengths (see kv_quant_kvlen_kernel)
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kvlen_kernel(const QuantParams p, const VPrepParams q,
+                                                                                     const int per_k, const int nwg_k, const int per_v,
+                                                                                     const int32_t* __restrict__ kv_lens) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[3][64];
+  __shared__ __attribute__((aligned(16))) float exch[16][D];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[2][G::BLKS * G::IMG];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const bool k_half = (int)blockIdx.x < nwg_k;
+  const int wg = k_half ? blockIdx.x : blockIdx.x - nwg_k;
+  QuantParams pb = p;
+  VPrepParams qb = q;
+  int64_t part_shift;
+  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, k_half ? wg * per_k : wg * per_v * G::BLKS, h, b, H, k_half)) return;
+  qb.part += part_shift;  // (the V partials have the layout of the K sums)
+  if (k_half) k_quant_stream_body<D, BF16, TRITON>(pb, per_k, wg, h, b, H, gmax, exch);
+  else v_quant_stream_walk<D, BF16>(pb, qb, per_v, wg, h, b, H, exch, tile);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K2: sub_mean_f16
 // ------------------------------------------------------------------------------------------------
@@ -753,12 +884,6 @@ __global__ __launch_bounds__(256) void sub_mean_f16_kernel(const uint16_t* __res
 }
 
 // ---- host side (sage_entry.h): checks that fill the parameters, then the launches -----------------------------------------
-
-// chunks of pass 1 (kmean_chunk_rows): at most 16
-static int kmean_chunks(int N) {
-  const int rows = kmean_chunk_rows(N);
-  return (N + rows - 1) / rows;
-}
 
 // Units (64-row K blocks, V units) per workgroup of a streaming quantizer: as many as leave about `target` workgroups for
 // all B*H heads, at most `cap`, and at least one.
@@ -831,8 +956,8 @@ int quant_launch(const QuantCall& c, hipStream_t st) {
 }
 
 int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
-                         float* scale, void* km, int gran, int rounding, void* workspace) {
-  if (!km || !workspace) return SAGE_ERR_INVALID_ARGUMENT;
+                         float* scale, void* km, int gran, int rounding, void* workspace, const int32_t* kv_lens) {
+  if (!km || !workspace || (kv_lens && !aligned16(km))) return SAGE_ERR_INVALID_ARGUMENT;  // (km = 0 of an empty batch: 16-byte stores)
   if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
   if (!tensor_ok(k, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (const int s = dim_dtype_status(D, dtype)) return s;
@@ -844,6 +969,7 @@ int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B,
                                 nullptr, opt))
     return s;
   c.k = *k;
+  c.kv_lens = kv_lens;
   // as many blocks per workgroup as leave about as many workgroups per CU as the quantizer's registers allow to be resident
   // (five at head_dim 64, four at 128), so that every workgroup is resident from the start and streams its share of a head
   const int nblk = (N + 63) / 64;
@@ -854,7 +980,18 @@ int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B,
 int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
   const QuantParams& p = c.q.p;
   launch_begin();
-  launch_k_mean_partial(c.k, c.q.B, c.q.H, p.N, c.q.D, c.q.bf16, c.part, p.S, st);
+  if (c.kv_lens) {
+    const int slots = kmean_max_chunks(p.N);  // chunk slots per head: every batch is chunked by its own length
+    by_dim(c.q.D, [&](auto d) {
+      by_flag(c.q.bf16, [&](auto bf) {
+        hipLaunchKernelGGL((k_mean_partial_kvlen_kernel<decltype(d)::value, decltype(bf)::value>), dim3(slots, c.q.H, c.q.B),
+                           dim3(256), 0, st, (const uint16_t*)c.k.data, c.k.stride_b, c.k.stride_h, c.k.stride_n, p.N, c.part,
+                           slots, c.kv_lens);
+      });
+    });
+  } else {
+    launch_k_mean_partial(c.k, c.q.B, c.q.H, p.N, c.q.D, c.q.bf16, c.part, p.S, st);
+  }
   if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
   const int nblk = (p.N + 63) / 64;
   const dim3 grid((nblk + c.per_wg - 1) / c.per_wg, c.q.H, c.q.B);
@@ -862,8 +999,12 @@ int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
   by_dim(c.q.D, [&](auto d) {
     by_flag(c.q.bf16, [&](auto bf) {
       by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
-        hipLaunchKernelGGL((k_quant_stream_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value>), grid,
-                           dim3(256), 0, st, p, c.per_wg);
+        constexpr int DD = decltype(d)::value;
+        constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value;
+        if (c.kv_lens)
+          hipLaunchKernelGGL((k_quant_stream_kvlen_kernel<DD, BF, TR>), grid, dim3(256), 0, st, p, c.per_wg, c.kv_lens);
+        else
+          hipLaunchKernelGGL((k_quant_stream_kernel<DD, BF, TR>), grid, dim3(256), 0, st, p, c.per_wg);
       });
     });
   });
@@ -872,15 +1013,18 @@ int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
 
 int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
                      const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding, const sage_tensor* v_fp8,
-                     float* v_scale, float scale_max, void* workspace) {
+                     float* v_scale, float scale_max, void* workspace, const int32_t* kv_lens) {
   if (!km || !workspace || !v_scale || !(scale_max > 0.f)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (kv_lens && !aligned16(km)) return SAGE_ERR_INVALID_ARGUMENT;  // (km = 0 of an empty batch: 16-byte stores)
   if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
   if (!tensor_ok(k, 8) || !tensor_ok(v, 8) || B <= 0 || H <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
   if (!tensor_ok(v_fp8, 16)) return SAGE_ERR_INVALID_ARGUMENT;
   if (const int s = dim_dtype_status(D, dtype)) return s;
   const int S = kmean_chunks(N);
+  const int slots = kv_lens ? kmean_max_chunks(N) : S;  // chunk slots per head (every batch is chunked by its own length)
   c.kpart = (float*)workspace;
-  c.vpart = c.kpart + (size_t)B * H * S * D;
+  c.vpart = c.kpart + (size_t)B * H * slots * D;
+  c.kv_lens = kv_lens;
   QuantOptions opt;
   opt.mean_part = c.kpart;
   opt.S = S;
@@ -914,8 +1058,14 @@ int kv_prepare_launch(const KVPrepCall& c, hipStream_t st) {
   launch_begin();
   by_dim(c.k.D, [&](auto d) {
     by_flag(c.k.bf16, [&](auto bf) {
-      hipLaunchKernelGGL((kv_partial_kernel<decltype(d)::value, decltype(bf)::value>), dim3(2 * p.S, H, B), dim3(256), 0, st,
-                         p.x, p.xsb, p.xsh, p.xsn, q.v, q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, p.S);
+      constexpr int DD = decltype(d)::value;
+      constexpr bool BF = decltype(bf)::value;
+      if (c.kv_lens)
+        hipLaunchKernelGGL((kv_partial_kvlen_kernel<DD, BF>), dim3(2 * kmean_max_chunks(p.N), H, B), dim3(256), 0, st, p.x, p.xsb,
+                           p.xsh, p.xsn, q.v, q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, kmean_max_chunks(p.N), c.kv_lens);
+      else
+        hipLaunchKernelGGL((kv_partial_kernel<DD, BF>), dim3(2 * p.S, H, B), dim3(256), 0, st, p.x, p.xsb, p.xsh, p.xsn, q.v,
+                           q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, p.S);
     });
   });
   if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
@@ -925,7 +1075,13 @@ int kv_prepare_launch(const KVPrepCall& c, hipStream_t st) {
       by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
         constexpr int DD = decltype(d)::value;
         constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value;
-        if (c.streaming)
+        if (c.kv_lens && c.streaming)
+          hipLaunchKernelGGL((kv_quant_stream_kvlen_kernel<DD, BF, TR>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q,
+                             c.per_k, nwg_k, c.per_v, c.kv_lens);
+        else if (c.kv_lens)
+          hipLaunchKernelGGL((kv_quant_kvlen_kernel<DD, BF, TR>), dim3(c.nblk_k + c.nunit_v, H, B), dim3(256), 0, st, p, q,
+                             c.nblk_k, c.kv_lens);
+        else if (c.streaming)
           hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, TR>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q, c.per_k,
                              nwg_k, c.per_v);
         else
@@ -1037,6 +1193,30 @@ extern "C" int sage_kv_prepare_fp8(const sage_tensor* k, const sage_tensor* v, i
   KVPrepCall c;
   if (const int s = kv_prepare_check(c, k, v, dtype, B, H, N, D, k_int8, k_scale, km, gran, rounding, v_fp8, v_scale,
                                      scale_max, workspace))
+    return s;
+  return kv_prepare_launch(c, (hipStream_t)stream);
+}
+
+// ---- per-batch key lengths: the twins' arguments, then kv_lens (device, int32 [B], 4-byte aligned)
+static bool kv_lens_ok(const int32_t* kv_lens) { return kv_lens && (reinterpret_cast<uintptr_t>(kv_lens) & 3u) == 0; }
+
+extern "C" int sage_k_smooth_quant_kvlen(const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
+                                         float* scale, void* km, int gran, int rounding, void* workspace,
+                                         const int32_t* kv_lens, sage_stream_t stream) {
+  if (!kv_lens_ok(kv_lens)) return SAGE_ERR_INVALID_ARGUMENT;
+  KSmoothCall c;
+  if (const int s = k_smooth_quant_check(c, k, dtype, B, H, N, D, out, scale, km, gran, rounding, workspace, kv_lens)) return s;
+  return k_smooth_quant_launch(c, (hipStream_t)stream);
+}
+
+extern "C" int sage_kv_prepare_fp8_kvlen(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                                         const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding,
+                                         const sage_tensor* v_fp8, float* v_scale, float scale_max, void* workspace,
+                                         const int32_t* kv_lens, sage_stream_t stream) {
+  if (!kv_lens_ok(kv_lens)) return SAGE_ERR_INVALID_ARGUMENT;
+  KVPrepCall c;
+  if (const int s = kv_prepare_check(c, k, v, dtype, B, H, N, D, k_int8, k_scale, km, gran, rounding, v_fp8, v_scale,
+                                     scale_max, workspace, kv_lens))
     return s;
   return kv_prepare_launch(c, (hipStream_t)stream);
 }

@@ -15,6 +15,8 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_block_sparse_plan_pv(q, k, v, block_lists, plan_shape, pvthreshd, ...)  per-head threshold
     torch.ops.sageattention_amd.attn_sparge_pv(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, ...)
     torch.ops.sageattention_amd.attn_sparge_pv_lse(...) -> (o, lse, skipped)        tensor in, the skip counters out)
+    torch.ops.sageattention_amd.attn_kvlen(q, k, v, kv_lens, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran) -> o
+    torch.ops.sageattention_amd.attn_kvlen_lse(...) -> (o, lse)           (per-batch key lengths, int32 [B] on the device)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -25,7 +27,8 @@ import torch
 
 from . import core
 
-__all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable", "sageattn_sparge_compilable"]
+__all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable", "sageattn_sparge_compilable",
+           "sageattn_kvlen_compilable"]
 
 
 def _entry(pv: str):
@@ -294,6 +297,43 @@ def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
         return op(q, k, v, thr, par, tensor_layout, float(sm_scale), pv, qk_quant_gran)
     op = torch.ops.sageattention_amd.attn_sparge_select_lse if return_lse else torch.ops.sageattention_amd.attn_sparge_select
     return op(q, k, v, thr, par, rule, keep_first, keep_last, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+
+
+@torch.library.custom_op("sageattention_amd::attn_kvlen", mutates_args=())
+def attn_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str, is_causal: bool,
+               sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_kvlen(q, k, v, kv_lens, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale, pv=pv,
+                               qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_kvlen.register_fake
+def _(q, k, v, kv_lens, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_kvlen_lse", mutates_args=())
+def attn_kvlen_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str,
+                   is_causal: bool, sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_kvlen(q, k, v, kv_lens, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale, pv=pv,
+                                 qk_quant_gran=qk_quant_gran, return_lse=True)
+    return o.contiguous(), lse
+
+
+@attn_kvlen_lse.register_fake
+def _(q, k, v, kv_lens, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
+
+
+def sageattn_kvlen_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: torch.Tensor,
+                              tensor_layout: str = "HND", is_causal: bool = False, sm_scale: Optional[float] = None,
+                              pv: str = "fp16", qk_quant_gran: str = "per_thread", return_lse: bool = False):
+    """``sageattn_kvlen`` (core.py) as a traceable custom op: ``kv_lens`` is the int32 [B] tensor of valid keys per batch."""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if sm_scale is None:
+        sm_scale = q.size(-1) ** -0.5
+    op = torch.ops.sageattention_amd.attn_kvlen_lse if return_lse else torch.ops.sageattention_amd.attn_kvlen
+    return op(q, k, v, kv_lens, tensor_layout, bool(is_causal), float(sm_scale), pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",

@@ -84,6 +84,19 @@ def k_smooth_quant(k: torch.Tensor, tensor_layout: str, gran: int, rounding: int
     """``km = k.mean(seq)`` (core.py:612) and the INT8 quantization of ``k - km`` (K half of core.py:621-624) as one call
     of the library (sage_k_smooth_quant): bit-identical to ``k_mean`` + ``_quant(..., mean=km)``, two launches at every
     length (the quantizer finishes the mean from at most 16 chunk sums).  Returns (k_int8, k_scale, km [B,H,D])."""
+    return _k_smooth_quant(k, tensor_layout, gran, rounding, dense_heads, None)
+
+
+def k_smooth_quant_kvlen(k: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str, gran: int, rounding: int,
+                         dense_heads: bool = True):
+    """``k_smooth_quant`` with per-batch key lengths (sage_k_smooth_quant_kvlen; ``kv_lens`` int32 [B] on k's device, clamped
+    to [0, N] by the kernels): batch b is smoothed and quantized as ``k[b:b+1, :len_b]`` would be -- km[b], the INT8 rows
+    < len_b and their scales have those bits -- and rows >= len_b are never read.  The rest of the results is unspecified;
+    km of a batch without keys is 0."""
+    return _k_smooth_quant(k, tensor_layout, gran, rounding, dense_heads, kv_lens)
+
+
+def _k_smooth_quant(k, tensor_layout, gran, rounding, dense_heads, kv_lens):
     B, H, N, D = L.dims(k, tensor_layout)
     if dense_heads and tensor_layout == "NHD":
         out = torch.empty((B, H, N, D), dtype=torch.int8, device=k.device).transpose(1, 2)
@@ -94,9 +107,12 @@ def k_smooth_quant(k: torch.Tensor, tensor_layout: str, gran: int, rounding: int
     km = torch.empty((B, H, D), dtype=k.dtype, device=k.device)
     lib = L.lib()
     ws = torch.empty(max(1, lib.sage_k_mean_workspace_bytes(B, H, N, D) // 4), dtype=torch.float32, device=k.device)
-    L.check(lib.sage_k_smooth_quant(L.desc(k, tensor_layout), L.dtype_code(k.dtype), B, H, N, D, L.desc(out, tensor_layout),
-                                    scale.data_ptr(), km.data_ptr(), gran, rounding, ws.data_ptr(), L.stream_ptr(k.device)),
-            "sage_k_smooth_quant")
+    args = (L.desc(k, tensor_layout), L.dtype_code(k.dtype), B, H, N, D, L.desc(out, tensor_layout), scale.data_ptr(),
+            km.data_ptr(), gran, rounding, ws.data_ptr())
+    if kv_lens is None:
+        L.check(lib.sage_k_smooth_quant(*args, L.stream_ptr(k.device)), "sage_k_smooth_quant")
+    else:
+        L.check(lib.sage_k_smooth_quant_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(k.device)), "sage_k_smooth_quant_kvlen")
     return out, scale, km
 
 
@@ -104,6 +120,18 @@ def kv_prepare_fp8(k: torch.Tensor, v: torch.Tensor, tensor_layout: str, gran: i
     """The K/V side of the FP8-PV operator's pre-pass as one call of the library (sage_kv_prepare_fp8): ``k_smooth_quant(k)``
     and ``per_channel_fp8(v, smooth_v=False)``, bit-identical to them, two launches at every length (five separate ones before).
     Returns (k_int8, k_scale, km, v_fp8, v_scale)."""
+    return _kv_prepare_fp8(k, v, tensor_layout, gran, rounding, scale_max, None)
+
+
+def kv_prepare_fp8_kvlen(k: torch.Tensor, v: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str, gran: int, rounding: int,
+                         scale_max: float = 448.0):
+    """``kv_prepare_fp8`` with per-batch key lengths (sage_kv_prepare_fp8_kvlen; ``kv_lens`` as for ``k_smooth_quant_kvlen``):
+    the K half as there; v_scale[b] is taken over the rows < len_b and the V^T columns < len_b have the bits of the call on
+    ``v[b:b+1, :len_b]``; the columns up to the end of the last 64-token block are zero bytes, those beyond unspecified."""
+    return _kv_prepare_fp8(k, v, tensor_layout, gran, rounding, scale_max, kv_lens)
+
+
+def _kv_prepare_fp8(k, v, tensor_layout, gran, rounding, scale_max, kv_lens):
     B, H, N, D = L.dims(k, tensor_layout)
     assert L.dims(v, tensor_layout) == (B, H, N, D), "k and v must have the same shape"
     npad = (N + 63) // 64 * 64
@@ -121,10 +149,12 @@ def kv_prepare_fp8(k: torch.Tensor, v: torch.Tensor, tensor_layout: str, gran: i
     v_scale = torch.empty((B, H, D), dtype=torch.float32, device=v.device)
     lib = L.lib()
     ws = torch.empty(max(1, lib.sage_kv_prepare_fp8_workspace_bytes(B, H, N, D) // 4), dtype=torch.float32, device=k.device)
-    L.check(lib.sage_kv_prepare_fp8(L.desc(k, tensor_layout), L.desc(v, tensor_layout), L.dtype_code(k.dtype), B, H, N, D,
-                                    L.desc(k8, tensor_layout), ks.data_ptr(), km.data_ptr(), gran, rounding, vd,
-                                    v_scale.data_ptr(), float(scale_max), ws.data_ptr(), L.stream_ptr(k.device)),
-            "sage_kv_prepare_fp8")
+    args = (L.desc(k, tensor_layout), L.desc(v, tensor_layout), L.dtype_code(k.dtype), B, H, N, D, L.desc(k8, tensor_layout),
+            ks.data_ptr(), km.data_ptr(), gran, rounding, vd, v_scale.data_ptr(), float(scale_max), ws.data_ptr())
+    if kv_lens is None:
+        L.check(lib.sage_kv_prepare_fp8(*args, L.stream_ptr(k.device)), "sage_kv_prepare_fp8")
+    else:
+        L.check(lib.sage_kv_prepare_fp8_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(k.device)), "sage_kv_prepare_fp8_kvlen")
     return k8, ks, km, v8, v_scale
 
 
