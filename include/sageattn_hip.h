@@ -126,6 +126,10 @@ int sage_sub_mean_f16(const sage_tensor* v, int dtype, int B, int H, int N, int 
  * described by (stride_b, stride_h, stride_n:=stride of the D index); zero beyond N.
  * v_scale[b,h,d] = amax_d/scale_max (fp32 [B,H,D]); v_mean (optional, fp32 [B,H,D]): when non
  * null the channel mean (sum/ceil16(N), fused.cu:335,381) is subtracted first.
+ * A channel with amax_d == 0 (all zero over the sequence; every channel of a zero-padded head dim) is defined: its
+ * image is all 0x00 and v_scale is 0, so the attention output of that channel is exactly 0.  The reference forms
+ * scale_max/0 = inf and (0-0)*inf = NaN there (fused.cu:399); this is the only departure from it, and only where it
+ * returns NaN.  The same holds for sage_kv_prepare_fp8(_kvlen) and sage_kv_stats_reduce.
  * The reference's 16-row permutation (quant.py:234) is an NVIDIA mma-fragment artefact and is
  * not applied (the fork's HIP port disables it too, fused.hip:362-367).  Its gfx950 counterpart IS:
  * inside every 64-token block position pos holds token
@@ -240,7 +244,10 @@ int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage_tensor* k8
  * In place: (o_acc, lse_acc) <- merge((o_acc, lse_acc), (o_blk, lse_blk)) with
  *   lse = logaddexp(lse_a, lse_b);  o = o_a*exp(lse_a-lse) + o_b*exp(lse_b-lse).
  * o_acc: fp32 [rows, D] contiguous; lse_acc / lse_blk: fp32 [rows] natural log;
- * o_blk: fp16/bf16 [rows, D] contiguous. */
+ * o_blk: fp16/bf16 [rows, D] contiguous.
+ * A side with lse = -inf is empty and weighs 0; an empty side's o may hold anything (an uninitialised accumulator with
+ * lse_acc = -inf is the natural start of a ring, a fully masked block leaves its o undefined): NaN or Inf there never
+ * reaches the result.  Both sides empty: (0, -inf). */
 int sage_merge_attn_states(float* o_acc, float* lse_acc, const void* o_blk, int o_dtype,
                            const float* lse_blk, int64_t rows, int D, sage_stream_t stream);
 
@@ -341,7 +348,8 @@ int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage_tensor* k8
                                     float sm_scale, sage_stream_t stream);
 
 /* Per-channel statistics of a [B,H,N,D] fp16/bf16 tensor over its N rows: stats fp32 [B,H,3,D] = (max, min, sum),
- * deterministic two-level reduction.  The local halves of `k.mean` (core.py:612) and of the per-channel amax of
+ * deterministic two-level reduction.  For N % 16 != 0 the rows [N, ceil16(N)) count as zeros (the reference's padded
+ * amax, fused.cu:335): max = max(true max, 0), min = min(true min, 0); max|x| and the sum are those of the N rows.  The local halves of `k.mean` (core.py:612) and of the per-channel amax of
  * per_channel_fp8 (quant.py:225-322, fused.cu:316-427).  workspace: sage_seq_stats_workspace_bytes bytes. */
 size_t sage_seq_stats_workspace_bytes(int B, int H, int N, int D);
 int sage_seq_stats(const sage_tensor* x, int dtype, int B, int H, int N, int D, float* stats, void* workspace,
@@ -352,6 +360,7 @@ int sage_seq_stats(const sage_tensor* x, int dtype, int B, int H, int N, int D, 
  * quantizers:
  *   km [BH][D] (dtype) = sum of sums / n_total                      (core.py:612 over the WHOLE sequence)
  *   v_scale fp32 [BH][D] = max |v| / scale_max,  v_coef fp32 [BH][2][D] = (0, scale_max / max |v|)   (quant.py:228,318-321)
+ *   (max |v| == 0: v_scale = 0 and the coefficient 0, see sage_quant_v_fp8)
  * Fixed summation order: every rank computes identical bits from the same gathered statistics. */
 int sage_kv_stats_reduce(const float* k_stats, const float* v_stats, int parts, int64_t part_stride, int BH, int D,
                          int64_t n_total, int dtype, float scale_max, void* km, float* v_scale, float* v_coef,

@@ -62,7 +62,10 @@ __global__ __launch_bounds__(256) void v_stats_partial_kernel(const uint16_t* __
   }
 }
 
-// per (b,h): finish the reduction; v_scale = amax/scale_max; keep mean and scale_max/amax for pass 2
+// per (b,h): finish the reduction; v_scale = amax/scale_max; keep mean and scale_max/amax for pass 2.
+// A channel that is constant over the sequence (amax == 0: all zero without smoothing, e.g. every channel of a padded head
+// dim) gets the coefficient 0 instead of scale_max/0 = inf: its image is all 0x00 and v_scale is 0, where the reference
+// (fused.cu:399) writes (0 - 0) * inf = NaN.  The only departure from the reference, and only where it returns NaN.
 __global__ void v_stats_final_kernel(const float* __restrict__ part, int S, int D, int N, float scale_max, int smooth,
                                      float* __restrict__ v_scale, float* __restrict__ v_mean, float* __restrict__ coef) {
   const int64_t bh = blockIdx.x;
@@ -88,7 +91,7 @@ __global__ void v_stats_final_kernel(const float* __restrict__ part, int S, int 
   v_scale[bh * D + d] = amax / scale_max;
   if (smooth) v_mean[bh * D + d] = mean;
   coef[(bh * 2) * D + d] = mean;
-  coef[(bh * 2 + 1) * D + d] = scale_max / amax;
+  coef[(bh * 2 + 1) * D + d] = amax > 0.f ? scale_max / amax : 0.f;
 }
 
 // Pass 2: quantize + transpose (body: sage_fp8_kernels.h)
@@ -155,7 +158,7 @@ __global__ void kv_stats_reduce_kernel(const float* __restrict__ ks, const float
     const float amax = fmaxf(fabsf(a), fabsf(c));
     v_scale[bh * D + d] = amax / scale_max;
     v_coef[(bh * 2) * D + d] = 0.f;
-    v_coef[(bh * 2 + 1) * D + d] = scale_max / amax;
+    v_coef[(bh * 2 + 1) * D + d] = amax > 0.f ? scale_max / amax : 0.f;  // see v_stats_final_kernel
   }
 }
 

@@ -17,18 +17,23 @@ __global__ __launch_bounds__(256) void merge_states_kernel(float* __restrict__ o
   const float la = lse_acc[row], lb = lse_blk[row];
   const float mx = fmaxf(la, lb);
   // logaddexp; la = -inf (empty accumulator) gives wa = 0, wb = 1
-  const float ea = (la == -INFINITY) ? 0.f : __expf(la - mx), eb = (lb == -INFINITY) ? 0.f : __expf(lb - mx);
+  const bool use_a = la != -INFINITY, use_b = lb != -INFINITY;
+  const float ea = use_a ? __expf(la - mx) : 0.f, eb = use_b ? __expf(lb - mx) : 0.f;
   const float sum = ea + eb;
   const float lse = (sum > 0.f) ? mx + __logf(sum) : -INFINITY;
   const float wa = (sum > 0.f) ? ea / sum : 0.f, wb = (sum > 0.f) ? eb / sum : 0.f;
   float* oa = o_acc + row * D + c * 8;
   float fb[8];
   unpack8<BF16>(*reinterpret_cast<const uint4*>(o_blk + row * D + c * 8), fb);
-  float4 a0 = *reinterpret_cast<float4*>(oa), a1 = *reinterpret_cast<float4*>(oa + 4);
-  a0.x = a0.x * wa + fb[0] * wb; a0.y = a0.y * wa + fb[1] * wb; a0.z = a0.z * wa + fb[2] * wb; a0.w = a0.w * wa + fb[3] * wb;
-  a1.x = a1.x * wa + fb[4] * wb; a1.y = a1.y * wa + fb[5] * wb; a1.z = a1.z * wa + fb[6] * wb; a1.w = a1.w * wa + fb[7] * wb;
-  *reinterpret_cast<float4*>(oa) = a0;
-  *reinterpret_cast<float4*>(oa + 4) = a1;
+  const float4 a0 = *reinterpret_cast<float4*>(oa), a1 = *reinterpret_cast<float4*>(oa + 4);
+  const float fa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  // an empty side's o may hold anything (a torch.empty accumulator, the o of a fully masked block): its contribution is
+  // taken by a select, as in merge_many_kernel -- NaN * 0 would poison the row
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (use_a ? fa[j] : 0.f) * wa + (use_b ? fb[j] : 0.f) * wb;
+  *reinterpret_cast<float4*>(oa) = make_float4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<float4*>(oa + 4) = make_float4(r[4], r[5], r[6], r[7]);
   __syncthreads();  // all threads of a row have read lse_acc[row] (rows never straddle a block: 256 % tpr == 0)
   if (c == 0) lse_acc[row] = lse;
 }
@@ -60,7 +65,12 @@ __global__ __launch_bounds__(256) void merge_many_kernel(const MergeMany m, uint
 #pragma unroll
   for (int i = 0; i < MAXC; ++i) {
     const int s = i < m.count ? i : m.count - 1;
-    l[i] = m.lse[s][row] * in_mult;
+    {
+      // the scaled LSE is rounded ONCE: contracted into `l[i] - mx` below (an fma), the maximum's own exponent argument is
+      // the product's rounding residue instead of 0, and a lone or dominant block's LSE comes back one ulp off
+#pragma clang fp contract(off)
+      l[i] = m.lse[s][row] * in_mult;
+    }
     raw[i] = *reinterpret_cast<const uint4*>(m.o[s] + row * D + c * 8);
   }
   float mx = -INFINITY;

@@ -710,7 +710,7 @@ __device__ __forceinline__ void v_quant_unit(const QuantParams& p, const VPrepPa
     for (int j = 0; j < 8; ++j) {
       float a = exch[0][tc * 8 + j];
       for (int s_ = 1; s_ < p.S; ++s_) a = fmaxf(a, exch[s_][tc * 8 + j]);
-      rc[j] = q.scale_max / a;   // v_stats_final_kernel
+      rc[j] = a > 0.f ? q.scale_max / a : 0.f;   // v_stats_final_kernel (an all-zero channel: coefficient 0, not inf)
       vs[j] = a / q.scale_max;
     }
 #pragma unroll
@@ -794,7 +794,7 @@ __device__ __forceinline__ void v_quant_stream_walk(const QuantParams& p, const 
     for (int j = 0; j < 8; ++j) {
       float a = exch[0][tc * 8 + j];
       for (int s_ = 1; s_ < p.S; ++s_) a = fmaxf(a, exch[s_][tc * 8 + j]);
-      rc[j] = q.scale_max / a;   // v_stats_final_kernel
+      rc[j] = a > 0.f ? q.scale_max / a : 0.f;   // v_stats_final_kernel (an all-zero channel: coefficient 0, not inf)
       vs[j] = a / q.scale_max;
     }
 #pragma unroll

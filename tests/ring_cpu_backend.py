@@ -5,6 +5,12 @@ import torch
 from oracle import sage_oracle as O
 
 
+def _weighted(o, w):
+    """o * w per row; a block that weighs 0 (lse = -inf) contributes 0 whatever its o holds (NaN * 0 would poison the row)."""
+    w = w.unsqueeze(-1)
+    return torch.where(w > 0, o.float() * w, torch.zeros((), dtype=torch.float32))
+
+
 class OracleRingBackend:
     def __init__(self, pv="fp16", qk_quant_gran="per_thread"):
         self.pv, self.gran = pv, qk_quant_gran
@@ -62,7 +68,7 @@ class OracleRingBackend:
         lses = torch.stack([b[1] for b in blocks])                       # [P,B,H,M]
         lse = torch.logsumexp(lses, dim=0)
         w = torch.exp(lses - lse).nan_to_num(0.0)                        # blocks with lse = -inf weigh 0
-        o = sum(b[0].float() * w[i].unsqueeze(-1) for i, b in enumerate(blocks))
+        o = sum(_weighted(b[0], w[i]) for i, b in enumerate(blocks))
         return o.to(blocks[0][0].dtype), lse
 
 
@@ -109,7 +115,7 @@ class OracleGatherBackend:
             k8, ks = O.quant_int8_grouped(k, gid, ng, mean=self.km4, rounding="cuda")
         parts = [k8.contiguous(), ks.contiguous()]
         if self.pv == "fp8":
-            y = v.float().transpose(2, 3) * O._ieee_div(O.FP8_E4M3_MAX, self.amax).unsqueeze(-1)   # quant.py:318-321 with the GLOBAL amax
+            y = v.float().transpose(2, 3) * O._scale_coef(O.FP8_E4M3_MAX, self.amax).unsqueeze(-1)   # quant.py:318-321 with the GLOBAL amax; 0 where it is 0
             parts.append(y.clamp(-O.FP8_E4M3_MAX, O.FP8_E4M3_MAX).to(torch.float8_e4m3fn).contiguous())
         else:
             parts.append(v.contiguous())
@@ -174,7 +180,7 @@ class OracleGatherBackend:
         lses = torch.stack([b[1] for b in parts]) / O.LOG2E
         lse = torch.logsumexp(lses, dim=0)
         w = torch.exp(lses - lse).nan_to_num(0.0)
-        o = sum(b[0].float() * w[i].unsqueeze(-1) for i, b in enumerate(parts)).to(parts[0][0].dtype)
+        o = sum(_weighted(b[0], w[i]) for i, b in enumerate(parts)).to(parts[0][0].dtype)
         if not want_lse:
             return o, None
         return o, lse + qstate["corr"] * qstate["sm_scale"]

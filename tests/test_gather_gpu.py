@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import calc_diff
+from seqpar_ref import sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -123,7 +124,9 @@ def test_tile_major_quantizers_are_bit_identical_to_the_dense_ones():
     T = n // 64
     rec = G[0].view(T, R)
     # statistics and the reduced operands
-    assert torch.equal(st[0, :, 2].view(B, Hk, D), k.float().sum(2)) or (st[0, :, 2].view(B, Hk, D) - k.float().sum(2)).abs().max() < 1e-2
+    # the sum within the bound derived from the kernel's addition count (tests/seqpar_ref.py: sum_additions)
+    ksum, kabs = k.double().sum(2).cpu(), k.double().abs().sum(2).cpu()
+    assert ((st[0, :, 2].view(B, Hk, D).cpu().double() - ksum).abs() <= sum_bound(kabs, n, D)).all()
     assert torch.equal(st[1, :, 0].view(B, Hk, D), v.float().amax(2)) and torch.equal(st[1, :, 1].view(B, Hk, D), v.float().amin(2))
     km = sa.quant.k_mean(k)
     assert (be.km.float() - km.float()).abs().max() <= 2.0 ** -10 * km.float().abs().max()
