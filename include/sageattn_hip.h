@@ -511,9 +511,10 @@ int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, int q_dtype,
  * Grids, scale arrays ([B,H,ceil(N/64)(*4)]), the V^T row length (64*ceil(N/64)) and the workgroup geometry are those of N;
  * the bits do not depend on the geometry.  Scales of blocks wholly beyond len_b, INT8 rows >= len_b and V^T columns
  * >= 64*ceil(len_b/64) are unspecified and never read.
- * Not built, SAGE_ERR_UNSUPPORTED from the argument check: kv_lens together with a block map, an attn_mask, cu_seqlens or a
- * kv_layout (the entry points below have none of those arguments).  kv_lens NULL or misaligned: SAGE_ERR_INVALID_ARGUMENT.
- * All checks run before any launch. */
+ * Not built, SAGE_ERR_UNSUPPORTED from the argument check: kv_lens of these DENSE entry points together with a block map, an
+ * attn_mask, cu_seqlens or a kv_layout (the entry points below have none of those arguments; a block map with lengths has
+ * entry points of its own, sage_attn_*_blocksparse_kvlen further down).  kv_lens NULL or misaligned:
+ * SAGE_ERR_INVALID_ARGUMENT.  All checks run before any launch. */
 
 /* sage_k_smooth_quant with kv_lens: the mean of batch b is the sum over its rows < len_b, chunked as a call on len_b rows
  * chunks them and added in the same order, divided by len_b.  The K quantizer treats rows >= len_b as absent for the block
@@ -552,6 +553,58 @@ int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, const sage_t
                                  const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                  int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                  const int32_t* kv_lens, sage_stream_t stream);
+
+/* ==== per-batch key lengths for block-sparse attention (joint video + text attention over a guidance batch whose prompts
+ * differ in length: a padded batch with kv_lens that wants the block-sparse kernels) ====
+ * A block map cuts at 64-key tiles; a prompt ends where it ends.  kv_lens, len_b as above; ntk_b = ceil(len_b / 64).  The rule:
+ *   - For every b with len_b > 0 the rows of batch b in o, lse and the skip counters are BIT-IDENTICAL to the
+ *     _blocksparse twin (with pv_thresh: the _blocksparse_pvskip twin) called on the slices q[b:b+1], k[b:b+1, :, :len_b],
+ *     v[b:b+1, :, :len_b] with the lists of the caller's map cut to its first ntk_b key-tile columns.
+ *   - Tiles j >= ntk_b of a list are treated as off; tile ntk_b - 1 is masked at len_b, not at N.
+ *   - A q-block whose list has no entry < ntk_b has o = 0, lse = -inf and counters 0 -- the convention of empty q-blocks.
+ *     With len_b == 0 every row of the batch has these values.
+ *   - Nothing in rows >= len_b of K or V influences any output, NaN and Inf included ("K" and "V" are the quantized operands:
+ *     make them with sage_k_smooth_quant_kvlen / sage_kv_prepare_fp8_kvlen, whose statistics run over the rows < len_b).
+ *   - The lists are read-only: the kernel counts the entries < ntk_b of a row (the list ascends) and walks that prefix.  Lists
+ *     compacted once for (B, Hq, M, N) stay valid for any kv_lens, call after call.
+ *   - The lengths are read on the device only; a call captures into a HIP graph and a replay reads the lengths held then.
+ * The arguments of the _blocksparse_pvskip twin, then kv_lens.  pv_thresh == NULL selects the kernel without the P.V skip
+ * (skipped is then not read); otherwise pv_thresh and skipped as for the twin.  kv_lens NULL or misaligned:
+ * SAGE_ERR_INVALID_ARGUMENT; every other status as the twin gives it.  All checks run before any launch.  The rows of the
+ * emptied q-blocks are written by a second, tiny launch on the same stream.
+ * Not built: query lengths, a causal form, and kv_lens on the one-call operators, sage_attn_tile_mass and
+ * sage_block_plan_recall. */
+int sage_attn_qk_int8_pv_f16_blocksparse_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
+                                               int v_dtype, const sage_tensor* o, int o_dtype, const float* q_scale,
+                                               const float* k_scale, const float* v_mean, float* lse, int B, int Hq,
+                                               int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
+                                               int warpq, float sm_scale, int logit_mult_is_one,
+                                               const int32_t* block_lists, int64_t block_lists_bytes,
+                                               const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
+                                               sage_stream_t stream);
+int sage_attn_qk_int8_pv_f8_blocksparse_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                              const sage_tensor* o, int o_dtype, const float* q_scale,
+                                              const float* k_scale, const float* v_scale, const float* v_mean,
+                                              float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
+                                              int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
+                                              const int32_t* block_lists, int64_t block_lists_bytes,
+                                              const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
+                                              sage_stream_t stream);
+int sage_attn_fusedq_pv_f16_blocksparse_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                              const sage_tensor* v, int v_dtype, const sage_tensor* o, int o_dtype,
+                                              const float* k_scale, const void* km, const float* v_mean, float* lse,
+                                              int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+                                              int warpq, float sm_scale, const int32_t* block_lists,
+                                              int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                              const int32_t* kv_lens, sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_blocksparse_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                             const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                             const float* k_scale, const void* km, const float* v_scale,
+                                             const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N,
+                                             int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                             const int32_t* block_lists, int64_t block_lists_bytes,
+                                             const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
+                                             sage_stream_t stream);
 
 /* ==== block-map predictor (new: makes the tile lists above from Q and K at run time, after SpargeAttn's first stage --
  * pooled scores gated by the self-similarity of the blocks.  The reference has no counterpart; the rule below is this
@@ -614,6 +667,26 @@ int sage_block_select(const float* pooled_q, const float* sim_q, const float* po
                       int rule, const float* rule_param /* cdfthreshd or topk, fp32 [Hq] */,
                       int keep_first, int keep_last, int32_t* block_lists, int64_t block_lists_bytes,
                       uint8_t* block_map, sage_stream_t stream);
+
+/* The predictor with per-batch key lengths (kv_lens, len_b, ntk_b as for sage_attn_*_blocksparse_kvlen): the twins'
+ * arguments, then kv_lens (NULL or misaligned: SAGE_ERR_INVALID_ARGUMENT; every other status as the twin).  Grids, strides
+ * and output layouts are those of N.
+ * sage_block_pool_sim_kvlen pools block i of batch b over its c = min(blk, len_b - blk*i) valid rows; rows >= len_b are
+ * never loaded.  The statistics of the blocks of batch b below ceil(len_b / blk) are bit-identical to those of the twin on
+ * x[b:b+1, :, :len_b]; those of blocks wholly beyond the length are unspecified and never read.  (Pool K with it; Q has no
+ * lengths and goes through sage_block_pool_sim.)
+ * sage_block_select_kvlen applies the rule of sage_block_select with ntk_b in the place of ntk everywhere: KEPT is
+ * j < keep_first or j >= ntk_b - keep_last (keep_last pins the last VALID blocks), CANDIDATE, n and kcount follow, and key
+ * blocks j >= ntk_b do not exist -- their tiles are off and their map columns are written 0.  With len_b == 0 every list of
+ * the batch has count 0: the one exception to "every q-block keeps at least one tile".  For len_b > 0 the count and the
+ * entries of every list row of batch b equal those sage_block_select writes for the slice (statistics of the slice, N =
+ * len_b); the row stride of the lists and of the map stays that of N. */
+int sage_block_pool_sim_kvlen(const sage_tensor* x, int dtype, int B, int H, int N, int D, int blk, const void* mean,
+                              float* pooled, float* sim, const int32_t* kv_lens, sage_stream_t stream);
+int sage_block_select_kvlen(const float* pooled_q, const float* sim_q, const float* pooled_k, const float* sim_k,
+                            int B, int Hq, int Hk, int M, int N, int D, float sm_scale, const float* simthreshd1,
+                            int rule, const float* rule_param, int keep_first, int keep_last, int32_t* block_lists,
+                            int64_t block_lists_bytes, uint8_t* block_map, const int32_t* kv_lens, sage_stream_t stream);
 
 /* ==== calibration of the predictor (new: what a block map loses, measured on the operands of the attention kernels; the
  * instrument behind a threshold search such as SpargeAttn's tuning mode.  The reference has no counterpart.) ====

@@ -21,6 +21,10 @@ SOURCES = [
     ("sage_attn_pvskip.hip", ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm", "-structurizecfg-skip-uniform-regions"]),
     # the dense kernels with per-batch key lengths: the same body and flags as sage_attn.hip
     ("sage_attn_kvlen.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # the block-sparse kernels with per-batch key lengths, and their twin with the P.V skip (its option as above)
+    ("sage_attn_sparse_kvlen.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    ("sage_attn_sparse_kvlen_pvskip.hip", ["-fno-slp-vectorize", "-ffp-contract=off", "-mllvm",
+                                           "-structurizecfg-skip-uniform-regions"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -63,7 +67,10 @@ def _check_occupancy(src, compiler_output):
                             re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name) or  # the block-sparse twins
                             re.search(r"attn_i8_kvlen_kernelILi64ELi4E(Lb[01]E){4}EE", name) or     # ... with key lengths
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
-                            re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name))
+                            re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name) or
+                            # the block-sparse kernels with key lengths, held to the lines of their twins above
+                            re.search(r"attn_i8_blocksparse_kvlen_kernelILi64E(Lb[01]E){3}EE", name) or
+                            re.search(r"attn_i8_blocksparse_pvskip_kvlen_kernelILi64ELb[01]ELb0ELb[01]EEE", name))
         if m and guarded and int(m.group(1)) > 168:
             raise RuntimeError(f"{src}: kernel {name} uses {m.group(1)} VGPRs (> 168: two waves per SIMD instead of three)")
 
@@ -164,6 +171,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_pvskip.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_kvlen.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_sparse_kvlen.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_sparse_kvlen_pvskip.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -149,6 +149,29 @@ SIGNATURES = {
     "sage_attn_fusedq_pv_f8_kvlen": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                              c_void_p, c_void_p]),
+    # block-sparse attention with per-batch key lengths: the _blocksparse_pvskip twins' arguments, then kv_lens
+    "sage_attn_qk_int8_pv_f16_blocksparse_kvlen": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                           c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
+                                                           c_void_p, c_void_p, c_void_p]),
+    "sage_attn_qk_int8_pv_f8_blocksparse_kvlen": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                          c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f16_blocksparse_kvlen": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                          c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p]),
+    "sage_attn_fusedq_pv_f8_blocksparse_kvlen": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                         c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                                         c_void_p, c_void_p, c_void_p]),
+    # the predictor with per-batch key lengths: the twins' arguments, then kv_lens
+    "sage_block_pool_sim_kvlen": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "sage_block_select_kvlen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_void_p]),
     "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

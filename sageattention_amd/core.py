@@ -165,7 +165,8 @@ def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, 
     """sage_attn_fusedq_pv_{f16,f8} on the operands ``kv`` of ``_prepass`` (FP8 P.V where it has a v_scale); ``q_quant`` is
     (qk_quant_gran, rows per Q scale group).  With ``sparse`` = (plan, pv_thresh, skipped) their block-sparse twins, and with
     a ``pv_thresh`` (fp32 [Hq]) in it the twins with the P.V skip, which fill ``skipped`` (int32 [B,Hq,ceil(M/128),4] or
-    None).  With ``kv_lens`` (int32 [B]; not with ``sparse``) the twins with per-batch key lengths.  -> (o, lse or None)"""
+    None).  With ``kv_lens`` (int32 [B]) the twins with per-batch key lengths: the dense ones, and with ``sparse`` the
+    ``_blocksparse_kvlen`` entry points (a None ``pv_thresh`` travels as NULL: no P.V skip).  -> (o, lse or None)"""
     k8, ks, km, v, v_scale, v_mean = kv
     qk_quant_gran, warpq = q_quant
     B, Hq, M, D = L.dims(q, tensor_layout)
@@ -190,7 +191,10 @@ def _fused_attn(q, kv, tensor_layout, is_causal, q_quant, sm_scale, return_lse, 
         plan, pv_thresh, skipped = sparse
         name += "_blocksparse"
         args += (plan.lists.data_ptr(), plan.lists.numel() * 4)
-        if pv_thresh is not None:
+        if kv_lens is not None:
+            name += "_kvlen"
+            args += (L.ptr(pv_thresh), L.ptr(skipped), kv_lens.data_ptr())
+        elif pv_thresh is not None:
             name += "_pvskip"
             args += (pv_thresh.data_ptr(), L.ptr(skipped))
     elif kv_lens is not None:
@@ -622,6 +626,7 @@ def sageattn_block_sparse(
     is_causal: bool = False,
     pvthreshd=None,
     return_skipped: bool = False,
+    kv_lens: Optional[torch.Tensor] = None,
 ):
     """SageAttention over the active 128x64 tiles of a block map (SpargeAttn's ``mask_id`` geometry): ``block_map[b,h,i,j]``
     non-zero means query rows [128 i, 128 i + 128) of head h attend keys [64 j, 64 j + 64); tiles that are off are neither
@@ -634,13 +639,24 @@ def sageattn_block_sparse(
     first of its list, whose scores all lie at least ``pvthreshd`` below the running maximum of their rows (the rule:
     include/sageattn_hip.h, sage_attn_*_blocksparse_pvskip).  Every probability left out is below e^-pvthreshd.  Values of
     a tensor that are not > 0, +inf or NaN never skip.  ``return_skipped`` appends the int32 counters
-    [B, Hq, ceil(M/128), 4]: how many tiles each wave skipped.  Returns o, then lse, then the counters, each when asked for."""
+    [B, Hq, ceil(M/128), 4]: how many tiles each wave skipped.  Returns o, then lse, then the counters, each when asked for.
+
+    ``kv_lens`` (int32 [B] on q's device, read on the device only -- no host synchronisation, the call captures into a HIP
+    graph) gives every batch its own number of valid keys, ``len_b = clamp(kv_lens[b], 0, N)``: tiles at or beyond
+    ``ceil(len_b / 64)`` count as off, the last valid tile is masked at ``len_b``, and the K (and FP8 V) statistics are
+    taken over the valid rows only, so nothing in rows >= len_b of k or v influences any output, NaN and Inf included.  For
+    len_b > 0, ``o[b]``, ``lse[b]`` and the counters of batch b are bit-identical to this operator called on ``q[b:b+1]``, the
+    first len_b keys of ``k[b:b+1]`` / ``v[b:b+1]`` and the map cut to ``ceil(len_b / 64)`` columns; a q-block left without
+    a tile -- every q-block of a batch without keys -- gives o = 0, lse = -inf, counters 0.  The map or plan is that of N
+    and is not modified: one plan serves any lengths.  Needs ``smooth_k=True``; ``pv="fp8"`` wants k and v of one shape.
+    The rule: include/sageattn_hip.h, per-batch key lengths for block-sparse attention."""
     _check_pvskip_args(pvthreshd, return_skipped)
     if is_causal:  # accepted only to be refused by name: unknown keywords are a TypeError
         raise ValueError("sageattn_block_sparse is non-causal: express the causal structure in the block map")
     _check_sparse_args(pv, qk_quant_gran, tensor_layout)
     B, Hq, M, _ = L.dims(q, tensor_layout)
     N = L.dims(k, tensor_layout)[2]
+    kv_lens = _check_sparse_kv_lens(kv_lens, q, k, v, pv, smooth_k)
     if isinstance(block_map, BlockSparsePlan):
         if (block_map.B, block_map.Hq, block_map.M, block_map.N) != (B, Hq, M, N):
             raise ValueError(f"the plan was made for (B, Hq, M, N) = {(block_map.B, block_map.Hq, block_map.M, block_map.N)}, "
@@ -658,7 +674,19 @@ def sageattn_block_sparse(
     def plan_from(q, k, km, sm_scale):
         return block_map if isinstance(block_map, BlockSparsePlan) else block_sparse_plan(block_map, M, N)
     return _block_sparse_tail(q, k, v, tensor_layout, sm_scale, (pv, qk_quant_gran, smooth_k), plan_from,
-                              (return_lse, False, pvthreshd, return_skipped))
+                              (return_lse, False, pvthreshd, return_skipped), kv_lens)
+
+
+def _check_sparse_kv_lens(kv_lens, q, k, v, pv, smooth_k):
+    """The ``kv_lens`` keyword of the block-sparse operators, checked before any device call -> the tensor or None"""
+    if kv_lens is None:
+        return None
+    kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+    if not smooth_k:
+        raise ValueError("kv_lens needs smooth_k=True: the length-aware K pre-pass always smooths")
+    if pv == "fp8" and k.shape != v.shape:
+        raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    return kv_lens
 
 
 def _check_sparse_args(pv, qk_quant_gran, tensor_layout):
@@ -676,11 +704,11 @@ def _pack(o, lse, plan, skipped):
     return out if len(out) > 1 else out[0]
 
 
-def _block_sparse_tail(q, k, v, tensor_layout, sm_scale, quant, plan_from, want):
+def _block_sparse_tail(q, k, v, tensor_layout, sm_scale, quant, plan_from, want, kv_lens=None):
     """What ``sageattn_block_sparse`` and ``sageattn_sparge`` do below their argument checks: pad, the K (or K + V)
     pre-pass, the plan -- ``plan_from(q, k, km, sm_scale)`` on the padded views and the smoothing mean --, the block-sparse
     attention kernel and the return tuple.  ``quant`` = (pv, qk_quant_gran, smooth_k), ``want`` = (return_lse, return_plan,
-    pvthreshd, return_skipped)."""
+    pvthreshd, return_skipped).  With ``kv_lens`` the length-aware pre-pass and the ``_blocksparse_kvlen`` kernels."""
     pv, qk_quant_gran, smooth_k = quant
     return_lse, return_plan, pvthreshd, return_skipped = want
     _common_checks(q, k, v)
@@ -688,10 +716,11 @@ def _block_sparse_tail(q, k, v, tensor_layout, sm_scale, quant, plan_from, want)
         q, k, v, head_dim_og = _pad_head_dim(q, k, v)
         if sm_scale is None:
             sm_scale = head_dim_og ** -0.5
-        kv = _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv == "fp8", False)
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, smooth_k, pv == "fp8", False, kv_lens)
         plan = plan_from(q, k, kv[2], sm_scale)
         thr, skipped = _pvskip_tensors(pvthreshd, return_skipped, plan.B, plan.Hq, plan.M, q.device)
-        o, lse = _fused_attn(q, kv, tensor_layout, False, (qk_quant_gran, 32), sm_scale, return_lse, (plan, thr, skipped))
+        o, lse = _fused_attn(q, kv, tensor_layout, False, (qk_quant_gran, 32), sm_scale, return_lse, (plan, thr, skipped),
+                             kv_lens=kv_lens)
         return _pack(o[..., :head_dim_og], lse, plan if return_plan else None, skipped)
 
 
@@ -734,10 +763,11 @@ def _check_select_args(topk, keep_first, keep_last):
             raise ValueError(f"{name} must be an int >= 0 (a number of 64-key blocks), got {value!r}")
 
 
-def _sparge_predict(q, k, km, tensor_layout, sm_scale, want_map, select):
+def _sparge_predict(q, k, km, tensor_layout, sm_scale, want_map, select, kv_lens=None):
     """sage_block_pool_sim on q (128-row blocks) and on k - km (64-row blocks), then sage_block_select with ``select`` =
     (simthreshd1, cdfthreshd, topk, keep_first, keep_last): rule TOPK when ``topk`` is given, else CDF -> (plan, uint8 map or
-    None).  q and k are padded ABI views, km [B,Hk,D] in their dtype."""
+    None).  q and k are padded ABI views, km [B,Hk,D] in their dtype.  With ``kv_lens`` (int32 [B]) the ``_kvlen`` twins: K is
+    pooled over the valid rows of every batch and the rule runs over its ceil(len_b / 64) key blocks."""
     simthreshd1, cdfthreshd, topk, keep_first, keep_last = select
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k, tensor_layout)
@@ -749,20 +779,22 @@ def _sparge_predict(q, k, km, tensor_layout, sm_scale, want_map, select):
     else:
         rule, par = L.SELECT_TOPK, _per_head(topk, Hq, q.device, "topk")
     pq, sq = block_pool_sim(q, 128, tensor_layout)
-    pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
+    pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km, kv_lens=kv_lens)
     lists = torch.empty(_plan_ints(B, Hq, M, N), dtype=torch.int32, device=q.device)
     bmap = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.uint8, device=q.device) if want_map else None
     ntk = (N + 63) // 64  # keeps beyond it act as ntk
-    L.check(L.lib().sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
-                                  float(sm_scale), thr.data_ptr(), rule, par.data_ptr(), min(keep_first, ntk),
-                                  min(keep_last, ntk), lists.data_ptr(), lists.numel() * 4, L.ptr(bmap),
-                                  L.stream_ptr(q.device)), "sage_block_select")
+    args = (pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D, float(sm_scale), thr.data_ptr(),
+            rule, par.data_ptr(), min(keep_first, ntk), min(keep_last, ntk), lists.data_ptr(), lists.numel() * 4, L.ptr(bmap))
+    if kv_lens is None:
+        L.check(L.lib().sage_block_select(*args, L.stream_ptr(q.device)), "sage_block_select")
+    else:
+        L.check(L.lib().sage_block_select_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(q.device)), "sage_block_select_kvlen")
     return BlockSparsePlan(lists, B, Hq, M, N), bmap
 
 
 def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", simthreshd1=0.6, cdfthreshd=0.98,
                 sm_scale: Optional[float] = None, km: Optional[torch.Tensor] = None, return_map: bool = False,
-                topk=None, keep_first: int = 0, keep_last: int = 0):
+                topk=None, keep_first: int = 0, keep_last: int = 0, kv_lens: Optional[torch.Tensor] = None):
     """Predict the block map of ``sageattn_block_sparse`` from Q and K (the rule: include/sageattn_hip.h,
     sage_block_select): pooled 128-row q-blocks against pooled 64-row key blocks of ``k - km``, per q-block the fewest key
     blocks that hold ``cdfthreshd`` of the softmax mass, and every tile of a block whose rows are not alike (mean cosine
@@ -773,8 +805,19 @@ def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", si
     ``topk`` (a float > 0 or an fp32 tensor [Hq]) selects by budget instead: per q-block the ``ceil(topk * n)`` best-scoring
     of the head's n candidate key blocks, so that every self-similar q-block of a head gets a list of the same length;
     ``cdfthreshd`` is then not read.  ``keep_first`` / ``keep_last`` (ints >= 0) pin the first / last key blocks on under
-    either rule (text tokens, an attention sink): they are always computed and take no part in the selection."""
+    either rule (text tokens, an attention sink): they are always computed and take no part in the selection.
+
+    ``kv_lens`` (int32 [B] on q's device, read on the device only): batch b has the key blocks below ``ceil(len_b / 64)``,
+    ``len_b = clamp(kv_lens[b], 0, N)`` -- the last of them pooled over its valid rows, ``keep_last`` pinning the last valid
+    blocks, n and the budget counted among them -- and its list rows equal those of this function on ``q[b:b+1]`` and the
+    first len_b keys of ``k[b:b+1]``; map columns beyond are False, and a batch without keys gets empty lists.  ``km``
+    then defaults to the length-aware smoothing mean, the one the attention call will smooth with.  That default is heavy for
+    a planning call: it runs the whole length-aware K pre-pass (``k_smooth_quant_kvlen``: an INT8 K tensor, its scales and a
+    workspace are allocated and written) and keeps only the mean -- pass ``km`` when the mean is at hand
+    (``sageattn_sparge`` does: its pre-pass runs once).  The plan is for (B, Hq, M, N)."""
     _check_select_args(topk, keep_first, keep_last)
+    if kv_lens is not None:
+        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
     assert q.is_cuda, "Input tensors must be on cuda."
     assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
     assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
@@ -782,12 +825,14 @@ def sparge_plan(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", si
         q, k, _, head_dim_og = _pad_head_dim(q, k, k)
         if sm_scale is None:
             sm_scale = head_dim_og ** -0.5
-        if km is None:
+        if km is None and kv_lens is not None:  # the mean over the valid rows: what the length-aware K pre-pass smooths with
+            km = k_smooth_quant_kvlen(k, kv_lens, tensor_layout, L.GRAN_PER_THREAD, L.ROUND_TRITON)[2]
+        elif km is None:
             km = k_mean(k, tensor_layout)
         else:
             km = torch.nn.functional.pad(km, (0, k.size(-1) - km.size(-1))).to(k.dtype).contiguous()
         plan, bmap = _sparge_predict(q, k, km, tensor_layout, sm_scale, return_map,
-                                     (simthreshd1, cdfthreshd, topk, keep_first, keep_last))
+                                     (simthreshd1, cdfthreshd, topk, keep_first, keep_last), kv_lens)
     return (plan, bmap.view(torch.bool)) if return_map else plan
 
 
@@ -809,6 +854,7 @@ def sageattn_sparge(
     keep_last: int = 0,
     pvthreshd=None,
     return_skipped: bool = False,
+    kv_lens: Optional[torch.Tensor] = None,
 ):
     """``sageattn_block_sparse`` on the block map that ``sparge_plan`` predicts for this q and k: the K (or K + V) pre-pass
     runs once, the predictor uses its smoothing mean, and the block-sparse attention kernel reads the predicted lists.
@@ -816,17 +862,20 @@ def sageattn_sparge(
     ``return_lse``, then the ``BlockSparsePlan`` with ``return_plan``.  Non-causal.  ``topk``, ``keep_first`` and
     ``keep_last`` as for ``sparge_plan``: with ``topk`` the budget rule is used and ``cdfthreshd`` is not read.
     ``pvthreshd`` and ``return_skipped`` as for ``sageattn_block_sparse`` (SpargeAttn's second stage, on the predicted
-    tiles); the counters come last: o, lse, plan, skipped."""
+    tiles); the counters come last: o, lse, plan, skipped.  ``kv_lens`` (int32 [B] on q's device) as for ``sparge_plan`` and
+    ``sageattn_block_sparse``: bit-identical to ``sageattn_block_sparse(q, k, v, sparge_plan(q, k, ..., kv_lens=kv_lens),
+    kv_lens=kv_lens)``."""
     _check_select_args(topk, keep_first, keep_last)
     _check_pvskip_args(pvthreshd, return_skipped)
     _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+    kv_lens = _check_sparse_kv_lens(kv_lens, q, k, v, pv, True)
 
     select = (simthreshd1, cdfthreshd, topk, keep_first, keep_last)
 
     def plan_from(q, k, km, sm_scale):
-        return _sparge_predict(q, k, km, tensor_layout, sm_scale, False, select)[0]
+        return _sparge_predict(q, k, km, tensor_layout, sm_scale, False, select, kv_lens)[0]
     return _block_sparse_tail(q, k, v, tensor_layout, sm_scale, (pv, qk_quant_gran, True), plan_from,
-                              (return_lse, return_plan, pvthreshd, return_skipped))
+                              (return_lse, return_plan, pvthreshd, return_skipped), kv_lens)
 
 
 # ---- calibration of the predictor ------------------------------------------------------------------------------------------------
@@ -851,7 +900,8 @@ def sageattn_tile_mass(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "H
     tile's keys and averaged over the block's valid rows (the definition: include/sageattn_hip.h, sage_attn_tile_mass).  It
     is computed from the INT8 Q and K and the scales that operator multiplies -- same head-dim padding, K pre-pass and Q
     quantizer -- so each row of the last axis sums to 1 and ``plan_recall`` of a map is the share of the probability that the
-    map keeps.  Costs about one dense attention call.  Non-causal."""
+    map keeps.  Costs about one dense attention call.  Non-causal.  Per-batch key lengths are not built here: there is no
+    ``kv_lens`` keyword (a TypeError, as every unknown keyword); the mass of a padded batch includes its padding."""
     _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
     assert q.is_cuda, "Input tensors must be on cuda."
     assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
@@ -877,7 +927,8 @@ def plan_recall(plan_or_map, mass: torch.Tensor):
     """What a plan keeps of ``mass`` (``sageattn_tile_mass``): (recall fp32 [B,Hq,nqb], kept int32 [B,Hq,nqb]) -- per q-block
     the summed mass of its active tiles and their number (sage_block_plan_recall: deterministic, and never smaller for a
     superset of tiles).  ``plan_or_map`` is a ``BlockSparsePlan`` or a bool / uint8 map [B|1, Hq|1, nqb, ntk], which is
-    compacted with ``block_sparse_plan`` first.  An empty q-block has recall 0."""
+    compacted with ``block_sparse_plan`` first.  An empty q-block has recall 0.  No ``kv_lens`` keyword: the lists of a plan
+    made with lengths are taken as they stand (tiles beyond a batch's length are off in them already)."""
     if not isinstance(mass, torch.Tensor) or mass.dim() != 4 or mass.dtype != torch.float32:
         raise ValueError("mass must be the fp32 [B,Hq,ceil(M/128),ceil(N/64)] tensor of sageattn_tile_mass")
     B, Hq, nqb, ntk = mass.shape
@@ -936,7 +987,9 @@ def sparge_tune(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", ta
     blocks that are not self-similar or are pinned on do not depend on the parameter.  sage_block_plan_recall adds the
     non-negative mass in fixed tile slots and a fixed tree, so a superset never sums to less, and the reductions over batches
     and q-blocks are fixed-order sums or minima of these.  Head recall is therefore monotone in the parameter, in fp32 as
-    well as in exact arithmetic, and the grid splits into a failing part below ``param`` and a passing part from it on."""
+    well as in exact arithmetic, and the grid splits into a failing part below ``param`` and a passing part from it on.
+
+    Per-batch key lengths are not built here: there is no ``kv_lens`` keyword (a TypeError); tune on unpadded data."""
     if rule not in ("cdf", "topk"):
         raise ValueError(f"rule must be 'cdf' or 'topk', got {rule!r}")
     if reduce not in ("mean", "min"):

@@ -65,6 +65,8 @@ void attn_i8_blocksparse_kernel(const AttnParams p) {
 //  in sage_attn_pvskip.hip: a file of its own because it needs a compiler option of its own, see there)
 // (attn_i8_kvlen_kernel, the dense kernel with per-batch key lengths -- KVLEN = true -- is built from the same body in
 //  sage_attn_kvlen.hip: as many instantiations again as attn_i8_kernel has without attn_mask, compiled beside this file)
+// (attn_i8_blocksparse_kvlen_kernel and attn_i8_blocksparse_pvskip_kvlen_kernel, the block-sparse kernels with per-batch key
+//  lengths -- SPARSE and KVLEN -- are built from the same body in sage_attn_sparse_kvlen.hip and sage_attn_sparse_kvlen_pvskip.hip)
 
 // The rows of the empty q-blocks of a block-sparse call (no active tile: the attention kernel returns at once): o = 0,
 // lse = -inf, and with skip counters (pv_skipped, else null) the four counters of the q-block = 0.  One workgroup per list
@@ -91,6 +93,7 @@ static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
 
 // block-sparse form: the kernel, or its twin with the P.V skip (sage_attn_pvskip.hip), then the rows of the empty q-blocks
 static int launch_blocksparse(const AttnCall& c, hipStream_t st) {
+  if (c.sparse_kvlen) return launch_blocksparse_kvlen(c, st);  // ... with key lengths: kernels and empty rows of their own
   const int s = c.pvskip ? launch_blocksparse_pvskip(c, st) : launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
     return attn_i8_blocksparse_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
   });
@@ -140,7 +143,10 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     if (!a.block_lists || !aligned16(a.block_lists)) return SAGE_ERR_INVALID_ARGUMENT;
     if (a.pv_skip && (!a.pv_thresh || ((uintptr_t)a.pv_thresh & 3) || ((uintptr_t)a.pv_skipped & 3)))
       return SAGE_ERR_INVALID_ARGUMENT;
+    if (a.block_key_lens && (!a.block_kv_lens || ((uintptr_t)a.block_kv_lens & 3))) return SAGE_ERR_INVALID_ARGUMENT;
     if (a.is_causal || a.cu_q || a.cu_k || a.mask || a.kvl || a.v_mean) return SAGE_ERR_UNSUPPORTED;
+  } else if (a.block_key_lens) {
+    return SAGE_ERR_UNSUPPORTED;  // the lengths of the block-sparse form without its lists
   }
   if (a.key_lens) {  // per-batch key lengths: the dense padded layout only; read on the device as aligned int32
     if (!a.kv_lens || ((uintptr_t)a.kv_lens & 3)) return SAGE_ERR_INVALID_ARGUMENT;
@@ -237,6 +243,8 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   if (c.pvskip) { p.pv_thresh = a.pv_thresh; p.pv_skipped = a.pv_skipped; }  // (... and those of two mask strides)
   c.kvlen = a.key_lens;
   if (c.kvlen) p.kv_lens = a.kv_lens;  // (shares the word of cu_k, null here)
+  c.sparse_kvlen = sparse && a.block_key_lens;
+  if (c.sparse_kvlen) p.kv_lens = a.block_kv_lens;  // (the word of cu_k again: the block-sparse form has no packed sequences)
   c.D = a.D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;
@@ -278,6 +286,14 @@ static void pv_skip(AttnArgs& a, const float* pv_thresh, int32_t* skipped) {
 // the forms with per-batch key lengths: batch b attends its keys [0, clamp(kv_lens[b], 0, N))
 static void key_lens(AttnArgs& a, const int32_t* kv_lens) {
   a.key_lens = true; a.kv_lens = kv_lens;
+}
+
+// the block-sparse forms with per-batch key lengths: the lists, the P.V skip iff pv_thresh is given, the lengths
+static void block_sparse_key_lens(AttnArgs& a, const int32_t* block_lists, int64_t block_lists_bytes, const float* pv_thresh,
+                                  int32_t* skipped, const int32_t* kv_lens) {
+  block_sparse(a, block_lists, block_lists_bytes);
+  if (pv_thresh) pv_skip(a, pv_thresh, skipped);
+  a.block_key_lens = true; a.block_kv_lens = kv_lens;
 }
 
 }  // namespace sage
@@ -590,6 +606,74 @@ extern "C" int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, c
   a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
   a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
   key_lens(a, kv_lens);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
+}
+
+// ---- block-sparse attention with per-batch key lengths: the _blocksparse_pvskip twins' arguments, then kv_lens; a NULL
+//      pv_thresh selects the kernel without the P.V skip (skipped is then not read)
+extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
+                                                          int v_dtype, const sage_tensor* o, int o_dtype, const float* q_scale,
+                                                          const float* k_scale, const float* v_mean, float* lse, int B, int Hq,
+                                                          int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
+                                                          int warpq, float sm_scale, int logit_mult_is_one,
+                                                          const int32_t* block_lists, int64_t block_lists_bytes,
+                                                          const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
+                                                          sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                                         const sage_tensor* o, int o_dtype, const float* q_scale,
+                                                         const float* k_scale, const float* v_scale, const float* v_mean,
+                                                         float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
+                                                         int qk_gran, int blkq, int warpq, float sm_scale,
+                                                         int logit_mult_is_one, const int32_t* block_lists,
+                                                         int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                                         const int32_t* kv_lens, sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
+  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
+  a.logit_mult_is_one = logit_mult_is_one;
+  block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_fusedq_pv_f16_blocksparse_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                                         const sage_tensor* v, int v_dtype, const sage_tensor* o, int o_dtype,
+                                                         const float* k_scale, const void* km, const float* v_mean, float* lse,
+                                                         int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
+                                                         int warpq, float sm_scale, const int32_t* block_lists,
+                                                         int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
+                                                         const int32_t* kv_lens, sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
+  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
+  a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
+  if (const int s = fused_q(a, q_dtype, km)) return s;
+  return run_attn(a, stream);
+}
+
+extern "C" int sage_attn_fusedq_pv_f8_blocksparse_kvlen(const sage_tensor* q, int q_dtype, const sage_tensor* k8,
+                                                        const sage_tensor* v_fp8, const sage_tensor* o, int o_dtype,
+                                                        const float* k_scale, const void* km, const float* v_scale,
+                                                        const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N,
+                                                        int D, int is_causal, int qk_gran, int warpq, float sm_scale,
+                                                        const int32_t* block_lists, int64_t block_lists_bytes,
+                                                        const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
+                                                        sage_stream_t stream) {
+  AttnArgs a;
+  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
   if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }

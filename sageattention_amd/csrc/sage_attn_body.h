@@ -1,16 +1,18 @@
 // The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip),
-// attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip) and attn_i8_kvlen_kernel (sage_attn_kvlen.hip), not a header in the
-// usual sense.  Expects in scope: the kernel
+// attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip), attn_i8_kvlen_kernel (sage_attn_kvlen.hip),
+// attn_i8_blocksparse_kvlen_kernel (sage_attn_sparse_kvlen.hip) and attn_i8_blocksparse_pvskip_kvlen_kernel
+// (sage_attn_sparse_kvlen_pvskip.hip), not a header in the usual sense.  Expects in scope: the kernel
 // parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE, PVSKIP, KVLEN
-// (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip).
+// (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip; SPARSE && KVLEN: the tile lists
+// clipped at the batch's length, sage_attn_sparse_kvlen.hip).
 #ifndef SAGE_ATTN_BODY_OF_KERNEL
-#error "sage_attn_body.h is the body of the attention kernels (sage_attn.hip, sage_attn_pvskip.hip, sage_attn_kvlen.hip): included nowhere else"
+#error "sage_attn_body.h is the body of the attention kernels (sage_attn*.hip): included nowhere else"
 #endif
   static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
   static_assert(!HAS_MASK || (!CAUSAL && !PV_FP8), "attn_mask: non-causal 16-bit-PV operator");
   static_assert(!SPARSE || (NWAVES == 4 && !CAUSAL && !HAS_MASK), "block-sparse: 4 waves = one block row of the map, non-causal");
   static_assert(!PVSKIP || SPARSE, "the P.V skip exists in the block-sparse form only");
-  static_assert(!KVLEN || (!SPARSE && !HAS_MASK), "per-batch key lengths: the dense kernel without attn_mask");
+  static_assert(!KVLEN || !HAS_MASK, "per-batch key lengths: the dense or the block-sparse kernel, without attn_mask");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -55,6 +57,8 @@
   // Lightest first measured 1-2 % slower on every causal shape, with more HBM-side reads.
   if constexpr (CAUSAL) qb = p.nqb - 1 - qb;
   const int hk = h / (p.Hq / p.Hk);
+  // the list row (and the skip counters) of the workgroup are those of (b, h): the id itself, but for the batch interleave above
+  const int bh_row = (SPARSE && KVLEN) ? b * p.Hq + h : bh;
   int M_ = p.M, N_ = p.N;
   int64_t q_boff = b * p.qsb, k_boff = b * p.ksb, v_boff = b * p.vsb, o_boff = b * p.osb;
   if (p.cu_q) {  // packed sequences: wave-uniform, before any barrier
@@ -89,12 +93,35 @@
   float pv_thr = 0.f;  // PVSKIP: the head's threshold (sage_attn_*_blocksparse_pvskip), in base-2 logit units below
   (void)pv_thr;
   if constexpr (SPARSE) {
-    bsl = p.bs_lists + ((int64_t)bh * p.nqb + qb) * p.bs_row;
+    bsl = p.bs_lists + ((int64_t)bh_row * p.nqb + qb) * p.bs_row;
     bs_count = uniform_load_i32(bsl);
     if constexpr (PVSKIP) pv_thr = uniform_load1(p.pv_thresh + h);
     ++bsl;
 #pragma unroll
     for (int i = 0; i < 5; ++i) bs_first[i] = uniform_load_i32(bsl + i);
+    if constexpr (KVLEN) {
+      // The list is the caller's, made for N keys and read-only: of a batch that ends earlier only the entries < ntk_b =
+      // ceil(len_b / 64) count, and the list ascends, so they are a prefix.  Its length by a ballot count over the row: every
+      // wave counts for itself (wave uniform, before any barrier), lane l looks at entries l, l + 64, l + 128, l + 192 of a
+      // 256-entry chunk, all four loads in flight together, and the counts are scalar popcounts -- nothing of it lives on into
+      // the loop.  A batch of full length (ntk_b = ceil(N / 64)) does not look.  The entries behind the prefix name real tiles
+      // beyond the length: the blind read-ahead below may copy them -- K comes back as zeros, the descriptor ends with row
+      // len_b - 1 -- but their ring slots belong to list positions >= the clipped count, which no wave computes.
+      const int ntk_b = (N_ + 63) >> 6;
+      if (ntk_b < ((p.N + 63) >> 6)) {
+        const int ln = threadIdx.x & 63;
+        int cnt = 0;
+        for (int base = 0; base < bs_count; base += 256) {
+          int e[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) e[u] = bsl[min(base + 64 * u + ln, bs_count - 1)];
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(base + 64 * u + ln < bs_count && e[u] < ntk_b));
+        }
+        bs_count = cnt;
+      }
+    }
     // an empty q-block: nothing to do here, before any barrier (wave uniform).  Its rows are DEFINED, o = 0 and lse = -inf:
     // attn_blocksparse_empty_kernel writes them.  (Written here, the stores cost the head_dim-64 variants the registers
     // that keep them at three waves per SIMD -- FP8 PV with per-thread scales spilled its bias tuple.)
@@ -1261,5 +1288,5 @@
   // PVSKIP: the wave's count of skipped tiles, one ordinary store by one lane (a wave without a row < M reports 0)
   if constexpr (PVSKIP) {
     if (p.pv_skipped && row_l == q0 && hh_l == 0)
-      p.pv_skipped[((int64_t)bh * p.nqb + qb) * 4 + wave] = pv_rows ? n_skipped : 0;
+      p.pv_skipped[((int64_t)bh_row * p.nqb + qb) * 4 + wave] = pv_rows ? n_skipped : 0;
   }

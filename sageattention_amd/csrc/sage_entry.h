@@ -124,6 +124,11 @@ struct AttnArgs {
   int32_t* pv_skipped = nullptr;
   bool key_lens = false;      // per-batch key lengths: batch b attends its keys [0, clamp(kv_lens[b], 0, N)) (device, int32 [B])
   const int32_t* kv_lens = nullptr;
+  // per-batch key lengths of the BLOCK-SPARSE form (with or without pv_skip): a field of its own.  key_lens above keeps
+  // meaning "the dense kernel with lengths" and stays SAGE_ERR_UNSUPPORTED together with block_sparse; the lists of this form
+  // are clipped at ceil(len_b / 64) tiles by the kernel (sage_attn_sparse_kvlen.hip).  Same tensor: device, int32 [B]
+  bool block_key_lens = false;
+  const int32_t* block_kv_lens = nullptr;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -134,6 +139,7 @@ struct AttnCall {
   bool sparse;  // attn_i8_blocksparse_kernel (always 4 waves)
   bool pvskip;  // ... its twin attn_i8_blocksparse_pvskip_kernel
   bool kvlen;   // attn_i8_kvlen_kernel: the dense kernel with per-batch key lengths
+  bool sparse_kvlen;  // attn_i8_blocksparse_kvlen_kernel / ..._pvskip_kvlen_kernel: sparse (and pvskip) with key lengths
 };
 int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
@@ -141,6 +147,10 @@ int attn_launch(const AttnCall& c, hipStream_t st);
 int launch_blocksparse_pvskip(const AttnCall& c, hipStream_t st);
 // the attention launch of a call with per-batch key lengths (c.kvlen; sage_attn_kvlen.hip): attn_launch goes through it
 int launch_kvlen(const AttnCall& c, hipStream_t st);
+// the launches of a block-sparse call with per-batch key lengths (c.sparse_kvlen; sage_attn_sparse_kvlen.hip): the attention
+// kernel -- with c.pvskip the twin of sage_attn_sparse_kvlen_pvskip.hip, second function -- and the rows of the emptied q-blocks
+int launch_blocksparse_kvlen(const AttnCall& c, hipStream_t st);
+int launch_blocksparse_pvskip_kvlen(const AttnCall& c, hipStream_t st);
 
 // ---- block-sparse tile lists (sage_misc.hip) ---------------------------------------------------------------------------
 // bytes of the lists of one call: a row of block_list_row(N) int32 per (b, h_q, 128-row q-block)

@@ -17,6 +17,13 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_sparge_pv_lse(...) -> (o, lse, skipped)        tensor in, the skip counters out)
     torch.ops.sageattention_amd.attn_kvlen(q, k, v, kv_lens, tensor_layout, is_causal, sm_scale, pv, qk_quant_gran) -> o
     torch.ops.sageattention_amd.attn_kvlen_lse(...) -> (o, lse)           (per-batch key lengths, int32 [B] on the device)
+    torch.ops.sageattention_amd.attn_block_sparse_kvlen(q, k, v, block_map, kv_lens, ...) -> o      (the block-sparse and Sparge
+    torch.ops.sageattention_amd.attn_block_sparse_plan_kvlen(q, k, v, block_lists, plan_shape, kv_lens, ...) -> o    ops with
+    torch.ops.sageattention_amd.attn_block_sparse_pv_kvlen / attn_block_sparse_plan_pv_kvlen(...) -> (o, skipped)   per-batch
+    torch.ops.sageattention_amd.attn_sparge_select_kvlen(q, k, v, simthreshd1, rule_param, rule, keep_first,       key lengths:
+                                                         keep_last, kv_lens, ...) -> o             kv_lens in front of the layout)
+    torch.ops.sageattention_amd.attn_sparge_select_lse_kvlen(...) -> (o, lse)
+    torch.ops.sageattention_amd.attn_sparge_pv_kvlen / attn_sparge_pv_lse_kvlen(..., pvthreshd, kv_lens, ...) -> (o, [lse,] skipped)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -150,12 +157,74 @@ def _(q, k, v, block_lists, plan_shape, pvthreshd, tensor_layout, sm_scale, pv, 
     return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
 
 
+# ... with per-batch key lengths (core.sageattn_block_sparse, kv_lens): ops of their own again, so that the schemas above stay
+# as they are.  kv_lens is the int32 [B] tensor, in front of the layout.
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_kvlen", mutates_args=())
+def attn_block_sparse_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor, kv_lens: torch.Tensor,
+                            tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_block_sparse(q, k, v, block_map, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran, kv_lens=kv_lens).contiguous()
+
+
+@attn_block_sparse_kvlen.register_fake
+def _(q, k, v, block_map, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_plan_kvlen", mutates_args=())
+def attn_block_sparse_plan_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_lists: torch.Tensor,
+                                 plan_shape: Sequence[int], kv_lens: torch.Tensor, tensor_layout: str, sm_scale: float,
+                                 pv: str, qk_quant_gran: str) -> torch.Tensor:
+    plan = core.BlockSparsePlan(block_lists, *(int(x) for x in plan_shape))
+    return core.sageattn_block_sparse(q, k, v, plan, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran, kv_lens=kv_lens).contiguous()
+
+
+@attn_block_sparse_plan_kvlen.register_fake
+def _(q, k, v, block_lists, plan_shape, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_pv_kvlen", mutates_args=())
+def attn_block_sparse_pv_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map: torch.Tensor,
+                               pvthreshd: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str, sm_scale: float, pv: str,
+                               qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, skipped = core.sageattn_block_sparse(q, k, v, block_map, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                            qk_quant_gran=qk_quant_gran, pvthreshd=pvthreshd, return_skipped=True,
+                                            kv_lens=kv_lens)
+    return o.contiguous(), skipped
+
+
+@attn_block_sparse_pv_kvlen.register_fake
+def _(q, k, v, block_map, pvthreshd, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
+@torch.library.custom_op("sageattention_amd::attn_block_sparse_plan_pv_kvlen", mutates_args=())
+def attn_block_sparse_plan_pv_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_lists: torch.Tensor,
+                                    plan_shape: Sequence[int], pvthreshd: torch.Tensor, kv_lens: torch.Tensor,
+                                    tensor_layout: str, sm_scale: float, pv: str,
+                                    qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    plan = core.BlockSparsePlan(block_lists, *(int(x) for x in plan_shape))
+    o, skipped = core.sageattn_block_sparse(q, k, v, plan, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                            qk_quant_gran=qk_quant_gran, pvthreshd=pvthreshd, return_skipped=True,
+                                            kv_lens=kv_lens)
+    return o.contiguous(), skipped
+
+
+@attn_block_sparse_plan_pv_kvlen.register_fake
+def _(q, k, v, block_lists, plan_shape, pvthreshd, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
 def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_map,
                                      tensor_layout: str = "HND", sm_scale: Optional[float] = None, pv: str = "fp16",
-                                     qk_quant_gran: str = "per_thread", pvthreshd=None, return_skipped: bool = False):
+                                     qk_quant_gran: str = "per_thread", pvthreshd=None, return_skipped: bool = False,
+                                     kv_lens: Optional[torch.Tensor] = None):
     """``sageattn_block_sparse`` (core.py) as a traceable custom op; ``block_map`` is the map tensor or a plan.  With
     ``pvthreshd`` (a float > 0 or an fp32 tensor [Hq]) it calls the ``_pv`` ops, and ``return_skipped`` appends the skip
-    counters; without it the ops it has always called."""
+    counters; without it the ops it has always called.  With ``kv_lens`` (int32 [B], per-batch key lengths) the ``_kvlen``
+    twin of the op it would call without."""
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
     core._check_pvskip_args(pvthreshd, return_skipped)
@@ -163,6 +232,17 @@ def sageattn_block_sparse_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.
         sm_scale = q.size(-1) ** -0.5
     ns, tail = torch.ops.sageattention_amd, (tensor_layout, float(sm_scale), pv, qk_quant_gran)
     is_plan = isinstance(block_map, core.BlockSparsePlan)
+    if kv_lens is not None:
+        if pvthreshd is not None:
+            thr = _as_per_head(pvthreshd, q, tensor_layout)
+            if is_plan:
+                o, skipped = ns.attn_block_sparse_plan_pv_kvlen(q, k, v, *_plan_args(block_map), thr, kv_lens, *tail)
+            else:
+                o, skipped = ns.attn_block_sparse_pv_kvlen(q, k, v, block_map, thr, kv_lens, *tail)
+            return (o, skipped) if return_skipped else o
+        if is_plan:
+            return ns.attn_block_sparse_plan_kvlen(q, k, v, *_plan_args(block_map), kv_lens, *tail)
+        return ns.attn_block_sparse_kvlen(q, k, v, block_map, kv_lens, *tail)
     if pvthreshd is not None:
         thr = _as_per_head(pvthreshd, q, tensor_layout)
         if is_plan:
@@ -269,15 +349,84 @@ def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, 
     return q.new_empty(q.shape), _lse_like(q, tensor_layout), _skipped_like(q, tensor_layout)
 
 
+# ... with per-batch key lengths (core.sageattn_sparge, kv_lens): the attn_sparge_select and attn_sparge_pv pairs again, kv_lens
+# (int32 [B]) in front of the layout
+@torch.library.custom_op("sageattention_amd::attn_sparge_select_kvlen", mutates_args=())
+def attn_sparge_select_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor,
+                             rule_param: torch.Tensor, rule: str, keep_first: int, keep_last: int, kv_lens: torch.Tensor,
+                             tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                qk_quant_gran=qk_quant_gran, keep_first=keep_first, keep_last=keep_last, kv_lens=kv_lens,
+                                **_select_kwargs(rule_param, rule)).contiguous()
+
+
+@attn_sparge_select_kvlen.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_select_lse_kvlen", mutates_args=())
+def attn_sparge_select_lse_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor,
+                                 rule_param: torch.Tensor, rule: str, keep_first: int, keep_last: int, kv_lens: torch.Tensor,
+                                 tensor_layout: str, sm_scale: float, pv: str,
+                                 qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                  qk_quant_gran=qk_quant_gran, return_lse=True, keep_first=keep_first, keep_last=keep_last,
+                                  kv_lens=kv_lens, **_select_kwargs(rule_param, rule))
+    return o.contiguous(), lse
+
+
+@attn_sparge_select_lse_kvlen.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, kv_lens, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_pv_kvlen", mutates_args=())
+def attn_sparge_pv_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor, rule_param: torch.Tensor,
+                         rule: str, keep_first: int, keep_last: int, pvthreshd: torch.Tensor, kv_lens: torch.Tensor,
+                         tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, skipped = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale, pv=pv,
+                                      qk_quant_gran=qk_quant_gran, keep_first=keep_first, keep_last=keep_last,
+                                      pvthreshd=pvthreshd, return_skipped=True, kv_lens=kv_lens,
+                                      **_select_kwargs(rule_param, rule))
+    return o.contiguous(), skipped
+
+
+@attn_sparge_pv_kvlen.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, kv_lens, tensor_layout, sm_scale, pv,
+      qk_quant_gran):
+    return q.new_empty(q.shape), _skipped_like(q, tensor_layout)
+
+
+@torch.library.custom_op("sageattention_amd::attn_sparge_pv_lse_kvlen", mutates_args=())
+def attn_sparge_pv_lse_kvlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, simthreshd1: torch.Tensor,
+                             rule_param: torch.Tensor, rule: str, keep_first: int, keep_last: int, pvthreshd: torch.Tensor,
+                             kv_lens: torch.Tensor, tensor_layout: str, sm_scale: float, pv: str,
+                             qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    o, lse, skipped = core.sageattn_sparge(q, k, v, tensor_layout=tensor_layout, simthreshd1=simthreshd1, sm_scale=sm_scale,
+                                           pv=pv, qk_quant_gran=qk_quant_gran, return_lse=True, keep_first=keep_first,
+                                           keep_last=keep_last, pvthreshd=pvthreshd, return_skipped=True, kv_lens=kv_lens,
+                                           **_select_kwargs(rule_param, rule))
+    return o.contiguous(), lse, skipped
+
+
+@attn_sparge_pv_lse_kvlen.register_fake
+def _(q, k, v, simthreshd1, rule_param, rule, keep_first, keep_last, pvthreshd, kv_lens, tensor_layout, sm_scale, pv,
+      qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout), _skipped_like(q, tensor_layout)
+
+
 def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
                                simthreshd1=0.6, cdfthreshd=0.98, sm_scale: Optional[float] = None, pv: str = "fp16",
                                qk_quant_gran: str = "per_thread", return_lse: bool = False, topk=None,
-                               keep_first: int = 0, keep_last: int = 0, pvthreshd=None, return_skipped: bool = False):
+                               keep_first: int = 0, keep_last: int = 0, pvthreshd=None, return_skipped: bool = False,
+                               kv_lens: Optional[torch.Tensor] = None):
     """``sageattn_sparge`` (core.py) as a traceable custom op; thresholds and ``topk`` are floats or fp32 tensors [Hq].
     With ``topk`` the budget rule is used and ``cdfthreshd`` is not read; ``keep_first`` / ``keep_last`` pin key blocks on.
     Without any of the three it calls ``attn_sparge`` / ``attn_sparge_lse`` as before, otherwise the ``attn_sparge_select``
     pair.  With ``pvthreshd`` (a float > 0 or an fp32 tensor [Hq]) it calls the ``attn_sparge_pv`` pair, and
-    ``return_skipped`` appends the skip counters: o, lse, skipped."""
+    ``return_skipped`` appends the skip counters: o, lse, skipped.  With ``kv_lens`` (int32 [B], per-batch key lengths) it
+    calls the ``_kvlen`` twins of the ``attn_sparge_select`` and ``attn_sparge_pv`` pairs."""
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
     core._check_select_args(topk, keep_first, keep_last)
@@ -286,6 +435,17 @@ def sageattn_sparge_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
         sm_scale = q.size(-1) ** -0.5
     rule, par = ("cdf", cdfthreshd) if topk is None else ("topk", topk)
     thr, par = _as_per_head(simthreshd1, q, tensor_layout), _as_per_head(par, q, tensor_layout)
+    ns = torch.ops.sageattention_amd
+    if kv_lens is not None:
+        tail = (kv_lens, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+        if pvthreshd is not None:
+            pvt = _as_per_head(pvthreshd, q, tensor_layout)
+            op = ns.attn_sparge_pv_lse_kvlen if return_lse else ns.attn_sparge_pv_kvlen
+            out = op(q, k, v, thr, par, rule, keep_first, keep_last, pvt, *tail)
+            out = out if return_skipped else out[:-1]
+            return out if len(out) > 1 else out[0]
+        op = ns.attn_sparge_select_lse_kvlen if return_lse else ns.attn_sparge_select_kvlen
+        return op(q, k, v, thr, par, rule, keep_first, keep_last, *tail)
     if pvthreshd is not None:
         pvt = _as_per_head(pvthreshd, q, tensor_layout)
         op = torch.ops.sageattention_amd.attn_sparge_pv_lse if return_lse else torch.ops.sageattention_amd.attn_sparge_pv

@@ -65,18 +65,25 @@ def k_mean(k: torch.Tensor, tensor_layout: str = "HND") -> torch.Tensor:
     return km
 
 
-def block_pool_sim(x: torch.Tensor, blk: int, tensor_layout: str = "HND", mean: Optional[torch.Tensor] = None):
+def block_pool_sim(x: torch.Tensor, blk: int, tensor_layout: str = "HND", mean: Optional[torch.Tensor] = None,
+                   kv_lens: Optional[torch.Tensor] = None):
     """Block statistics of the block-map predictor (sage_block_pool_sim): per block of ``blk`` (64 | 128) rows of ``x - mean``
     the mean row, fp32 [B,H,ceil(N/blk),D], and the mean pairwise cosine similarity of its rows, fp32 [B,H,ceil(N/blk)].
-    ``mean``: optional [B,H,D] in x's dtype (the smoothing mean of K)."""
+    ``mean``: optional [B,H,D] in x's dtype (the smoothing mean of K).  With ``kv_lens`` (int32 [B] on x's device;
+    sage_block_pool_sim_kvlen) batch b ends with row ``clamp(kv_lens[b], 0, N) - 1``: its last block is pooled over its valid
+    rows, rows beyond are never loaded and the statistics of blocks wholly beyond are unspecified."""
     B, H, N, D = L.dims(x, tensor_layout)
     nb = (N + blk - 1) // blk
     if mean is not None and (tuple(mean.shape) != (B, H, D) or mean.dtype != x.dtype or not mean.is_contiguous()):
         raise ValueError(f"mean must be a contiguous [B={B}, H={H}, D={D}] tensor of dtype {x.dtype}")
     pooled = torch.empty((B, H, nb, D), dtype=torch.float32, device=x.device)
     sim = torch.empty((B, H, nb), dtype=torch.float32, device=x.device)
-    L.check(L.lib().sage_block_pool_sim(L.desc(x, tensor_layout), L.dtype_code(x.dtype), B, H, N, D, blk, L.ptr(mean),
-                                        pooled.data_ptr(), sim.data_ptr(), L.stream_ptr(x.device)), "sage_block_pool_sim")
+    args = (L.desc(x, tensor_layout), L.dtype_code(x.dtype), B, H, N, D, blk, L.ptr(mean), pooled.data_ptr(), sim.data_ptr())
+    if kv_lens is None:
+        L.check(L.lib().sage_block_pool_sim(*args, L.stream_ptr(x.device)), "sage_block_pool_sim")
+    else:
+        L.check(L.lib().sage_block_pool_sim_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(x.device)),
+                "sage_block_pool_sim_kvlen")
     return pooled, sim
 
 

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 device code of two builds function by function: do the kernels a change was not meant to touch keep
+their instruction streams?
+
+    python tools/cmp_kernel_disasm.py OLD NEW [--filter REGEX]
+
+OLD and NEW are object files (sage_attn.o ...) or directories of them (csrc/ of two builds; objects are matched by name).
+Every device function is disassembled (llvm-objdump -d, no raw bytes), addresses and branch-target labels are dropped, and the
+remaining text -- mnemonics, registers, immediates, in order -- is compared.  Prints one line per object with the number of
+identical functions and names every function that differs or exists on one side only; exit status 1 if any differs."""
+import argparse
+import glob
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sageattention_amd import _build  # noqa: E402
+
+OBJDUMP = os.path.join(os.path.dirname(os.path.dirname(_build.HIPCC)), "lib", "llvm", "bin", "llvm-objdump")
+
+
+def functions(obj):
+    """{mangled name: [normalised instruction text]} of the gfx950 code object inside ``obj``"""
+    tmp = tempfile.mkdtemp(prefix="sage_dis_")
+    try:
+        local = os.path.join(tmp, "o.o")
+        shutil.copy(obj, local)
+        subprocess.run([OBJDUMP, "--offloading", local], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+        dev = glob.glob(local + ".*" + _build.ARCH)
+        if not dev:  # host code only (sage_op.o)
+            return {}
+        text = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", dev[0]], stdout=subprocess.PIPE, text=True, check=True).stdout
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    out, name = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <([^>]+)>:$", line)
+        if m:
+            name = m.group(1)
+            if not name.startswith("L"):  # a function, not a local label
+                out[name] = []
+                cur = out[name]
+            continue
+        if name is None or not line.strip():
+            continue
+        ins = re.sub(r"^\s*[0-9a-f]+:\s*", "", line)      # address column
+        ins = re.sub(r"//.*$", "", ins).strip()            # objdump's comment (address, encoding)
+        ins = re.sub(r"<[^>]+>", "<label>", ins)           # branch targets by name
+        if ins:
+            cur.append(ins)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--filter", default="", help="only functions whose mangled name matches this regex")
+    a = ap.parse_args()
+    if os.path.isdir(a.old):
+        names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(a.old, "*.o")))
+        pairs = [(os.path.join(a.old, n), os.path.join(a.new, n)) for n in names if os.path.exists(os.path.join(a.new, n))]
+    else:
+        pairs = [(a.old, a.new)]
+    bad = 0
+    for old, new in pairs:
+        fo, fn = functions(old), functions(new)
+        keep = [n for n in sorted(set(fo) | set(fn)) if re.search(a.filter, n)]
+        same = [n for n in keep if n in fo and n in fn and fo[n] == fn[n]]
+        print(f"{os.path.basename(old)}: {len(same)} of {len(keep)} functions identical "
+              f"({sum(len(fo[n]) for n in same)} instructions)")
+        for n in keep:
+            if n in same:
+                continue
+            bad += n in fo and n in fn
+            what = "only in OLD" if n not in fn else "only in NEW" if n not in fo else \
+                f"DIFFERS ({len(fo[n])} -> {len(fn[n])} instructions)"
+            print(f"  {n}: {what}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
