@@ -265,12 +265,52 @@ static int run_attn(const AttnArgs& a, sage_stream_t stream) {
   return attn_launch(c, (hipStream_t)stream);
 }
 
-// the fused-Q forms: q is the fp16 / bf16 query tensor, km the k_mean of the LSE correction; 128-row q-blocks, and the
-// kernel applies sm_scale
-static int fused_q(AttnArgs& a, int q_dtype, const void* km) {
-  if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
-  a.q_dtype = q_dtype; a.km = km; a.blkq = 128; a.logit_mult_is_one = 0;
-  return SAGE_OK;
+// The argument block of an entry point, filled from what the forms of its family share: {INT8 Q, fused Q} x {FP16 / BF16 V,
+// FP8 V}.  Parameters in the order of the C signatures.  The one fill is that of INT8 Q with FP16 / BF16 V; the other three
+// families go through it and add what is theirs.
+static AttnArgs int8_f16_args(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v, int v_dtype, const sage_tensor* o,
+                              int o_dtype, const float* q_scale, const float* k_scale, const float* v_mean, float* lse, int B,
+                              int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq, int warpq,
+                              float sm_scale, int logit_mult_is_one) {
+  AttnArgs a;
+  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
+  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
+  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  return a;
+}
+
+// FP8 V: v is the FP8 V^T (v_dtype keeps its default), v_scale its scales
+static AttnArgs int8_f8_args(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v_fp8, const sage_tensor* o,
+                             int o_dtype, const float* q_scale, const float* k_scale, const float* v_scale, const float* v_mean,
+                             float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
+                             int warpq, float sm_scale, int logit_mult_is_one) {
+  AttnArgs a = int8_f16_args(q8, k8, v_fp8, SAGE_F16, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
+  a.pv_fp8 = true; a.v_scale = v_scale;
+  return a;
+}
+
+// the fused-Q forms: q is the fp16 / bf16 query tensor (no q_scale), km the k_mean of the LSE correction; 128-row q-blocks,
+// and the kernel applies sm_scale.  `status` is that of q_dtype: an entry point returns it, if not SAGE_OK, before it goes on
+static AttnArgs fusedq_f16_args(int& status, const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
+                                int qk_gran, int warpq, float sm_scale) {
+  AttnArgs a = int8_f16_args(q, k8, v, v_dtype, o, o_dtype, nullptr, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal, qk_gran,
+                             128, warpq, sm_scale, 0);
+  a.q_dtype = q_dtype; a.km = km;
+  status = q_dtype != SAGE_F16 && q_dtype != SAGE_BF16 ? SAGE_ERR_INVALID_ARGUMENT : SAGE_OK;
+  return a;
+}
+
+static AttnArgs fusedq_f8_args(int& status, const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
+                               const sage_tensor* o, int o_dtype, const float* k_scale, const void* km, const float* v_scale,
+                               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int is_causal,
+                               int qk_gran, int warpq, float sm_scale) {
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v_fp8, SAGE_F16, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  a.pv_fp8 = true; a.v_scale = v_scale;
+  return a;
 }
 
 // the block-sparse forms: the tile lists of sage_block_map_compact
@@ -319,10 +359,8 @@ extern "C" int sage_attn_qk_int8_pv_f16(const sage_tensor* q8, const sage_tensor
                                         const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                         int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                         int logit_mult_is_one, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   return run_attn(a, stream);
 }
 
@@ -331,11 +369,8 @@ extern "C" int sage_attn_qk_int8_pv_f8(const sage_tensor* q8, const sage_tensor*
                                        const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                        int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                        int logit_mult_is_one, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
-  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                            qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   return run_attn(a, stream);
 }
 
@@ -345,11 +380,9 @@ extern "C" int sage_attn_qk_int8_pv_f16_varlen(const sage_tensor* q8, const sage
                                                int max_seqlen_q, int max_seqlen_k, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!cu_seqlens_q || !cu_seqlens_k) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k; a.B = num_seqs; a.Hq = Hq; a.Hk = Hk; a.M = max_seqlen_q; a.N = max_seqlen_k;
-  a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, /*v_mean*/ nullptr, /*lse*/ nullptr, num_seqs, Hq,
+                             Hk, max_seqlen_q, max_seqlen_k, D, is_causal, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
+  a.cu_q = cu_seqlens_q; a.cu_k = cu_seqlens_k;
   return run_attn(a, stream);
 }
 
@@ -357,11 +390,10 @@ extern "C" int sage_attn_fusedq_pv_f16(const sage_tensor* q, int q_dtype, const 
                                        const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
                                        const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                        int is_causal, int qk_gran, int warpq, float sm_scale, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.warpq = warpq; a.sm_scale = sm_scale;
-  if (const int s = fused_q(a, q_dtype, km)) return s;
+  int status;
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v, v_dtype, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   return run_attn(a, stream);
 }
 
@@ -370,11 +402,10 @@ extern "C" int sage_attn_fusedq_pv_f8(const sage_tensor* q, int q_dtype, const s
                                       const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                       int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                       sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
-  if (const int s = fused_q(a, q_dtype, km)) return s;
+  int status;
+  AttnArgs a = fusedq_f8_args(status, q, q_dtype, k8, v_fp8, o, o_dtype, k_scale, km, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                              is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   return run_attn(a, stream);
 }
 
@@ -384,11 +415,9 @@ extern "C" int sage_attn_qk_int8_pv_f16_masked(const sage_tensor* q8, const sage
                                                int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
                                                float sm_scale, int logit_mult_is_one, sage_stream_t stream) {
   if (!attn_mask) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq;
-  a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one; a.mask = attn_mask; a.mask_kind = mask_kind;
-  a.mask_strides = mask_strides;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, /*v_mean*/ nullptr, lse, B, Hq, Hk, M, N, D,
+                             /*is_causal*/ 0, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
+  a.mask = attn_mask; a.mask_kind = mask_kind; a.mask_strides = mask_strides;
   return run_attn(a, stream);
 }
 
@@ -398,10 +427,9 @@ extern "C" int sage_attn_qk_int8_pv_f16_kvtiles(const sage_tensor* q8, const sag
                                                 int N, int D, int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                                 sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.kvl = kv_layout;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, /*v_mean*/ nullptr, lse, B, Hq, Hk, M, N, D,
+                             is_causal, qk_gran, blkq, warpq, sm_scale, /*logit_mult_is_one*/ 0);
+  a.kvl = kv_layout;
   return run_attn(a, stream);
 }
 
@@ -411,10 +439,9 @@ extern "C" int sage_attn_qk_int8_pv_f8_kvtiles(const sage_tensor* q8, const sage
                                                int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran, int blkq,
                                                int warpq, float sm_scale, sage_stream_t stream) {
   if (!kv_layout) return SAGE_ERR_INVALID_ARGUMENT;
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.kvl = kv_layout;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, /*v_mean*/ nullptr, lse, B, Hq, Hk, M, N, D,
+                            is_causal, qk_gran, blkq, warpq, sm_scale, /*logit_mult_is_one*/ 0);
+  a.kvl = kv_layout;
   return run_attn(a, stream);
 }
 
@@ -426,10 +453,8 @@ extern "C" int sage_attn_qk_int8_pv_f16_blocksparse(const sage_tensor* q8, const
                                                     int warpq, float sm_scale, int logit_mult_is_one,
                                                     const int32_t* block_lists, int64_t block_lists_bytes,
                                                     sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse(a, block_lists, block_lists_bytes);
   return run_attn(a, stream);
 }
@@ -441,11 +466,8 @@ extern "C" int sage_attn_qk_int8_pv_f8_blocksparse(const sage_tensor* q8, const 
                                                    int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
                                                    const int32_t* block_lists, int64_t block_lists_bytes,
                                                    sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
-  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                            qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse(a, block_lists, block_lists_bytes);
   return run_attn(a, stream);
 }
@@ -456,12 +478,11 @@ extern "C" int sage_attn_fusedq_pv_f16_blocksparse(const sage_tensor* q, int q_d
                                                    int B, int Hq, int Hk, int M, int N, int D, int is_causal, int qk_gran,
                                                    int warpq, float sm_scale, const int32_t* block_lists,
                                                    int64_t block_lists_bytes, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v, v_dtype, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse(a, block_lists, block_lists_bytes);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -472,12 +493,11 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse(const sage_tensor* q, int q_dt
                                                   int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                                   const int32_t* block_lists, int64_t block_lists_bytes,
                                                   sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f8_args(status, q, q_dtype, k8, v_fp8, o, o_dtype, k_scale, km, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                              is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse(a, block_lists, block_lists_bytes);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -490,10 +510,8 @@ extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_pvskip(const sage_tensor* q8
                                                            int logit_mult_is_one, const int32_t* block_lists,
                                                            int64_t block_lists_bytes, const float* pv_thresh,
                                                            int32_t* skipped, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse(a, block_lists, block_lists_bytes);
   pv_skip(a, pv_thresh, skipped);
   return run_attn(a, stream);
@@ -507,11 +525,8 @@ extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_pvskip(const sage_tensor* q8,
                                                           float sm_scale, int logit_mult_is_one, const int32_t* block_lists,
                                                           int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                           sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
-  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                            qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse(a, block_lists, block_lists_bytes);
   pv_skip(a, pv_thresh, skipped);
   return run_attn(a, stream);
@@ -525,13 +540,12 @@ extern "C" int sage_attn_fusedq_pv_f16_blocksparse_pvskip(const sage_tensor* q, 
                                                           float sm_scale, const int32_t* block_lists,
                                                           int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                           sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v, v_dtype, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse(a, block_lists, block_lists_bytes);
   pv_skip(a, pv_thresh, skipped);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -543,13 +557,12 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse_pvskip(const sage_tensor* q, i
                                                          float sm_scale, const int32_t* block_lists,
                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                          sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f8_args(status, q, q_dtype, k8, v_fp8, o, o_dtype, k_scale, km, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                              is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse(a, block_lists, block_lists_bytes);
   pv_skip(a, pv_thresh, skipped);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -559,10 +572,8 @@ extern "C" int sage_attn_qk_int8_pv_f16_kvlen(const sage_tensor* q8, const sage_
                                               const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
                                               int is_causal, int qk_gran, int blkq, int warpq, float sm_scale,
                                               int logit_mult_is_one, const int32_t* kv_lens, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   key_lens(a, kv_lens);
   return run_attn(a, stream);
 }
@@ -573,11 +584,8 @@ extern "C" int sage_attn_qk_int8_pv_f8_kvlen(const sage_tensor* q8, const sage_t
                                              int M, int N, int D, int is_causal, int qk_gran, int blkq, int warpq,
                                              float sm_scale, int logit_mult_is_one, const int32_t* kv_lens,
                                              sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
-  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                            qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   key_lens(a, kv_lens);
   return run_attn(a, stream);
 }
@@ -587,12 +595,11 @@ extern "C" int sage_attn_fusedq_pv_f16_kvlen(const sage_tensor* q, int q_dtype, 
                                              const void* km, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
                                              int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                              const int32_t* kv_lens, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v, v_dtype, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   key_lens(a, kv_lens);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -601,12 +608,11 @@ extern "C" int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, c
                                             const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk,
                                             int M, int N, int D, int is_causal, int qk_gran, int warpq, float sm_scale,
                                             const int32_t* kv_lens, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f8_args(status, q, q_dtype, k8, v_fp8, o, o_dtype, k_scale, km, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                              is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   key_lens(a, kv_lens);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -620,10 +626,8 @@ extern "C" int sage_attn_qk_int8_pv_f16_blocksparse_kvlen(const sage_tensor* q8,
                                                           const int32_t* block_lists, int64_t block_lists_bytes,
                                                           const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
                                                           sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale; a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f16_args(q8, k8, v, v_dtype, o, o_dtype, q_scale, k_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                             qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
   return run_attn(a, stream);
 }
@@ -636,11 +640,8 @@ extern "C" int sage_attn_qk_int8_pv_f8_blocksparse_kvlen(const sage_tensor* q8, 
                                                          int logit_mult_is_one, const int32_t* block_lists,
                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                          const int32_t* kv_lens, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q8; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.q_scale = q_scale; a.k_scale = k_scale;
-  a.v_scale = v_scale; a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D;
-  a.is_causal = is_causal; a.qk_gran = qk_gran; a.blkq = blkq; a.warpq = warpq; a.sm_scale = sm_scale;
-  a.logit_mult_is_one = logit_mult_is_one;
+  AttnArgs a = int8_f8_args(q8, k8, v_fp8, o, o_dtype, q_scale, k_scale, v_scale, v_mean, lse, B, Hq, Hk, M, N, D, is_causal,
+                            qk_gran, blkq, warpq, sm_scale, logit_mult_is_one);
   block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
   return run_attn(a, stream);
 }
@@ -652,12 +653,11 @@ extern "C" int sage_attn_fusedq_pv_f16_blocksparse_kvlen(const sage_tensor* q, i
                                                          int warpq, float sm_scale, const int32_t* block_lists,
                                                          int64_t block_lists_bytes, const float* pv_thresh, int32_t* skipped,
                                                          const int32_t* kv_lens, sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_mean = v_mean;
-  a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal; a.qk_gran = qk_gran;
-  a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f16_args(status, q, q_dtype, k8, v, v_dtype, o, o_dtype, k_scale, km, v_mean, lse, B, Hq, Hk, M, N, D,
+                               is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }
 
@@ -669,11 +669,10 @@ extern "C" int sage_attn_fusedq_pv_f8_blocksparse_kvlen(const sage_tensor* q, in
                                                         const int32_t* block_lists, int64_t block_lists_bytes,
                                                         const float* pv_thresh, int32_t* skipped, const int32_t* kv_lens,
                                                         sage_stream_t stream) {
-  AttnArgs a;
-  a.q = q; a.k8 = k8; a.v = v_fp8; a.pv_fp8 = true; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale; a.v_scale = v_scale;
-  a.v_mean = v_mean; a.lse = lse; a.B = B; a.Hq = Hq; a.Hk = Hk; a.M = M; a.N = N; a.D = D; a.is_causal = is_causal;
-  a.qk_gran = qk_gran; a.warpq = warpq; a.sm_scale = sm_scale;
+  int status;
+  AttnArgs a = fusedq_f8_args(status, q, q_dtype, k8, v_fp8, o, o_dtype, k_scale, km, v_scale, v_mean, lse, B, Hq, Hk, M, N, D,
+                              is_causal, qk_gran, warpq, sm_scale);
+  if (status) return status;
   block_sparse_key_lens(a, block_lists, block_lists_bytes, pv_thresh, skipped, kv_lens);
-  if (const int s = fused_q(a, q_dtype, km)) return s;
   return run_attn(a, stream);
 }

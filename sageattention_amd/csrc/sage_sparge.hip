@@ -7,6 +7,9 @@
 //                           prefix that holds cdfthreshd of their softmax mass; TOPK: the topk fraction of them with the
 //                           greatest scores -- written as the tile list the block-sparse attention kernels read (and
 //                           optionally as a map).
+// Each kernel is one text with a template flag KVLEN for the forms with per-batch key lengths (sage_block_pool_sim_kvlen,
+// sage_block_select_kvlen): `if constexpr (KVLEN)` at the few points where a length changes the walk, nothing of it in the
+// instantiations without.
 // The rule itself is stated in include/sageattn_hip.h.
 #include "sage_entry.h"
 
@@ -55,6 +58,7 @@ struct PoolParams {
   float* sim;            // [B,H,nblk]
   int H, N, nblk;
   int per_wg, chunks;    // blocks per workgroup, workgroups per head
+  const int32_t* kv_lens;  // KVLEN only (else null): int32 [B], batch b has the rows < clamp(kv_lens[b], 0, N)
 };
 
 // A workgroup walks per_wg consecutive blocks of one head.  D/8 threads hold a row (16 bytes each), 256/(D/8) rows per pass,
@@ -64,7 +68,9 @@ struct PoolParams {
 // Summation order (fixed, so results are deterministic): a row's squared norm over the 8 channels of a thread and then
 // over the row's lanes; a channel's sums over a thread's NP rows, then over the RPP thread rows in LDS; sim over the 64
 // lanes of wave 0.  Zero rows (past the end, or a zero vector) add exact zeros.
-template <int D, int BLK, bool BF16>
+// KVLEN (sage_block_pool_sim_kvlen): the same walk, with the end of batch b at its length len_b instead of N.  The grid and
+// the output layout stay those of N.
+template <int D, int BLK, bool BF16, bool KVLEN>
 __global__ __launch_bounds__(256) void block_pool_sim_kernel(const PoolParams p) {
   constexpr int TPR = D / 8, RPP = 256 / TPR, NP = BLK / RPP;
   static_assert(NP >= 1, "block too small");
@@ -78,92 +84,18 @@ __global__ __launch_bounds__(256) void block_pool_sim_kernel(const PoolParams p)
   const uint16_t* xbase = p.x + b * p.sb + h * p.sh + tc * 8;
   float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (p.mean) unpack8<BF16>(*reinterpret_cast<const uint4*>(p.mean + bh * D + tc * 8), m);
-  const int blk0 = chunk * p.per_wg, blk1 = min(blk0 + p.per_wg, p.nblk);  // the host launches no empty workgroup
-  const int last = p.N - 1;
-  uint4 raw[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i)
-    raw[i] = *reinterpret_cast<const uint4*>(xbase + (int64_t)min(blk0 * BLK + i * RPP + tr, last) * p.sn);
-  for (int blk = blk0; blk < blk1; ++blk) {
-    float f[NP][8];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      unpack8<BF16>(raw[i], f[i]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[i][j] -= m[j];
-    }
-    if (blk + 1 < blk1) {
-#pragma unroll
-      for (int i = 0; i < NP; ++i)
-        raw[i] = *reinterpret_cast<const uint4*>(xbase + (int64_t)min((blk + 1) * BLK + i * RPP + tr, last) * p.sn);
-    }
-    float accx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, accu[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool valid = blk * BLK + i * RPP + tr <= last;
-      float nsq = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) nsq = __builtin_fmaf(f[i][j], f[i][j], nsq);
-      nsq = row_lanes_sum<TPR>(nsq);
-      const float inv = valid && nsq > 0.f ? rsqrtf(nsq) : 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        accx[j] += valid ? f[i][j] : 0.f;
-        accu[j] = __builtin_fmaf(f[i][j], inv, accu[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[0][tr][tc * 8 + j] = accx[j];
-      red[1][tr][tc * 8 + j] = accu[j];
-    }
-    __syncthreads();
-    const int c = min(BLK, p.N - blk * BLK);
-    const int64_t oblk = bh * p.nblk + blk;
-    if (threadIdx.x < 2 * D) {  // the first D threads finish the mean, the next D the sum of unit rows
-      const int which = threadIdx.x / D, d = threadIdx.x % D;
-      float s = 0.f;
-      for (int r = 0; r < RPP; ++r) s += red[which][r][d];  // fixed order
-      if (which == 0) p.pooled[oblk * D + d] = s / (float)c;
-      else ssum[d] = s;
-    }
-    __syncthreads();  // also: every read of `red` is done before the next block's writes
-    if (threadIdx.x < 64) {
-      float v = ssum[threadIdx.x] * ssum[threadIdx.x];
-      if constexpr (D == 128) v = __builtin_fmaf(ssum[threadIdx.x + 64], ssum[threadIdx.x + 64], v);
-      v = wave_sum(v);
-      if (threadIdx.x == 0) p.sim[oblk] = v / (float)(c * c);
-    }
-    // wave 0 reads ssum before it arrives at the next block's first barrier; the others write it only behind that barrier
-  }
-}
-
-// block_pool_sim_kernel with per-batch lengths (sage_block_pool_sim_kvlen): the same walk, with the end of batch b at its length
-// len_b instead of N -- the ragged block is the one that holds row len_b - 1, rows beyond it are never loaded (the row clamp goes
-// to len_b - 1), and the blocks wholly beyond it are left alone (workgroup uniform: the loop ends in front of the first of them).
-// The grid and the output layout stay those of N.  A kernel of its own: block_pool_sim_kernel keeps its text and its code.
-struct PoolLenParams : PoolParams {
-  const int32_t* kv_lens;  // int32 [B], batch b has the rows < clamp(kv_lens[b], 0, N)
-};
-template <int D, int BLK, bool BF16>
-__global__ __launch_bounds__(256) void block_pool_sim_kvlen_kernel(const PoolLenParams p) {
-  constexpr int TPR = D / 8, RPP = 256 / TPR, NP = BLK / RPP;
-  static_assert(NP >= 1, "block too small");
-  __shared__ float red[2][RPP][D + 1];
-  __shared__ float ssum[D];
-  const int chunk = (int)(blockIdx.x % (unsigned)p.chunks);
-  const int64_t bh = blockIdx.x / (unsigned)p.chunks;
-  const int h = (int)(bh % p.H);
-  const int64_t b = bh / p.H;
-  const int tr = threadIdx.x / TPR, tc = threadIdx.x % TPR;
-  const uint16_t* xbase = p.x + b * p.sb + h * p.sh + tc * 8;
-  float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (p.mean) unpack8<BF16>(*reinterpret_cast<const uint4*>(p.mean + bh * D + tc * 8), m);
-  const int N_ = min(max(p.kv_lens[b], 0), p.N);  // len_b
+  int nrows = p.N;
+  if constexpr (KVLEN) nrows = min(max(p.kv_lens[b], 0), p.N);  // len_b
   const int blk0 = chunk * p.per_wg;  // the host launches no empty workgroup
-  const int blk1 = min(min(blk0 + p.per_wg, p.nblk), (N_ + BLK - 1) / BLK);
-  if (blk0 >= blk1) return;  // all of this workgroup's blocks lie beyond the length (len_b == 0: every workgroup of b)
-  const int last = N_ - 1;
+  int blk1 = min(blk0 + p.per_wg, p.nblk);
+  if constexpr (KVLEN) {
+    // the ragged block is the one that holds row len_b - 1, rows beyond it are never loaded (the row clamp goes to
+    // len_b - 1), and the blocks wholly beyond it are left alone (workgroup uniform, in front of the first barrier;
+    // len_b == 0: every workgroup of b)
+    blk1 = min(blk1, (nrows + BLK - 1) / BLK);
+    if (blk0 >= blk1) return;
+  }
+  const int last = nrows - 1;
   uint4 raw[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i)
@@ -202,7 +134,7 @@ __global__ __launch_bounds__(256) void block_pool_sim_kvlen_kernel(const PoolLen
       red[1][tr][tc * 8 + j] = accu[j];
     }
     __syncthreads();
-    const int c = min(BLK, N_ - blk * BLK);
+    const int c = min(BLK, nrows - blk * BLK);
     const int64_t oblk = bh * p.nblk + blk;
     if (threadIdx.x < 2 * D) {  // the first D threads finish the mean, the next D the sum of unit rows
       const int which = threadIdx.x / D, d = threadIdx.x % D;
@@ -234,6 +166,7 @@ struct SelectParams {
   int Hq, Hk, nqb, ntk, row_ints;
   int kf, kl;  // key blocks j < kf and j >= ntk - kl are kept: always on, never candidates (both clamped to ntk)
   float sm_scale;
+  const int32_t* kv_lens;  // KVLEN only (else null): int32 [B], batch b has ceil(clamp(kv_lens[b], 0, N) / 64) key blocks
 };
 
 // orders a wave's LDS writes before its own later reads of other lanes' words (one wave owns a row: no workgroup barrier)
@@ -266,7 +199,10 @@ __device__ __forceinline__ uint32_t score_key(float s) {
 // Both:
 //  4. emission as block_map_compact_kernel: ballot + prefix popcount, ascending, the tail padded with the last tile.
 // Every sum runs in a fixed order and every decision is taken on values all lanes hold alike: deterministic, no atomics.
-template <int D, int RULE>
+// KVLEN (sage_block_select_kvlen): the rule runs over the ntk_b = ceil(len_b / 64) key blocks of the row's batch instead of
+// ntk -- kept blocks, candidates, n, kcount, the emission -- while every stride (pooled K, sim K, the LDS quarter, the list
+// row, the map row) stays that of N.
+template <int D, int RULE, bool KVLEN>
 __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p) {
   static_assert(RULE == SAGE_SELECT_CDF || RULE == SAGE_SELECT_TOPK, "two rules");
   extern __shared__ float prow_all[];
@@ -274,179 +210,21 @@ __global__ __launch_bounds__(256) void block_select_kernel(const SelectParams p)
   const int64_t row = (int64_t)blockIdx.x * 4 + w;
   if (row >= p.rows) return;
   float* prow = prow_all + (int64_t)w * p.ntk;
-  const int ntk = p.ntk;
   const int64_t bh = row / p.nqb;
   const int hq = (int)(bh % p.Hq);
   const int64_t b = bh / p.Hq;
   const int64_t bhk = b * p.Hk + hq / (p.Hq / p.Hk);
+  int ntk = p.ntk, kf = p.kf, kl = p.kl;
+  if constexpr (KVLEN) {
+    // ntk_b <= p.ntk (p.ntk << 6 >= N, and ceil(min(len, N) / 64) = ceil(min(len, 64 ntk) / 64))
+    ntk = __builtin_amdgcn_readfirstlane((min(max(p.kv_lens[b], 0), (p.ntk << 6)) + 63) >> 6);
+    kf = min(kf, ntk);
+    kl = min(kl, ntk);
+  }
   const float thr = p.thr[hq], par = p.par[hq];
   // a q-block that is not self-similar, or a cdfthreshd / topk of 1 and above (or NaN), keeps every tile
   bool all_on = !(p.sq[row] > thr) || !(par < 1.0f);
-  float mx = -INFINITY;
-  uint32_t tbits = 0;
-  int take = 0;
-  if (!all_on) {
-    const int sub = lane & 7, g = lane >> 3;
-    const float* pk = p.pk + bhk * ntk * D;
-    const float* sk = p.sk + bhk * ntk;
-    float4 q4[D / 32];
-#pragma unroll
-    for (int i = 0; i < D / 32; ++i) q4[i] = *reinterpret_cast<const float4*>(p.pq + row * D + (i * 8 + sub) * 4);
-    constexpr int U = 2;  // key blocks per lane group and step: all their loads are issued before the first use
-    for (int j0 = 0; j0 < ntk; j0 += 8 * U) {
-      float4 k4[U][D / 32];
-      float skv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int jc = min(j0 + 8 * u + g, ntk - 1);  // past the end: the last block again, not stored
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i) k4[u][i] = *reinterpret_cast<const float4*>(pk + (int64_t)jc * D + (i * 8 + sub) * 4);
-        skv[u] = sk[jc];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int j = j0 + 8 * u + g;
-        float dot = 0.f;
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i) {
-          dot = __builtin_fmaf(q4[i].x, k4[u][i].x, dot);
-          dot = __builtin_fmaf(q4[i].y, k4[u][i].y, dot);
-          dot = __builtin_fmaf(q4[i].z, k4[u][i].z, dot);
-          dot = __builtin_fmaf(q4[i].w, k4[u][i].w, dot);
-        }
-        dot = row_lanes_sum<8>(dot);
-        const bool cand = skv[u] > thr && j >= p.kf && j < ntk - p.kl;
-        const float s = dot * p.sm_scale;
-        if (sub == 0 && j < ntk) {
-          if constexpr (RULE == SAGE_SELECT_TOPK) prow[j] = __uint_as_float(cand ? score_key(s) : 0u);
-          else prow[j] = cand ? s : -INFINITY;
-        }
-      }
-    }
-    wave_lds_sync();
-    if constexpr (RULE == SAGE_SELECT_CDF) {
-      for (int j = lane; j < ntk; j += 64) mx = fmaxf(mx, prow[j]);
-      mx = wave_max(mx);
-      all_on = mx == -INFINITY;  // no candidate: every tile is forced on
-    }
-  }
-  if constexpr (RULE == SAGE_SELECT_TOPK) {
-    if (!all_on) {
-      // candidates whose key is >= t (t >= 1), from ballots: the same value in every lane
-      auto count_from = [&](uint32_t t) {
-        int c = 0;
-        for (int j0 = 0; j0 < ntk; j0 += 64) {
-          const int j = j0 + lane;
-          c += __popcll(__ballot(j < ntk && __float_as_uint(prow[j]) >= t));
-        }
-        return c;
-      };
-      const int n = count_from(1u);
-      all_on = n == 0;  // no candidate: every tile is forced on
-      if (!all_on) {
-        const float want = ceilf(par * (float)n);  // one fp32 product; par < 1 here
-        const int kcount = want >= (float)n ? n : want > 1.f ? (int)want : 1;
-        uint64_t lo = 1, hi = 1ull << 32;  // count_from(lo) >= kcount > count_from(hi): no key is 2^32
-        while (hi - lo > 1) {
-          const uint64_t mid = lo + ((hi - lo) >> 1);
-          if (count_from((uint32_t)mid) >= kcount) lo = mid; else hi = mid;
-        }
-        tbits = (uint32_t)lo;  // one of the keys; hi = lo + 1
-        take = kcount - (hi < (1ull << 32) ? count_from((uint32_t)hi) : 0);
-      }
-    }
-  } else if (!all_on) {
-    float tot = 0.f;
-    for (int j = lane; j < ntk; j += 64) {  // each lane rewrites the words it read
-      const float s = prow[j];
-      const float pj = s == -INFINITY ? -1.0f : expf(s - mx);
-      prow[j] = pj;
-      tot += fmaxf(pj, 0.f);
-    }
-    wave_lds_sync();
-    const float target = par * wave_sum(tot);
-    // sum of the p whose pattern is >= t, in the order of `tot`: skipped terms add exact zeros
-    auto mass_from = [&](int t) {
-      float gsum = 0.f;
-      for (int j = lane; j < ntk; j += 64) {
-        const float pj = prow[j];
-        gsum += __float_as_int(pj) >= t ? pj : 0.f;
-      }
-      return wave_sum(gsum);
-    };
-    int lo = 0, hi = 0x3F800001;  // mass_from(lo) >= target; no p is above 1.0f
-    while (hi - lo > 1) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (mass_from(mid) >= target) lo = mid; else hi = mid;
-    }
-    tbits = (uint32_t)lo;
-    const float tstar = __int_as_float(lo);
-    const float above = mass_from(lo + 1);
-    int nties = 0;
-    for (int j = lane; j < ntk; j += 64) nties += __float_as_int(prow[j]) == lo ? 1 : 0;
-    nties = wave_sum_i(nties);
-    take = 1;
-    if (tstar > 0.f) {
-      const float need = ceilf((target - above) / tstar);
-      take = need >= (float)nties ? nties : need > 1.f ? (int)need : 1;
-      if (take > 1 && above + (float)(take - 1) * tstar >= target) --take;
-      if (take < nties && above + (float)take * tstar < target) ++take;
-    }
-  }
-  int* out = p.lists + row * p.row_ints;
-  uint8_t* mrow = p.map ? p.map + row * ntk : nullptr;
-  int count = 0, lastj = 0, ties_before = 0;
-  for (int j0 = 0; j0 < ntk; j0 += 64) {
-    const int j = j0 + lane;
-    const bool in = j < ntk;
-    bool on = in;
-    if (!all_on) {
-      const uint32_t pb = in ? __float_as_uint(prow[j]) : 0u;
-      const bool tie = in && pb == tbits;
-      const uint64_t tbal = __ballot(tie);
-      const int rank = ties_before + __popcll(tbal & ((1ull << lane) - 1ull));
-      ties_before += __popcll(tbal);
-      // forced on: the blocks that are no candidates hold -1.0f (CDF) or the key 0 (TOPK)
-      const bool forced = RULE == SAGE_SELECT_TOPK ? pb == 0u : (int)pb < 0;
-      const bool above = RULE == SAGE_SELECT_TOPK ? pb > tbits : (int)pb > (int)tbits;
-      on = in && (forced || above || (tie && rank < take));
-    }
-    const uint64_t bal = __ballot(on);
-    if (on) out[1 + count + __popcll(bal & ((1ull << lane) - 1ull))] = j;
-    if (mrow && in) mrow[j] = on ? 1 : 0;
-    count += __popcll(bal);
-    if (bal) lastj = j0 + 63 - __clzll((long long)bal);
-  }
-  for (int i = 1 + count + lane; i < p.row_ints; i += 64) out[i] = lastj;
-  if (lane == 0) out[0] = count;
-}
-
-// block_select_kernel with per-batch lengths (sage_block_select_kvlen): the rule runs over the ntk_b = ceil(len_b / 64) key blocks
-// of the row's batch instead of ntk -- kept blocks, candidates, n, kcount, the emission -- while every stride (pooled K, sim K,
-// the LDS quarter, the list row, the map row) stays that of N.  Map columns >= ntk_b are written 0; with ntk_b == 0 the list is
-// empty.  A kernel of its own: block_select_kernel keeps its text and its code.
-struct SelectLenParams : SelectParams {
-  const int32_t* kv_lens;  // int32 [B], batch b has ceil(clamp(kv_lens[b], 0, N) / 64) key blocks
-};
-template <int D, int RULE>
-__global__ __launch_bounds__(256) void block_select_kvlen_kernel(const SelectLenParams p) {
-  static_assert(RULE == SAGE_SELECT_CDF || RULE == SAGE_SELECT_TOPK, "two rules");
-  extern __shared__ float prow_all[];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t row = (int64_t)blockIdx.x * 4 + w;
-  if (row >= p.rows) return;
-  float* prow = prow_all + (int64_t)w * p.ntk;
-  const int64_t bh = row / p.nqb;
-  const int hq = (int)(bh % p.Hq);
-  const int64_t b = bh / p.Hq;
-  const int64_t bhk = b * p.Hk + hq / (p.Hq / p.Hk);
-  // ntk_b <= p.ntk (p.ntk << 6 >= N, and ceil(min(len, N) / 64) = ceil(min(len, 64 ntk) / 64))
-  const int ntk = __builtin_amdgcn_readfirstlane((min(max(p.kv_lens[b], 0), (p.ntk << 6)) + 63) >> 6);
-  const int kf = min(p.kf, ntk), kl = min(p.kl, ntk);
-  const float thr = p.thr[hq], par = p.par[hq];
-  // a q-block that is not self-similar, or a cdfthreshd / topk of 1 and above (or NaN), keeps every tile
-  bool all_on = !(p.sq[row] > thr) || !(par < 1.0f);
-  all_on = all_on || ntk == 0;  // a batch without keys: nothing to score, and nothing is emitted below
+  if constexpr (KVLEN) all_on = all_on || ntk == 0;  // a batch without keys: nothing to score, and nothing is emitted below
   float mx = -INFINITY;
   uint32_t tbits = 0;
   int take = 0;
@@ -584,8 +362,10 @@ __global__ __launch_bounds__(256) void block_select_kvlen_kernel(const SelectLen
   }
   for (int i = 1 + count + lane; i < p.row_ints; i += 64) out[i] = lastj;
   if (lane == 0) out[0] = count;
-  if (mrow)
-    for (int j = ntk + lane; j < p.ntk; j += 64) mrow[j] = 0;
+  if constexpr (KVLEN) {  // map columns >= ntk_b are written 0 (with ntk_b == 0 the list above is empty)
+    if (mrow)
+      for (int j = ntk + lane; j < p.ntk; j += 64) mrow[j] = 0;
+  }
 }
 
 // Blocks per workgroup of the pooling kernel: as many as leave about `target` workgroups for all B*H heads.
@@ -606,7 +386,7 @@ static int block_pool_sim(const sage_tensor* x, int dtype, int B, int H, int N, 
   if (const int s = dim_dtype_status(D, dtype)) return s;
   if (blk != 64 && blk != 128) return SAGE_ERR_INVALID_ARGUMENT;
   if (mean && !aligned16(mean)) return SAGE_ERR_INVALID_ARGUMENT;
-  PoolLenParams p;
+  PoolParams p;
   p.x = (const uint16_t*)x->data; p.sb = x->stride_b; p.sh = x->stride_h; p.sn = x->stride_n;
   p.mean = (const uint16_t*)mean; p.pooled = pooled; p.sim = sim; p.kv_lens = kv_lens;
   p.H = H; p.N = N; p.nblk = (int)(((int64_t)N + blk - 1) / blk);
@@ -619,13 +399,11 @@ static int block_pool_sim(const sage_tensor* x, int dtype, int B, int H, int N, 
   by_dim(D, [&](auto d) {
     by_flag(blk == 128, [&](auto big) {
       by_flag(dtype == SAGE_BF16, [&](auto bf) {
-        constexpr int DD = decltype(d)::value, BLK = decltype(big)::value ? 128 : 64;
-        constexpr bool BF = decltype(bf)::value;
-        if (kvlen)
-          hipLaunchKernelGGL((block_pool_sim_kvlen_kernel<DD, BLK, BF>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
-        else
-          hipLaunchKernelGGL((block_pool_sim_kernel<DD, BLK, BF>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
-                             static_cast<const PoolParams&>(p));
+        by_flag(kvlen, [&](auto len) {
+          constexpr int DD = decltype(d)::value, BLK = decltype(big)::value ? 128 : 64;
+          constexpr bool BF = decltype(bf)::value, KVLEN = decltype(len)::value;
+          hipLaunchKernelGGL((block_pool_sim_kernel<DD, BLK, BF, KVLEN>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+        });
       });
     });
   });
@@ -658,7 +436,7 @@ static int block_select(const float* pooled_q, const float* sim_q, const float* 
   if (!(sm_scale > 0.f) || !(sm_scale < INFINITY)) return SAGE_ERR_INVALID_ARGUMENT;
   if (((int64_t)N + 63) / 64 > SAGE_SPARGE_MAX_KEY_TILES) return SAGE_ERR_TOO_LARGE;  // the rows of a workgroup in LDS
   if (block_lists_bytes < block_sparse_bytes(B, Hq, M, N)) return SAGE_ERR_INVALID_ARGUMENT;
-  SelectLenParams p;
+  SelectParams p;
   p.pq = pooled_q; p.sq = sim_q; p.pk = pooled_k; p.sk = sim_k; p.thr = simthreshd1; p.par = rule_param;
   p.lists = (int*)block_lists; p.map = block_map;
   p.Hq = Hq; p.Hk = Hk; p.nqb = (M + 127) / 128; p.ntk = (N + 63) / 64; p.row_ints = (int)block_list_row(N);
@@ -669,12 +447,12 @@ static int block_select(const float* pooled_q, const float* sim_q, const float* 
   launch_begin();
   by_dim(D, [&](auto d) {
     by_flag(rule == SAGE_SELECT_TOPK, [&](auto topk) {
-      constexpr int DD = decltype(d)::value, RULE = decltype(topk)::value ? SAGE_SELECT_TOPK : SAGE_SELECT_CDF;
-      const dim3 grid((unsigned)((p.rows + 3) / 4));
-      const size_t lds = (size_t)4 * p.ntk * sizeof(float);
-      if (kvlen) hipLaunchKernelGGL((block_select_kvlen_kernel<DD, RULE>), grid, dim3(256), lds, (hipStream_t)stream, p);
-      else hipLaunchKernelGGL((block_select_kernel<DD, RULE>), grid, dim3(256), lds, (hipStream_t)stream,
-                              static_cast<const SelectParams&>(p));
+      by_flag(kvlen, [&](auto len) {
+        constexpr int DD = decltype(d)::value, RULE = decltype(topk)::value ? SAGE_SELECT_TOPK : SAGE_SELECT_CDF;
+        const dim3 grid((unsigned)((p.rows + 3) / 4));
+        const size_t lds = (size_t)4 * p.ntk * sizeof(float);
+        hipLaunchKernelGGL((block_select_kernel<DD, RULE, decltype(len)::value>), grid, dim3(256), lds, (hipStream_t)stream, p);
+      });
     });
   });
   return launch_status();

@@ -276,6 +276,28 @@ def test_pooled_statistics_of_the_valid_blocks(sa, D):
     assert torch.equal(pooled[3:4, :, :3], rp) and torch.equal(sim[3:4, :, :3], rs)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("D", [64, 128])
+def test_full_lengths_take_the_other_branch_of_one_text(sa, D, dtype):
+    """The kernels with and without lengths are the two branches of one text (template flag KVLEN, sage_sparge.hip): with every
+    length equal to N they give the same bits -- pooled, sim, lists and map, both block sizes, both rules."""
+    from sageattention_amd.quant import block_pool_sim, k_mean
+    q, k = _clustered_qk(D, dtype)
+    full = torch.full((len(PLENS),), PN, dtype=torch.int32, device="cuda")
+    km = k_mean(k, "HND")
+    for blk in (64, 128):
+        for mean in (None, km):
+            got, want = block_pool_sim(k, blk, "HND", mean=mean, kv_lens=full), block_pool_sim(k, blk, "HND", mean=mean)
+            assert torch.isfinite(want[0]).all() and torch.isfinite(want[1]).all()
+            assert torch.equal(got[0], want[0]), f"pooled, {blk}-row blocks"
+            assert torch.equal(got[1], want[1]), f"sim, {blk}-row blocks"
+    for select in (dict(cdfthreshd=0.9), dict(topk=0.25, keep_first=1, keep_last=2)):
+        plan, bmap = sa.sparge_plan(q, k, kv_lens=full, return_map=True, **select)
+        rplan, rmap = sa.sparge_plan(q, k, return_map=True, **select)
+        assert torch.equal(plan.lists, rplan.lists) and torch.equal(bmap, rmap), select
+        assert not bmap.all() and bmap.any(), "the inputs are meant to give sparse lists"
+
+
 @pytest.mark.parametrize("select", [dict(cdfthreshd=0.9), dict(topk=0.25, keep_first=1, keep_last=2)], ids=["cdf", "topk"])
 @pytest.mark.parametrize("D", [64, 128])
 def test_plan_equals_the_plan_of_the_slice(sa, D, select):

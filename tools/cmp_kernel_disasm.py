@@ -1,13 +1,24 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 device code of two builds function by function: do the kernels a change was not meant to touch keep
+r"""Compare the gfx950 device code of two builds function by function: do the kernels a change was not meant to touch keep
 their instruction streams?
 
-    python tools/cmp_kernel_disasm.py OLD NEW [--filter REGEX]
+    python tools/cmp_kernel_disasm.py OLD NEW [--filter REGEX] [--rename REGEX=REPL ...]
 
 OLD and NEW are object files (sage_attn.o ...) or directories of them (csrc/ of two builds; objects are matched by name).
 Every device function is disassembled (llvm-objdump -d, no raw bytes), addresses and branch-target labels are dropped, and the
 remaining text -- mnemonics, registers, immediates, in order -- is compared.  Prints one line per object with the number of
-identical functions and names every function that differs or exists on one side only; exit status 1 if any differs."""
+identical functions and names every function that differs or exists on one side only; exit status 1 if any differs.
+
+Functions are matched by mangled name.  Where a change renames kernels, --rename REGEX=REPL (repeatable, applied in order with
+re.sub to OLD's names before matching) maps the old names to the new ones.  The predictor kernels of sage_sparge.hip lost their
+_kvlen twins to a trailing template flag KVLEN; to compare against a build from before that:
+
+    --rename '(block_(?:pool_sim|select)_kernelI.*)EEvNS_(\d+(?:Pool|Select)ParamsE)$=\1Lb0EEEvNS_\2'
+    --rename '27block_pool_sim_kvlen_kernel(I.*)EEvNS_13PoolLenParamsE$=21block_pool_sim_kernel\1Lb1EEEvNS_10PoolParamsE'
+    --rename '25block_select_kvlen_kernel(I.*)EEvNS_15SelectLenParamsE$=19block_select_kernel\1Lb1EEEvNS_12SelectParamsE'
+
+(the first gives block_*_kernel<...> the flag false; the twins take one substitution each, because a mangled name spells out
+the lengths of the kernel's and the parameter struct's names)"""
 import argparse
 import glob
 import os
@@ -60,6 +71,8 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--filter", default="", help="only functions whose mangled name matches this regex")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="re.sub applied to OLD's mangled names before matching (repeatable, in order)")
     a = ap.parse_args()
     if os.path.isdir(a.old):
         names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(a.old, "*.o")))
@@ -69,6 +82,9 @@ def main():
     bad = 0
     for old, new in pairs:
         fo, fn = functions(old), functions(new)
+        for r in a.rename:
+            rx, repl = r.split("=", 1)
+            fo = {re.sub(rx, repl, n): ins for n, ins in fo.items()}
         keep = [n for n in sorted(set(fo) | set(fn)) if re.search(a.filter, n)]
         same = [n for n in keep if n in fo and n in fn and fo[n] == fn[n]]
         print(f"{os.path.basename(old)}: {len(same)} of {len(keep)} functions identical "
