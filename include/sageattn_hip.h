@@ -572,8 +572,8 @@ int sage_attn_fusedq_pv_f8_kvlen(const sage_tensor* q, int q_dtype, const sage_t
  * (skipped is then not read); otherwise pv_thresh and skipped as for the twin.  kv_lens NULL or misaligned:
  * SAGE_ERR_INVALID_ARGUMENT; every other status as the twin gives it.  All checks run before any launch.  The rows of the
  * emptied q-blocks are written by a second, tiny launch on the same stream.
- * Not built: query lengths, a causal form, and kv_lens on the one-call operators, sage_attn_tile_mass and
- * sage_block_plan_recall. */
+ * Not built: query lengths, a causal form, and kv_lens on the one-call operators.  (The calibration entry points have twins
+ * with kv_lens: sage_attn_tile_mass_kvlen and sage_block_plan_recall_kvlen, at the end of this file.) */
 int sage_attn_qk_int8_pv_f16_blocksparse_kvlen(const sage_tensor* q8, const sage_tensor* k8, const sage_tensor* v,
                                                int v_dtype, const sage_tensor* o, int o_dtype, const float* q_scale,
                                                const float* k_scale, const float* v_mean, float* lse, int B, int Hq,
@@ -720,6 +720,35 @@ int sage_attn_tile_mass(const sage_tensor* q8, const sage_tensor* k8, const floa
  * The lists are trusted as by the attention kernels.  Argument checks as sage_block_map_compact. */
 int sage_block_plan_recall(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq, int M,
                            int N, float* recall, int32_t* kept, sage_stream_t stream);
+
+/* Calibration with per-batch key lengths (kv_lens, len_b = clamp(kv_lens[b], 0, N), ntk_b = ceil(len_b / 64) as for
+ * sage_attn_*_blocksparse_kvlen): the calibration sees the operands, the key range and the lists of the attention call it
+ * calibrates.  Each entry point takes the arguments of its twin, then kv_lens (NULL or misaligned:
+ * SAGE_ERR_INVALID_ARGUMENT; every other status as the twin gives it); all checks run before the launch.  Grids, strides and
+ * output layouts are those of N.  The lengths are read on the device only; a call captures into a HIP graph and a replay
+ * reads the lengths held then.  The rule:
+ * sage_attn_tile_mass_kvlen
+ *   - Operands: k8 and k_scale as sage_k_smooth_quant_kvlen makes them (statistics over the rows < len_b), q8 and q_scale
+ *     as for the twin (Q has no lengths).
+ *   - For every b with len_b > 0, mass[b, :, :, :ntk_b] is BIT-IDENTICAL to the twin called on q8[b:b+1], k8[b:b+1, :, :len_b]
+ *     and their scales (N = len_b) with the same granularity: the softmax runs over the keys < len_b, tile ntk_b - 1 is masked
+ *     at len_b, and both passes add in the order of the twin, over fewer tiles.
+ *   - The entries [ntk_b, ceil(N/64)) are exactly 0, and every entry of mass is written by every call.  A batch with
+ *     len_b == 0 has an all-zero row: the one exception to "every mass[b,h,i,:] sums to 1".
+ *   - Nothing in rows >= len_b of k8 and no scale of a tile >= ntk_b influences anything -- they are never loaded.
+ * sage_block_plan_recall_kvlen
+ *   - recall[b,h,i] = sum of mass[b,h,i,j] over the listed tiles j < ntk_b, kept[b,h,i] = the number of those entries.
+ *   - The sum runs in the tile slots and the fixed tree of the twin, so it is BIT-IDENTICAL to the twin on the lists of the
+ *     map cut to ntk_b columns and the mass cut likewise, and as monotone under set inclusion.
+ *   - The clip is by list entry and does not rely on mass being 0 beyond the length.  The lists are read-only: lists made
+ *     without lengths (sage_block_map_compact, sage_block_select) serve any lengths, as do those of sage_block_select_kvlen,
+ *     which hold no entry >= ntk_b in the first place.  A batch with len_b == 0 has recall 0 and kept 0. */
+int sage_attn_tile_mass_kvlen(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale, const float* k_scale,
+                              int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
+                              float sm_scale, int logit_mult_is_one, float* mass, const int32_t* kv_lens,
+                              sage_stream_t stream);
+int sage_block_plan_recall_kvlen(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq,
+                                 int M, int N, float* recall, int32_t* kept, const int32_t* kv_lens, sage_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,11 @@ SIGNATURES = {
                                     c_int, c_float, c_int, c_void_p, c_void_p]),
     "sage_block_plan_recall": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    # calibration with per-batch key lengths: the twins' arguments, then kv_lens
+    "sage_attn_tile_mass_kvlen": (c_int, [_P, _P, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "sage_block_plan_recall_kvlen": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
 }
 
 

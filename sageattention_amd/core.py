@@ -23,7 +23,8 @@ from .quant import (_quant, block_pool_sim, k_mean, k_smooth_quant, k_smooth_qua
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
            "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan",
-           "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen"]
+           "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen",
+           "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen"]
 
 
 def _common_checks(q, k, v):
@@ -879,18 +880,34 @@ def sageattn_sparge(
 
 
 # ---- calibration of the predictor ------------------------------------------------------------------------------------------------
-def _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale):
-    """sage_attn_tile_mass on the padded query view ``q`` and the K operands of ``_prep_k`` -> fp32 [B,Hq,nqb,ntk]"""
+def _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale, kv_lens=None):
+    """sage_attn_tile_mass on the padded query view ``q`` and the K operands of ``_prep_k`` -> fp32 [B,Hq,nqb,ntk].  With
+    ``kv_lens`` (int32 [B]) sage_attn_tile_mass_kvlen on the K operands of ``k_smooth_quant_kvlen``."""
     B, Hq, M, D = L.dims(q, tensor_layout)
     _, Hk, N, _ = L.dims(k8, tensor_layout)
     if Hq % Hk != 0:
         raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
     q8, qs, _ = _quant_q(q, km, tensor_layout, qk_quant_gran, sm_scale, 32, False, Hq, Hk)
     mass = torch.empty((B, Hq, (M + 127) // 128, (N + 63) // 64), dtype=torch.float32, device=q.device)
-    L.check(L.lib().sage_attn_tile_mass(L.desc(q8, tensor_layout), L.desc(k8, tensor_layout), qs.data_ptr(), ks.data_ptr(),
-                                        B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], 128, 32, float(sm_scale), 0,
-                                        mass.data_ptr(), L.stream_ptr(q.device)), "sage_attn_tile_mass")
+    args = (L.desc(q8, tensor_layout), L.desc(k8, tensor_layout), qs.data_ptr(), ks.data_ptr(), B, Hq, Hk, M, N, D,
+            _GRAN_CODE[qk_quant_gran], 128, 32, float(sm_scale), 0, mass.data_ptr())
+    if kv_lens is None:
+        L.check(L.lib().sage_attn_tile_mass(*args, L.stream_ptr(q.device)), "sage_attn_tile_mass")
+    else:
+        L.check(L.lib().sage_attn_tile_mass_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(q.device)),
+                "sage_attn_tile_mass_kvlen")
     return mass
+
+
+def _check_kv_lens_kind(kv_lens):
+    """What ``_check_kv_lens`` asks of ``kv_lens`` alone -- an int32 tensor of one dimension --, for the functions that check
+    it before they look at any other argument; [B] and the device follow in ``_check_kv_lens``"""
+    if not isinstance(kv_lens, torch.Tensor):
+        raise TypeError("kv_lens must be an int32 tensor of shape [B]")
+    if kv_lens.dtype != torch.int32:
+        raise TypeError(f"kv_lens must be of dtype int32, got {kv_lens.dtype}")
+    if kv_lens.dim() != 1:
+        raise ValueError(f"kv_lens shape {tuple(kv_lens.shape)} does not match [B]")
 
 
 def sageattn_tile_mass(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", sm_scale: Optional[float] = None,
@@ -900,9 +917,15 @@ def sageattn_tile_mass(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "H
     tile's keys and averaged over the block's valid rows (the definition: include/sageattn_hip.h, sage_attn_tile_mass).  It
     is computed from the INT8 Q and K and the scales that operator multiplies -- same head-dim padding, K pre-pass and Q
     quantizer -- so each row of the last axis sums to 1 and ``plan_recall`` of a map is the share of the probability that the
-    map keeps.  Costs about one dense attention call.  Non-causal.  Per-batch key lengths are not built here: there is no
-    ``kv_lens`` keyword (a TypeError, as every unknown keyword); the mass of a padded batch includes its padding."""
+    map keeps.  Costs about one dense attention call.  Non-causal.  There is no ``kv_lens`` keyword here (a TypeError, as
+    every unknown keyword) and the mass of a padded batch includes its padding: per-batch key lengths are the twin
+    ``sageattn_tile_mass_kvlen``."""
     _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
+    return _tile_mass_of(q, k, None, tensor_layout, sm_scale, qk_quant_gran, smooth_k)
+
+
+def _tile_mass_of(q, k, kv_lens, tensor_layout, sm_scale, qk_quant_gran, smooth_k):
+    """``sageattn_tile_mass`` and its twin below their argument checks"""
     assert q.is_cuda, "Input tensors must be on cuda."
     assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
     assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
@@ -910,16 +933,43 @@ def sageattn_tile_mass(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "H
         q, k, _, head_dim_og = _pad_head_dim(q, k, k)
         if sm_scale is None:
             sm_scale = head_dim_og ** -0.5
-        k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
-        return _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale)
+        if kv_lens is None:
+            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, smooth_k)
+        else:
+            k8, ks, km = k_smooth_quant_kvlen(k, kv_lens, tensor_layout, *_k_pairing(qk_quant_gran))
+        return _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale, kv_lens)
 
 
-def _plan_recall(plan, mass):
+def sageattn_tile_mass_kvlen(q: torch.Tensor, k: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str = "HND",
+                             sm_scale: Optional[float] = None, qk_quant_gran: str = "per_thread"):
+    """``sageattn_tile_mass`` with a per-batch number of valid keys: the exact tile mass of what
+    ``sageattn_block_sparse(q, k, ..., kv_lens=kv_lens)`` multiplies.  ``kv_lens`` is an int32 [B] tensor on q's device, read
+    on the device only (no host synchronisation; the call captures into a HIP graph and a replay reads the lengths the tensor
+    holds then); ``len_b = clamp(kv_lens[b], 0, N)``, ``ntk_b = ceil(len_b / 64)``.
+
+    For every b with len_b > 0, ``mass[b, :, :, :ntk_b]`` is bit-identical to ``sageattn_tile_mass`` on ``q[b:b+1]`` and the
+    first len_b keys of ``k[b:b+1]`` with the same ``qk_quant_gran``; the entries ``[ntk_b, ceil(N/64))`` are exactly 0, and
+    every entry is written by every call.  A batch without keys has an all-zero row -- the one exception to "every
+    ``mass[b,h,i,:]`` sums to 1".  Nothing in rows >= len_b of k influences anything, NaN and Inf included: the smoothing mean
+    and the K scales are those of the length-aware K pre-pass (``k_smooth_quant_kvlen``), taken over the valid rows, and the
+    kernel neither loads rows nor scales beyond them.  K smoothing is always on (that pre-pass always smooths): there is no
+    ``smooth_k``.  The rule: include/sageattn_hip.h, sage_attn_tile_mass_kvlen."""
+    _check_kv_lens_kind(kv_lens)
+    _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
+    kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+    return _tile_mass_of(q, k, kv_lens, tensor_layout, sm_scale, qk_quant_gran, True)
+
+
+def _plan_recall(plan, mass, kv_lens=None):
     recall = torch.empty(mass.shape[:3], dtype=torch.float32, device=mass.device)
     kept = torch.empty(mass.shape[:3], dtype=torch.int32, device=mass.device)
-    L.check(L.lib().sage_block_plan_recall(plan.lists.data_ptr(), plan.lists.numel() * 4, mass.data_ptr(), plan.B, plan.Hq,
-                                           plan.M, plan.N, recall.data_ptr(), kept.data_ptr(), L.stream_ptr(mass.device)),
-            "sage_block_plan_recall")
+    args = (plan.lists.data_ptr(), plan.lists.numel() * 4, mass.data_ptr(), plan.B, plan.Hq, plan.M, plan.N, recall.data_ptr(),
+            kept.data_ptr())
+    if kv_lens is None:
+        L.check(L.lib().sage_block_plan_recall(*args, L.stream_ptr(mass.device)), "sage_block_plan_recall")
+    else:
+        L.check(L.lib().sage_block_plan_recall_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(mass.device)),
+                "sage_block_plan_recall_kvlen")
     return recall, kept
 
 
@@ -927,11 +977,32 @@ def plan_recall(plan_or_map, mass: torch.Tensor):
     """What a plan keeps of ``mass`` (``sageattn_tile_mass``): (recall fp32 [B,Hq,nqb], kept int32 [B,Hq,nqb]) -- per q-block
     the summed mass of its active tiles and their number (sage_block_plan_recall: deterministic, and never smaller for a
     superset of tiles).  ``plan_or_map`` is a ``BlockSparsePlan`` or a bool / uint8 map [B|1, Hq|1, nqb, ntk], which is
-    compacted with ``block_sparse_plan`` first.  An empty q-block has recall 0.  No ``kv_lens`` keyword: the lists of a plan
-    made with lengths are taken as they stand (tiles beyond a batch's length are off in them already)."""
+    compacted with ``block_sparse_plan`` first.  An empty q-block has recall 0.  No ``kv_lens`` keyword: every listed tile
+    counts (in a plan made with lengths the tiles beyond a batch's length are off already); ``plan_recall_kvlen`` clips any
+    plan or map to per-batch key lengths."""
+    return _plan_recall_of(plan_or_map, mass, None)
+
+
+def plan_recall_kvlen(plan_or_map, mass: torch.Tensor, kv_lens: torch.Tensor):
+    """``plan_recall`` under per-batch key lengths (``kv_lens`` int32 [B] on the device of ``mass``, read on the device only;
+    ``ntk_b = ceil(clamp(kv_lens[b], 0, N) / 64)`` with N = 64 ntk for a map, the plan's N for a plan):
+    ``recall[b,h,i]`` is the sum of ``mass[b,h,i,j]`` over the listed tiles j < ntk_b and ``kept[b,h,i]`` the number of those
+    entries -- what ``sageattn_block_sparse(..., kv_lens=kv_lens)`` computes of the list.  The sum runs in the tile slots and
+    the fixed tree of ``plan_recall``, so it is bit-identical to ``plan_recall`` on the map and the mass both cut to ntk_b
+    columns, and as monotone under set inclusion.  The clip is by list entry: it does not rely on ``mass`` being 0 beyond the
+    length (``sageattn_tile_mass_kvlen`` writes 0 there all the same).  The lists are only read: a plan made without
+    lengths, or a static map, serves any lengths.  A batch without keys has recall 0 and kept 0."""
+    _check_kv_lens_kind(kv_lens)
+    return _plan_recall_of(plan_or_map, mass, kv_lens)
+
+
+def _plan_recall_of(plan_or_map, mass, kv_lens):
+    """``plan_recall`` and its twin: the checks of mass and plan, the compaction of a map, the launch"""
     if not isinstance(mass, torch.Tensor) or mass.dim() != 4 or mass.dtype != torch.float32:
         raise ValueError("mass must be the fp32 [B,Hq,ceil(M/128),ceil(N/64)] tensor of sageattn_tile_mass")
     B, Hq, nqb, ntk = mass.shape
+    if kv_lens is not None:
+        kv_lens = _check_kv_lens(kv_lens, B, mass.device)
     if isinstance(plan_or_map, BlockSparsePlan):
         plan = plan_or_map
         if (plan.B, plan.Hq, (plan.M + 127) // 128, (plan.N + 63) // 64) != (B, Hq, nqb, ntk):
@@ -948,7 +1019,7 @@ def plan_recall(plan_or_map, mass: torch.Tensor):
     if plan.lists.device != mass.device:
         raise ValueError(f"the plan is on {plan.lists.device}, mass on {mass.device}")
     with torch.cuda.device(mass.device):
-        return _plan_recall(plan, mass.contiguous())
+        return _plan_recall(plan, mass.contiguous(), kv_lens)
 
 
 class SpargeTuning:
@@ -989,7 +1060,54 @@ def sparge_tune(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", ta
     and q-blocks are fixed-order sums or minima of these.  Head recall is therefore monotone in the parameter, in fp32 as
     well as in exact arithmetic, and the grid splits into a failing part below ``param`` and a passing part from it on.
 
-    Per-batch key lengths are not built here: there is no ``kv_lens`` keyword (a TypeError); tune on unpadded data."""
+    There is no ``kv_lens`` keyword here (a TypeError) and a padded batch is tuned with its padding: per-batch key lengths
+    are the twin ``sparge_tune_kvlen``."""
+    _check_tune_args(target, rule, keep_first, keep_last, steps, reduce, qk_quant_gran, tensor_layout)
+    return _sparge_tune(q, k, None, tensor_layout, target, rule, simthreshd1, keep_first, keep_last, steps, reduce, sm_scale,
+                        qk_quant_gran, mass)
+
+
+def sparge_tune_kvlen(q: torch.Tensor, k: torch.Tensor, kv_lens: torch.Tensor, tensor_layout: str = "HND",
+                      target: float = 0.95, rule: str = "cdf", simthreshd1=0.6, keep_first: int = 0, keep_last: int = 0,
+                      steps: int = 8, reduce: str = "mean", sm_scale: Optional[float] = None,
+                      qk_quant_gran: str = "per_thread", mass: Optional[torch.Tensor] = None):
+    """``sparge_tune`` for a padded batch with per-batch key lengths: the parameter that
+    ``sageattn_sparge(q, k, v, ..., kv_lens=kv_lens)`` needs to keep ``target`` of the mass of the keys it attends.
+    ``kv_lens`` is an int32 [B] tensor on q's device, read on the device only (no host synchronisation; the function captures
+    into a HIP graph and a replay reads the lengths the tensor holds then); ``len_b = clamp(kv_lens[b], 0, N)``,
+    ``ntk_b = ceil(len_b / 64)``.  Returns a ``SpargeTuning``.
+
+    It is the search of ``sparge_tune`` with four substitutions: the smoothing mean (and, for the mass, the INT8 K and its
+    scales) come from the length-aware K pre-pass ``k_smooth_quant_kvlen``; K is pooled with
+    ``block_pool_sim(..., kv_lens=kv_lens)``; the selection is sage_block_select_kvlen, what ``sparge_plan(...,
+    kv_lens=kv_lens)`` runs; and the recall is ``plan_recall_kvlen`` of ``sageattn_tile_mass_kvlen`` (pass ``mass`` to reuse
+    one).  When ``mass`` is passed the K pre-pass still runs, whole, to get that mean -- the heavy default ``sparge_plan``
+    describes for its ``km``.
+
+    Batches without keys take no part in the reductions.  With ``rec, kept = plan_recall_kvlen(plan, mass, kv_lens)``,
+    ``weight`` the valid rows of the q-blocks as fp32 [1,1,nqb], ``lens = kv_lens.clamp(0, N)``, ``valid = lens > 0``,
+    ``nv = valid.sum()`` and ``ntk_b = (lens + 63) // 64``, all on the device and in fp32:
+      ``"mean"``   ``(rec * weight * valid[:, None, None]).sum((0, 2)) * (nv.clamp(min=1) * M).to(torch.float32).reciprocal()``
+      ``"min"``    ``torch.where(valid[:, None, None], rec, inf).amin((0, 2))``
+      density      ``kept.sum((0, 2)).to(torch.float32) * (nqb * ntk_b.sum()).clamp(min=1).to(torch.float32).reciprocal()``
+    (the product with a reciprocal, not a quotient, because that is what torch makes of ``sparge_tune``'s division by the
+    Python number ``B * M``: with all lengths equal to N every field of the result is bit-identical to ``sparge_tune(q, k,
+    ...)``).  When no batch has keys (``nv == 0``) the head recall is 1 and the density 0, so ``param`` is ``2^-steps`` and
+    ``met`` True.
+
+    The monotonicity argument of ``sparge_tune`` carries over unchanged: sage_block_select_kvlen keeps supersets at larger
+    parameters within the ntk_b key blocks of every batch, the clipped recall adds non-negative mass in fixed tile slots and
+    a fixed tree, and the reductions above are fixed-order sums or minima of it scaled by factors that do not depend on the
+    parameter.  So bisection again returns the smallest passing grid value exactly."""
+    _check_kv_lens_kind(kv_lens)
+    _check_tune_args(target, rule, keep_first, keep_last, steps, reduce, qk_quant_gran, tensor_layout)
+    kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+    return _sparge_tune(q, k, kv_lens, tensor_layout, target, rule, simthreshd1, keep_first, keep_last, steps, reduce, sm_scale,
+                        qk_quant_gran, mass)
+
+
+def _check_tune_args(target, rule, keep_first, keep_last, steps, reduce, qk_quant_gran, tensor_layout):
+    """The keywords of ``sparge_tune`` and its twin, checked before anything touches a tensor"""
     if rule not in ("cdf", "topk"):
         raise ValueError(f"rule must be 'cdf' or 'topk', got {rule!r}")
     if reduce not in ("mean", "min"):
@@ -1000,6 +1118,11 @@ def sparge_tune(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", ta
         raise ValueError(f"steps must be an int in 1..16, got {steps!r}")
     _check_select_args(None, keep_first, keep_last)
     _check_sparse_args("fp16", qk_quant_gran, tensor_layout)
+
+
+def _sparge_tune(q, k, kv_lens, tensor_layout, target, rule, simthreshd1, keep_first, keep_last, steps, reduce, sm_scale,
+                 qk_quant_gran, mass):
+    """The search of ``sparge_tune`` (``kv_lens`` None) and of ``sparge_tune_kvlen`` below their argument checks"""
     assert q.is_cuda, "Input tensors must be on cuda."
     assert q.dtype in [torch.float16, torch.bfloat16], "Input tensors must be in dtype of torch.float16 or torch.bfloat16"
     assert q.device == k.device and q.dtype == k.dtype, "q and k must have one device and one dtype."
@@ -1013,34 +1136,54 @@ def sparge_tune(q: torch.Tensor, k: torch.Tensor, tensor_layout: str = "HND", ta
         if Hq % Hk != 0:
             raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
         nqb, ntk = (M + 127) // 128, (N + 63) // 64
-        if mass is None:
-            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
-            mass = _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale)
-        else:
+        if mass is not None:
             if tuple(mass.shape) != (B, Hq, nqb, ntk) or mass.dtype != torch.float32 or mass.device != dev:
                 raise ValueError(f"mass must be an fp32 tensor of shape {(B, Hq, nqb, ntk)} on {dev}")
             mass = mass.contiguous()
+        if kv_lens is not None:  # the length-aware pre-pass: its mean is what the attention call will smooth with
+            k8, ks, km = k_smooth_quant_kvlen(k, kv_lens, tensor_layout, *_k_pairing(qk_quant_gran))
+            if mass is None:
+                mass = _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale, kv_lens)
+        elif mass is None:
+            k8, ks, km = _prep_k(k, tensor_layout, qk_quant_gran, True)
+            mass = _tile_mass(q, k8, ks, km, tensor_layout, qk_quant_gran, sm_scale)
+        else:
             km = k_mean(k, tensor_layout)
         thr = _per_head(simthreshd1, Hq, dev, "simthreshd1")
         pq, sq = block_pool_sim(q, 128, tensor_layout)
-        pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km)
+        pk, sk = block_pool_sim(k, 64, tensor_layout, mean=km, kv_lens=kv_lens)
         plan = BlockSparsePlan(torch.empty(_plan_ints(B, Hq, M, N), dtype=torch.int32, device=dev), B, Hq, M, N)
         code = L.SELECT_CDF if rule == "cdf" else L.SELECT_TOPK
         weight = (torch.arange(nqb, device=dev) * -128 + M).clamp(max=128).to(torch.float32).view(1, 1, nqb)  # c_i
         unit = 2.0 ** -steps
+        if kv_lens is not None:  # the reductions the docstring of sparge_tune_kvlen states; nothing is read back
+            lens = kv_lens.clamp(0, N)
+            valid = (lens > 0).view(B, 1, 1)
+            some = valid.any()
+            weight_valid = weight * valid  # (rec * weight) * valid == rec * (weight * valid) bit for bit: valid is 0 or 1
+            inv_rows = (valid.sum().clamp(min=1) * M).to(torch.float32).reciprocal()
+            inv_tiles = (nqb * ((lens + 63) // 64).sum()).clamp(min=1).to(torch.float32).reciprocal()
 
         def evaluate(par):
             """-> (head recall, density) [Hq] of the selection with the per-head parameters ``par``"""
-            L.check(L.lib().sage_block_select(pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D,
-                                              float(sm_scale), thr.data_ptr(), code, par.data_ptr(), min(keep_first, ntk),
-                                              min(keep_last, ntk), plan.lists.data_ptr(), plan.lists.numel() * 4, None,
-                                              L.stream_ptr(dev)), "sage_block_select")
-            rec, kept = _plan_recall(plan, mass)
+            args = (pq.data_ptr(), sq.data_ptr(), pk.data_ptr(), sk.data_ptr(), B, Hq, Hk, M, N, D, float(sm_scale),
+                    thr.data_ptr(), code, par.data_ptr(), min(keep_first, ntk), min(keep_last, ntk), plan.lists.data_ptr(),
+                    plan.lists.numel() * 4, None)
+            if kv_lens is None:
+                L.check(L.lib().sage_block_select(*args, L.stream_ptr(dev)), "sage_block_select")
+                rec, kept = _plan_recall(plan, mass)
+                if reduce == "mean":
+                    head = (rec * weight).sum(dim=(0, 2)) / float(B * M)
+                else:
+                    head = rec.amin(dim=(0, 2))
+                return head, kept.sum(dim=(0, 2)).to(torch.float32) / float(B * nqb * ntk)
+            L.check(L.lib().sage_block_select_kvlen(*args, kv_lens.data_ptr(), L.stream_ptr(dev)), "sage_block_select_kvlen")
+            rec, kept = _plan_recall(plan, mass, kv_lens)
             if reduce == "mean":
-                head = (rec * weight).sum(dim=(0, 2)) / float(B * M)
+                head = (rec * weight_valid).sum(dim=(0, 2)) * inv_rows
             else:
-                head = rec.amin(dim=(0, 2))
-            return head, kept.sum(dim=(0, 2)).to(torch.float32) / float(B * nqb * ntk)
+                head = torch.where(valid, rec, float("inf")).amin(dim=(0, 2))
+            return torch.where(some, head, 1.0), kept.sum(dim=(0, 2)).to(torch.float32) * inv_tiles
 
         hi = torch.full((Hq,), 1 << steps, dtype=torch.int32, device=dev)  # passes (or nothing does)
         lo = torch.zeros_like(hi)                                          # fails: the empty parameter is never evaluated

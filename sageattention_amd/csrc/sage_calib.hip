@@ -5,6 +5,10 @@
 //                        the key tiles: row maximum and row sum, then the normalised probabilities.  QK^T only, no P.V.
 //   plan_recall_kernel   per list row of a plan: the sum of that mass over the tiles the list keeps, and their number.
 // The definitions are stated in include/sageattn_hip.h.  Neither kernel uses atomics; every sum runs in a fixed order.
+// Each kernel is one text with a trailing template flag KVLEN for the forms with per-batch key lengths (sage_attn_tile_mass_kvlen,
+// sage_block_plan_recall_kvlen), as the predictor's kernels are (sage_sparge.hip): `if constexpr (KVLEN)` at the few points
+// where a length changes something, nothing of it in the instantiations without lengths, and kv_lens the last member of the
+// parameter block (null without lengths).
 #include "sage_entry.h"
 
 namespace sage {
@@ -54,6 +58,8 @@ struct MassParams {
   int gq, gk;   // scales per (b,h)
   int qgran, blkq, warpq;
   float logit_mult;
+  int B;                   // KVLEN only: the workgroup ids are split head-major
+  const int32_t* kv_lens;  // KVLEN only (else null): int32 [B], batch b has the keys < clamp(kv_lens[b], 0, N)
 };
 
 // One workgroup of 4 waves per (q-block, h, b), 32 query rows per wave, the geometry of the attention kernels: S^T = K . Q^T
@@ -71,7 +77,15 @@ struct MassParams {
 //           the entry -- while the workgroup is already at the next tile.
 // Every entry of the q-block's row of `mass` is written; a wave whose rows are all >= M contributes an exact 0 and skips the
 // arithmetic (it still stages K and meets every barrier).
-template <int D, bool KTHREAD>
+// KVLEN (sage_attn_tile_mass_kvlen): the same two sweeps over the ntk_b = ceil(len_b / 64) tiles of the batch, len_b read with
+// one scalar load, so everything derived from it is workgroup uniform.  Rows are clamped to len_b - 1 and the tail mask sits
+// in tile ntk_b - 1 against len_b: neither a K row >= len_b nor the scales of a tile >= ntk_b are ever loaded.  Pass 1 adds
+// tiles in ascending order and pass 2 works tile by tile, so the entries < ntk_b have the bits of the kernel without lengths
+// on the slice of the first len_b keys; the entries [ntk_b, ntk) are stored as 0 behind the second sweep.  A batch without
+// keys has no row len_b - 1 to clamp to: its workgroups zero their row and leave before any load of K and any barrier.  The
+// workgroup ids are split head-major as in attn_i8_kvlen_kernel (batches alternate within a head, so that no XCD holds only
+// the longest batch), and the row of `mass` is addressed by (b, h, q-block).
+template <int D, bool KTHREAD, bool KVLEN>
 __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
   constexpr int KS = D / 32;              // k-steps of the int8 MFMA
   constexpr int KCH = D / 16;             // 16-B chunks per K row
@@ -85,13 +99,23 @@ __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
   const int r = lane & 31, hh = lane >> 5;
   const int qb = (int)(blockIdx.x % (unsigned)p.nqb);
   const int bh = (int)(blockIdx.x / (unsigned)p.nqb);
-  const int h = bh % p.Hq, b = bh / p.Hq;
+  const int h = KVLEN ? bh / p.B : bh % p.Hq, b = KVLEN ? bh % p.B : bh / p.Hq;
   const int hk = h / (p.Hq / p.Hk);
+  int nkeys = p.N, ntk = p.ntk;  // the batch's keys and key tiles
+  float* mrow = p.mass + (int64_t)blockIdx.x * p.ntk;
+  if constexpr (KVLEN) {
+    nkeys = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);  // len_b
+    ntk = (nkeys + 63) >> 6;                                    // ntk_b
+    mrow = p.mass + (((int64_t)b * p.Hq + h) * p.nqb + qb) * p.ntk;
+    if (ntk == 0) {  // workgroup uniform
+      for (int j = tid; j < p.ntk; j += 256) mrow[j] = 0.f;
+      return;
+    }
+  }
   const int q0 = qb * 128 + wave * 32;
   const int row = q0 + r;
   const int rowc = min(row, p.M - 1);
   const bool wave_live = q0 < p.M;  // wave uniform
-  const int ntk = p.ntk;
 
   // Q^T fragments (B operand) and the row's scale, indexed as prepare_q of the attention kernels
   v4i qf[KS];
@@ -130,7 +154,7 @@ __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
   auto load_tile = [&](const int j, v4i (&reg)[KC]) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < KC; ++i)
-      reg[i] = *reinterpret_cast<const v4i*>(kg + (int64_t)min(64 * j + st_row[i], p.N - 1) * p.ksn + st_pos[i]);
+      reg[i] = *reinterpret_cast<const v4i*>(kg + (int64_t)min(64 * j + st_row[i], nkeys - 1) * p.ksn + st_pos[i]);
   };
   auto store_tile = [&](const v4i (&reg)[KC]) __attribute__((always_inline)) {
 #pragma unroll
@@ -158,7 +182,7 @@ __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
       for (int e = 0; e < 16; ++e) t[mt][e] = (float)s[e] * ((e & 2) ? sc1 : sc0);
     }
     if (j == ntk - 1) {  // the sequence end, as mask_limit: one compare against a per-lane limit
-      const int lim = p.N - 1 - (j << 6) - 4 * hh;
+      const int lim = nkeys - 1 - (j << 6) - 4 * hh;
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -220,7 +244,6 @@ __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
 
   // ---- pass 2: normalised probabilities, reduced to one number per wave and tile
   const int c_rows = min(128, p.M - qb * 128);
-  float* const mrow = p.mass + (int64_t)blockIdx.x * ntk;
   auto emit = [&](const int j) __attribute__((always_inline)) {  // the entry of tile j - 1: its four numbers are in LDS
     if (tid == 0 && j > 0) mrow[j - 1] = (((wpart[0] + wpart[1]) + wpart[2]) + wpart[3]) / (float)c_rows;
   };
@@ -238,6 +261,8 @@ __global__ __launch_bounds__(256) void tile_mass_kernel(const MassParams p) {
   });
   __syncthreads();
   emit(ntk);
+  if constexpr (KVLEN)
+    for (int j = ntk + tid; j < p.ntk; j += 256) mrow[j] = 0.f;  // the tiles beyond the batch's keys
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -250,6 +275,8 @@ struct RecallParams {
   int* kept;
   int64_t rows;
   int ntk, row_ints;
+  int64_t rows_b;          // KVLEN only: list rows per batch, Hq * ceil(M/128)
+  const int32_t* kv_lens;  // KVLEN only (else null): int32 [B], batch b has ceil(clamp(kv_lens[b], 0, N) / 64) key tiles
 };
 
 // One wave per list row, four rows per workgroup.  The sum is taken in TILE slots, not in list positions: lane l adds, in
@@ -258,6 +285,10 @@ struct RecallParams {
 // is not smaller, in fp32 as in exact arithmetic -- what the bisection of the tuner rests on.
 // Membership without a search: the lists ascend, so the entries that fall into the 64 tiles of a step are the next ones of
 // the list, at most 64: each lane holds one and raises the flag of its tile in the wave's 64 words of LDS.
+// KVLEN (sage_block_plan_recall_kvlen): the batch of the row has ntk_b key tiles; the steps stop in front of ntk_b and an
+// entry counts only below it, whatever `mass` holds beyond -- the same slots and the same tree as on the list and the mass cut
+// to ntk_b columns.  `kept` is the number of entries that counted.  The lists are only read.
+template <bool KVLEN>
 __global__ __launch_bounds__(256) void plan_recall_kernel(const RecallParams p) {
   __shared__ int win[4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -267,24 +298,28 @@ __global__ __launch_bounds__(256) void plan_recall_kernel(const RecallParams p) 
   const int count = lst[0];
   const int cnt = min(max(count, 0), p.ntk);  // entries that are read
   const float* mrow = p.mass + row * p.ntk;
+  int ntk = p.ntk;
+  if constexpr (KVLEN)  // ntk_b, wave uniform
+    ntk = (min(max(uniform_load_i32(p.kv_lens + ((int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(w)) / p.rows_b), 0),
+               p.ntk << 6) + 63) >> 6;
   float acc = 0.f;
   int pos = 0;
-  for (int j0 = 0; j0 < p.ntk; j0 += 64) {
+  for (int j0 = 0; j0 < ntk; j0 += 64) {
     const int e = pos + lane < cnt ? lst[1 + pos + lane] : 0x7fffffff;
-    const bool here = e >= j0 && e < j0 + 64;
+    const bool here = e >= j0 && e < (KVLEN ? min(j0 + 64, ntk) : j0 + 64);
     win[w][lane] = 0;
     wave_lds_fence();
     if (here) win[w][e - j0] = 1;
     wave_lds_fence();
     const int j = j0 + lane;
-    if (win[w][lane] != 0 && j < p.ntk) acc += mrow[j];
+    if (win[w][lane] != 0 && j < ntk) acc += mrow[j];
     pos += __popcll(__ballot(here));
     // (a lane clears only the word it has just read; the other lanes write it behind the next fence)
   }
   acc = wave_sum_fixed(acc);
   if (lane == 0) {
     p.recall[row] = acc;
-    p.kept[row] = count;
+    p.kept[row] = KVLEN ? pos : count;
   }
 }
 
@@ -294,9 +329,11 @@ using namespace sage;
 
 static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-extern "C" int sage_attn_tile_mass(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale, const float* k_scale,
-                                   int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
-                                   float sm_scale, int logit_mult_is_one, float* mass, sage_stream_t stream) {
+// sage_attn_tile_mass and its twin with per-batch lengths (kvlen: kv_lens is required)
+static int tile_mass(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale, const float* k_scale, int B, int Hq,
+                     int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq, float sm_scale, int logit_mult_is_one,
+                     float* mass, bool kvlen, const int32_t* kv_lens, sage_stream_t stream) {
+  if (kvlen && (!kv_lens || !aligned4(kv_lens))) return SAGE_ERR_INVALID_ARGUMENT;
   if (!tensor_ok(q8, 16) || !tensor_ok(k8, 16) || !q_scale || !k_scale || !mass) return SAGE_ERR_INVALID_ARGUMENT;
   if (!aligned4(q_scale) || !aligned4(k_scale) || !aligned4(mass)) return SAGE_ERR_INVALID_ARGUMENT;
   if (B <= 0 || Hq <= 0 || Hk <= 0 || M <= 0 || N <= 0 || Hq % Hk != 0) return SAGE_ERR_INVALID_ARGUMENT;
@@ -319,21 +356,41 @@ extern "C" int sage_attn_tile_mass(const sage_tensor* q8, const sage_tensor* k8,
   p.gk = kthread ? p.ntk * 4 : p.ntk;
   p.qgran = qk_gran; p.blkq = blkq; p.warpq = warpq;
   p.logit_mult = logit_mult_is_one ? 1.0f : sm_scale * kLog2e;
+  p.B = B; p.kv_lens = kv_lens;
   // (Q and K are addressed with 64-bit offsets, not through buffer descriptors: no 2 GiB slice window)
   const int64_t grid = (int64_t)B * Hq * p.nqb;
   if (grid >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
   launch_begin();
   by_dim(D, [&](auto d) {
     by_flag(kthread, [&](auto kt) {
-      hipLaunchKernelGGL((tile_mass_kernel<decltype(d)::value, decltype(kt)::value>), dim3((unsigned)grid), dim3(256), 0,
-                         (hipStream_t)stream, p);
+      by_flag(kvlen, [&](auto len) {
+        hipLaunchKernelGGL((tile_mass_kernel<decltype(d)::value, decltype(kt)::value, decltype(len)::value>),
+                           dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+      });
     });
   });
   return launch_status();
 }
 
-extern "C" int sage_block_plan_recall(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq,
-                                      int M, int N, float* recall, int32_t* kept, sage_stream_t stream) {
+extern "C" int sage_attn_tile_mass(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale, const float* k_scale,
+                                   int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int blkq, int warpq,
+                                   float sm_scale, int logit_mult_is_one, float* mass, sage_stream_t stream) {
+  return tile_mass(q8, k8, q_scale, k_scale, B, Hq, Hk, M, N, D, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, mass, false,
+                   nullptr, stream);
+}
+
+extern "C" int sage_attn_tile_mass_kvlen(const sage_tensor* q8, const sage_tensor* k8, const float* q_scale,
+                                         const float* k_scale, int B, int Hq, int Hk, int M, int N, int D, int qk_gran,
+                                         int blkq, int warpq, float sm_scale, int logit_mult_is_one, float* mass,
+                                         const int32_t* kv_lens, sage_stream_t stream) {
+  return tile_mass(q8, k8, q_scale, k_scale, B, Hq, Hk, M, N, D, qk_gran, blkq, warpq, sm_scale, logit_mult_is_one, mass, true,
+                   kv_lens, stream);
+}
+
+// sage_block_plan_recall and its twin with per-batch lengths (kvlen: kv_lens is required)
+static int plan_recall(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq, int M, int N,
+                       float* recall, int32_t* kept, bool kvlen, const int32_t* kv_lens, sage_stream_t stream) {
+  if (kvlen && (!kv_lens || !aligned4(kv_lens))) return SAGE_ERR_INVALID_ARGUMENT;
   if (!block_lists || !aligned16(block_lists) || !mass || !recall || !kept) return SAGE_ERR_INVALID_ARGUMENT;
   if (!aligned4(mass) || !aligned4(recall) || !aligned4(kept)) return SAGE_ERR_INVALID_ARGUMENT;
   if (B <= 0 || Hq <= 0 || M <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
@@ -341,9 +398,25 @@ extern "C" int sage_block_plan_recall(const int32_t* block_lists, int64_t block_
   RecallParams p;
   p.lists = (const int*)block_lists; p.mass = mass; p.recall = recall; p.kept = (int*)kept;
   p.ntk = (int)(((int64_t)N + 63) / 64); p.row_ints = (int)block_list_row(N);
-  p.rows = (int64_t)B * Hq * (((int64_t)M + 127) / 128);
+  p.rows_b = (int64_t)Hq * (((int64_t)M + 127) / 128);
+  p.rows = (int64_t)B * p.rows_b;
+  p.kv_lens = kv_lens;
   if ((p.rows + 3) / 4 >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
   launch_begin();
-  hipLaunchKernelGGL(plan_recall_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
+  by_flag(kvlen, [&](auto len) {
+    hipLaunchKernelGGL(plan_recall_kernel<decltype(len)::value>, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+  });
   return launch_status();
+}
+
+extern "C" int sage_block_plan_recall(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq,
+                                      int M, int N, float* recall, int32_t* kept, sage_stream_t stream) {
+  return plan_recall(block_lists, block_lists_bytes, mass, B, Hq, M, N, recall, kept, false, nullptr, stream);
+}
+
+extern "C" int sage_block_plan_recall_kvlen(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B,
+                                            int Hq, int M, int N, float* recall, int32_t* kept, const int32_t* kv_lens,
+                                            sage_stream_t stream) {
+  return plan_recall(block_lists, block_lists_bytes, mass, B, Hq, M, N, recall, kept, true, kv_lens, stream);
 }

@@ -6,7 +6,7 @@ their instruction streams?
 
 OLD and NEW are object files (sage_attn.o ...) or directories of them (csrc/ of two builds; objects are matched by name).
 Every device function is disassembled (llvm-objdump -d, no raw bytes), addresses and branch-target labels are dropped, and the
-remaining text -- mnemonics, registers, immediates, in order -- is compared.  Prints one line per object with the number of
+remaining text -- mnemonics, registers, immediates, in order; not the padding behind a function's end -- is compared.  Prints one line per object with the number of
 identical functions and names every function that differs or exists on one side only; exit status 1 if any differs.
 
 Functions are matched by mangled name.  Where a change renames kernels, --rename REGEX=REPL (repeatable, applied in order with
@@ -18,7 +18,11 @@ _kvlen twins to a trailing template flag KVLEN; to compare against a build from 
     --rename '25block_select_kvlen_kernel(I.*)EEvNS_15SelectLenParamsE$=19block_select_kernel\1Lb1EEEvNS_12SelectParamsE'
 
 (the first gives block_*_kernel<...> the flag false; the twins take one substitution each, because a mangled name spells out
-the lengths of the kernel's and the parameter struct's names)"""
+the lengths of the kernel's and the parameter struct's names).  The calibration kernels of sage_calib.hip gained the same flag;
+against a build from before that:
+
+    --rename '(16tile_mass_kernelILi\d+ELb[01]E)EEvNS_10MassParamsE$=\1Lb0EEEvNS_10MassParamsE'
+    --rename '18plan_recall_kernelENS_12RecallParamsE$=18plan_recall_kernelILb0EEEvNS_12RecallParamsE'"""
 import argparse
 import glob
 import os
@@ -63,6 +67,9 @@ def functions(obj):
         ins = re.sub(r"<[^>]+>", "<label>", ins)           # branch targets by name
         if ins:
             cur.append(ins)
+    for ins in out.values():  # what follows a function's last instruction up to the next symbol: alignment, objdump's "..."
+        while ins and ins[-1] in ("s_nop 0", "s_code_end", "..."):
+            ins.pop()
     return out
 
 

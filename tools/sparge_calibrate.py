@@ -11,8 +11,15 @@ process with HIP events and alternating windows.  Writes profiles/sparge_calibra
      and topk that sparge_tune finds for target 0.95.
 SYNTHETIC data: the recalls and tuned values describe these generators, not a model.
 
+With --kv-lens the twins with per-batch key lengths instead (sageattn_tile_mass_kvlen, sparge_tune_kvlen), at (4,32,8192,128)
+and (4,32,2048,64); writes profiles/sparge_calibration_kvlen.md:
+  a. sageattn_tile_mass_kvlen with every length N beside sageattn_tile_mass, the latter timed twice per rotation: its two
+     columns against each other are the yardstick.
+  b. lengths [N, 3N/4, N/2, N/4] (0.625 of the tiles) as a ratio to the call with full lengths.
+  c. sparge_tune_kvlen beside sparge_tune with every length N, the mass computed inside.
+
 usage: sparge_calibrate.py [--launches 50] [--repeats 5] [--shapes c3,c3d64,wan] [--data-shape small] [--commit HASH]
-                           [--out profiles/sparge_calibration.md]"""
+                           [--out profiles/sparge_calibration.md] [--kv-lens]"""
 import argparse
 import os
 import statistics
@@ -23,6 +30,8 @@ import torch  # noqa: E402
 import sageattention_amd as sa  # noqa: E402
 
 SHAPES = {"c3": (4, 32, 8192, 128), "c3d64": (4, 32, 8192, 64), "wan": (1, 40, 32760, 128), "small": (2, 8, 4096, 128)}
+KVLEN_SHAPES = ((4, 32, 8192, 128), (4, 32, 2048, 64))
+PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
 ap = argparse.ArgumentParser()
 ap.add_argument("--launches", type=int, default=50)
 ap.add_argument("--repeats", type=int, default=5)
@@ -30,9 +39,12 @@ ap.add_argument("--shapes", default="c3,c3d64,wan")
 ap.add_argument("--data-shape", default="small")
 ap.add_argument("--simthreshd1", type=float, default=0.6)
 ap.add_argument("--commit", default="")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "sparge_calibration.md"))
+ap.add_argument("--kv-lens", action="store_true", help="measure the twins with per-batch key lengths instead")
+ap.add_argument("--out", default=None, help="default: profiles/sparge_calibration.md, with --kv-lens "
+                                            "profiles/sparge_calibration_kvlen.md")
 a = ap.parse_args()
+if a.out is None:
+    a.out = os.path.join(PROFILES, "sparge_calibration_kvlen.md" if a.kv_lens else "sparge_calibration.md")
 lines = []
 
 
@@ -69,6 +81,90 @@ def spread(ts):
 def fmt(t, nd=3):
     return "[" + ", ".join(f"{x:.{nd}f}" for x in t.tolist()) + "]"
 
+
+def write_out():
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def rotate(fns, launches):
+    """``a.repeats`` rotations over ``fns`` (name -> call), one window of ``launches`` calls each -> name -> [ms per call]"""
+    ts = {n: [] for n in fns}
+    for _ in range(a.repeats):
+        for n, fn in fns.items():
+            ts[n].append(window(fn, launches))
+    return ts
+
+
+def ratio_spread(num, den):
+    """median, min and max over the rotations of num / den, window by window"""
+    r = [x / y for x, y in zip(num, den)]
+    return f"{statistics.median(r):.3f} ({min(r):.3f} .. {max(r):.3f})"
+
+
+def kvlen_report():
+    emit("# Calibration with per-batch key lengths: sageattn_tile_mass_kvlen, sparge_tune_kvlen (MI355X)")
+    emit()
+    emit(f"commit {a.commit or 'unknown'}; tools/sparge_calibrate.py --kv-lens, HIP events, one process, {a.repeats} rotations of")
+    emit(f"alternating windows, {a.launches} calls each (sparge_tune: 5).  fp16, per-thread scales, random normal Q / K, whole calls")
+    emit("with their K pre-pass and Q quantizer.  Ratios are taken window by window within a rotation: median (min .. max).")
+    emit()
+    rows_a, rows_b, rows_c = [], [], []
+    for B, H, N, D in KVLEN_SHAPES:
+        gen = torch.Generator(device="cuda").manual_seed(N + D)
+        q, k = (torch.randn(B, H, N, D, generator=gen, device="cuda").half() for _ in range(2))
+        full = torch.full((B,), N, dtype=torch.int32, device="cuda")
+        part = torch.tensor([N, 3 * N // 4, N // 2, N // 4], dtype=torch.int32, device="cuda")
+        assert torch.equal(sa.sageattn_tile_mass_kvlen(q, k, full), sa.sageattn_tile_mass(q, k)), "full lengths: the same bits"
+        ts = rotate({"plain": lambda: sa.sageattn_tile_mass(q, k), "full": lambda: sa.sageattn_tile_mass_kvlen(q, k, full),
+                     "plain2": lambda: sa.sageattn_tile_mass(q, k), "part": lambda: sa.sageattn_tile_mass_kvlen(q, k, part)},
+                    a.launches)
+        shape = f"{(B, H, N, D)}"
+        rows_a.append(f"| {shape} | {spread(ts['plain'])} | {spread(ts['plain2'])} | {spread(ts['full'])} | "
+                      f"{ratio_spread(ts['plain2'], ts['plain'])} | {ratio_spread(ts['full'], ts['plain'])} |")
+        tiles = float(((part + 63) // 64).sum()) / (B * ((N + 63) // 64))
+        rows_b.append(f"| {shape} | {part.tolist()} | {tiles:.3f} | {spread(ts['part'])} | {ratio_spread(ts['part'], ts['full'])} |")
+        kw = dict(simthreshd1=a.simthreshd1, steps=8)
+        t0, t1 = sa.sparge_tune(q, k, **kw), sa.sparge_tune_kvlen(q, k, full, **kw)
+        assert all(torch.equal(getattr(t0, n), getattr(t1, n)) for n in ("param", "met", "recall", "recall_below", "density"))
+        tt = rotate({"plain": lambda: sa.sparge_tune(q, k, **kw), "full": lambda: sa.sparge_tune_kvlen(q, k, full, **kw),
+                     "plain2": lambda: sa.sparge_tune(q, k, **kw)}, 5)
+        rows_c.append(f"| {shape} | {spread(tt['plain'])} | {spread(tt['plain2'])} | {spread(tt['full'])} | "
+                      f"{ratio_spread(tt['plain2'], tt['plain'])} | {ratio_spread(tt['full'], tt['plain'])} |")
+        del q, k
+        torch.cuda.empty_cache()
+    emit("## a. full lengths: sageattn_tile_mass_kvlen beside sageattn_tile_mass")
+    emit()
+    emit("Every length is N; the mass is bit-identical to the call without lengths (asserted).  The plain call is timed twice per")
+    emit("rotation; its second column over its first is the yardstick for the last column.")
+    emit()
+    emit("| shape (B, H, N, D) | sageattn_tile_mass | sageattn_tile_mass again | sageattn_tile_mass_kvlen, full | again / plain | kvlen / plain |")
+    emit("|---|---|---|---|---|---|")
+    for r in rows_a:
+        emit(r)
+    emit()
+    emit("## b. lengths [N, 3N/4, N/2, N/4]")
+    emit()
+    emit("| shape (B, H, N, D) | kv_lens | share of the tiles | sageattn_tile_mass_kvlen | / the call with full lengths |")
+    emit("|---|---|---|---|---|")
+    for r in rows_b:
+        emit(r)
+    emit()
+    emit("## c. full lengths: sparge_tune_kvlen beside sparge_tune (steps=8, rule=\"cdf\", the mass computed inside)")
+    emit()
+    emit("Every field of the result is bit-identical (asserted).")
+    emit()
+    emit("| shape (B, H, N, D) | sparge_tune | sparge_tune again | sparge_tune_kvlen, full | again / plain | kvlen / plain |")
+    emit("|---|---|---|---|---|---|")
+    for r in rows_c:
+        emit(r)
+    write_out()
+
+
+if a.kv_lens:
+    kvlen_report()
+    sys.exit(0)
 
 emit("# Calibrating the block-map predictor: exact tile mass, recall, tuned thresholds (MI355X)")
 emit()
@@ -136,6 +232,4 @@ for name, (q, k) in data.items():
         emit(f"- tuned {rule}: param {fmt(t.param, 4)}; met {t.met.tolist()}; recall {fmt(t.recall, 4)}; recall one grid step below "
              f"{fmt(t.recall_below, 4)}; density {fmt(t.density)}")
     del mass
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("\n".join(lines) + "\n")
+write_out()
