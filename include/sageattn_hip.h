@@ -750,6 +750,49 @@ int sage_attn_tile_mass_kvlen(const sage_tensor* q8, const sage_tensor* k8, cons
 int sage_block_plan_recall_kvlen(const int32_t* block_lists, int64_t block_lists_bytes, const float* mass, int B, int Hq,
                                  int M, int N, float* recall, int32_t* kept, const int32_t* kv_lens, sage_stream_t stream);
 
+/* ==== split-KV attention (new: few query rows against many keys -- text or latent queries over a long video context, a
+ * decode step or a speculative chunk over a padded KV cache.  Every other attention entry point launches one workgroup per
+ * (b, h_q, 128-row q-block) that walks all key tiles of its head; with M = 1..1024 and N = 16K..128K that grid leaves most of
+ * the chip idle.  Here S = num_splits workgroups share the keys of a q-block and a second launch merges their results) ====
+ * Inputs: the padded [B,H,N,D] operands of sage_attn_fusedq_pv_{f16,f8} (K quantized with its smoothing mean km), an optional
+ * kv_lens (device, int32 [B], 4-byte aligned, NULL = every batch has N keys), 1 <= num_splits <= SAGE_MERGE_MAX.  The rule:
+ *   - Key ranges.  len_b = clamp(kv_lens[b], 0, N), or N without kv_lens; ntk_b = ceil(len_b / 64); tps_b = ceil(ntk_b / S).
+ *     Split s of batch b owns the key tiles [s * tps_b, min((s + 1) * tps_b, ntk_b)); the last valid tile is masked at len_b.
+ *     A split whose range is empty takes no part: the batch has ceil(ntk_b / tps_b) non-empty splits (0 when len_b == 0), the
+ *     first ones.  The merge computes this count itself; an empty split writes nothing, and nothing is read from its slot.
+ *   - Statistics are those of the whole call: km, the K scales and the FP8 v_scale are what sage_k_smooth_quant /
+ *     sage_kv_prepare_fp8 (with kv_lens: their _kvlen twins) make of all the keys.  All splits share one smoothing vector.
+ *   - Partial result of split s: the state of the attention loop run over exactly its tiles, in ascending order, from the
+ *     empty state.  The normalised row o_s is stored in fp32, before any rounding to the output type, into the workspace
+ *     ([S,B,Hq,M,D] fp32), its raw base-2 LSE lse2_s behind it ([S,B,Hq,M] fp32).  o_s rounded to o_dtype (nearest even) is
+ *     BIT-IDENTICAL to the o of sage_attn_fusedq_pv_*_blocksparse(_kvlen) called with lists that hold exactly those tile
+ *     columns in every q-block -- which in turn is bit-identical to the dense 4-wave kernel on the gathered tiles.
+ *   - Final result: with mx = max_s lse2_s and w_s = 2^(lse2_s - mx) over the non-empty splits in split order,
+ *     o = (sum_s w_s o_s) / (sum_s w_s), rounded ONCE to o_dtype, and lse = (mx + log2(sum_s w_s)) / log2(e) +
+ *     (q . km) * sm_scale, the smoothing correction added once.  No atomics: two calls give the same bits.
+ *   - len_b == 0: o = 0, lse = -inf.  Nothing in rows >= len_b of K or V influences any output, NaN and Inf included.
+ *   - The lengths are read on the device only: no host synchronisation, no pointer arrays; both launches capture into a HIP
+ *     graph, and a replay reads the lengths the buffer holds then.
+ * The arguments of sage_attn_fusedq_pv_{f16,f8} without is_causal, then kv_lens (may be NULL), num_splits, workspace (16-byte
+ * aligned, at least sage_splitkv_workspace_bytes(B, Hq, M, D, num_splits) bytes; contents unspecified afterwards, slots of
+ * empty splits untouched) and workspace_bytes.  lse may be NULL.  Always 4-wave workgroups (SAGE_TUNE_NWAVES does not apply).
+ * Checked before the first launch: num_splits outside [1, SAGE_MERGE_MAX], workspace NULL, unaligned or too small, kv_lens
+ * misaligned -> SAGE_ERR_INVALID_ARGUMENT; the 2 GiB slice window and every other argument as sage_attn_fusedq_pv_*.
+ * Not built, SAGE_ERR_UNSUPPORTED: SAGE_GRAN_PER_BLOCK, v_mean != NULL (V smoothing), km == NULL (K smoothing off) or
+ * misaligned.  There is no causal form (the library's causal mask is top-left aligned: with M << N it would mask nearly every
+ * key), no block map, attn_mask, cu_seqlens or kv_layout form, no INT8-Q form, no 8-wave geometry and no one-call operator. */
+size_t sage_splitkv_workspace_bytes(int B, int Hq, int M, int D, int num_splits); /* 0 for arguments out of range */
+int sage_attn_fusedq_pv_f16_splitkv(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                    int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                    const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D,
+                                    int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens, int num_splits,
+                                    void* workspace, size_t workspace_bytes, sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_splitkv(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                   const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                   const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                   int N, int D, int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens,
+                                   int num_splits, void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ from . import _qattn_rocm as qattn  # noqa: F401
 __all__ = ["qattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp8_cuda",
            "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_qk_int8_pv_fp16_triton"]
 
-_LAZY = {"sageattn": ".core", "sageattn_varlen": ".core", "ring_sageattn": ".core", "ulysses_sageattn": ".core"}
+_LAZY = {"sageattn": ".core", "sageattn_varlen": ".core", "ring_sageattn": ".core", "ulysses_sageattn": ".core",
+         "sageattn_splitkv": ".core", "splitkv_num_splits": ".core"}
 
 
 def __getattr__(name):

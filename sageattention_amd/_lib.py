@@ -188,6 +188,14 @@ SIGNATURES = {
                                           c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "sage_block_plan_recall_kvlen": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    # split-KV attention: the fused-Q twins' arguments without is_causal, then kv_lens (or NULL), num_splits, workspace, its bytes
+    "sage_splitkv_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "sage_attn_fusedq_pv_f16_splitkv": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                                c_int, c_void_p, c_size_t, c_void_p]),
+    "sage_attn_fusedq_pv_f8_splitkv": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                               c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 

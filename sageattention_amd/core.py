@@ -24,7 +24,7 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
            "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan",
            "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen",
-           "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen"]
+           "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits"]
 
 
 def _common_checks(q, k, v):
@@ -561,6 +561,146 @@ def sageattn_kvlen(
             sm_scale = head_dim_og ** -0.5
         kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
         o, lse = _fused_attn(q, kv, tensor_layout, is_causal, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens=kv_lens)
+        return _pack(o[..., :head_dim_og], lse, None, None)
+
+
+# ---- split-KV attention ----------------------------------------------------------------------------------------------------
+SPLITKV_MAX = 16               # SAGE_MERGE_MAX (include/sageattn_hip.h)
+SPLITKV_MIN_TILES = 8          # key tiles (of 64) a split should keep
+SPLITKV_SLOTS = 2 * 256        # resident 4-wave workgroups of an MI355X: two per CU, 256 CUs
+
+
+def splitkv_num_splits(B: int, Hq: int, M: int, N: int) -> int:
+    """The number of splits ``sageattn_splitkv(num_splits=None)`` takes for a call of this shape: from the shape alone (no
+    host synchronisation; ``kv_lens`` does not enter),
+
+        min(16, ceil(ntk / 8), ceil(2 * 256 / (B * Hq * ceil(M / 128)))), at least 1,      ntk = ceil(N / 64).
+
+    The third term asks for just enough splits that the grid ``B * Hq * ceil(M/128) * S`` reaches the 512 workgroups an MI355X
+    holds at once (two 4-wave workgroups on each of 256 CUs); the second keeps at least 8 key tiles per split, so that the
+    prologue, the epilogue and the merge of a split stay small beside its loop; the first is the merge kernel's slot count.
+    A grid that fills the chip already resolves to 1.  The two constants (8 tiles per split, two workgroups per CU) were
+    counted from the kernel's geometry and then measured (tools/splitkv_bench.py, profiles/splitkv.md: whole calls against the
+    dense operator, S swept over {1, 2, 4, 8, 16}); they stood: wherever the rule picks S > 1 the call is faster than the
+    dense one by far more than the dense call's spread against itself -- 0.66-0.68x its time at (1, 40, 512, 32760, 128) with
+    S = 4, 0.33x (FP16 PV) / 0.46x (FP8 PV) at (1, 32, 128, 65536, 128) with S = 16, 0.49x / 0.77x for a decode step
+    (8, 32, 1, 8192, 128) folded by its GQA group with S = 8 -- and within 6 % of the fastest S of the sweep; at
+    (4, 32, 8192, 8192, 128) it resolves to 1 (S = 2 there: 1.13-1.16x the dense time)."""
+    ntk = (int(N) + 63) // 64
+    grid = int(B) * int(Hq) * ((int(M) + 127) // 128)
+    return max(1, min(SPLITKV_MAX, -(-ntk // SPLITKV_MIN_TILES), -(-SPLITKV_SLOTS // max(grid, 1))))
+
+
+def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, num_splits, workspace=None, out=None):
+    """sage_attn_fusedq_pv_{f16,f8}_splitkv on the operands ``kv`` of ``_prepass``: the workspace (the fp32 partial results of
+    the splits), the attention launch over the splits and the merge.  ``workspace`` (uint8, on q's device) and ``out`` (a
+    tensor or view of q's shape and dtype with a contiguous last dim) are the caller's where given: afterwards the workspace
+    holds the partials, [S,B,Hq,M,D] fp32 and behind them [S,B,Hq,M] fp32.  -> (o, lse or None)"""
+    k8, ks, km, v, v_scale, _ = kv
+    qk_quant_gran, warpq = q_quant
+    B, Hq, M, D = L.dims(q, tensor_layout)
+    _, Hk, N, _ = L.dims(k8, tensor_layout)
+    if Hq % Hk != 0:
+        raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
+    lib = L.lib()
+    o = torch.empty(q.size(), dtype=q.dtype, device=q.device) if out is None else out
+    lse = torch.empty((B, Hq, M), dtype=torch.float32, device=q.device) if return_lse else None
+    nbytes = lib.sage_splitkv_workspace_bytes(B, Hq, M, D, num_splits)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    nbytes = ws.numel()
+    shape = (B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
+    tail = (L.ptr(kv_lens), num_splits, ws.data_ptr(), nbytes, L.stream_ptr(q.device))
+    if v_scale is not None:
+        name = "sage_attn_fusedq_pv_f8_splitkv"
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc_vt(v, tensor_layout),
+                L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), v_scale.data_ptr(), None,
+                L.ptr(lse))
+    else:
+        name = "sage_attn_fusedq_pv_f16_splitkv"
+        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc(v, tensor_layout),
+                L.dtype_code(v.dtype), L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), None,
+                L.ptr(lse))
+    L.check(getattr(lib, name)(*args, *shape, *tail), name)
+    return o, lse
+
+
+@torch.compiler.disable
+def sageattn_splitkv(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    kv_lens: Optional[torch.Tensor] = None,
+    num_splits: Optional[int] = None,
+    tensor_layout: str = "HND",
+    sm_scale: Optional[float] = None,
+    pv: str = "fp16",
+    qk_quant_gran: str = "per_thread",
+    return_lse: bool = False,
+    **refused: Any,
+):
+    """SageAttention for few query rows against many keys: the key tiles of every (batch, head, 128-row q-block) are spread
+    over ``num_splits`` workgroups, each of which runs the ordinary attention loop over its range and stores an fp32 partial
+    result, and a second launch merges the partials (log-sum-exp, in split order: deterministic, no atomics) and rounds once
+    to the output dtype.  The other operators launch ``B * Hq * ceil(M/128)`` workgroups, which fills an MI355X only with
+    many query rows; this one is for text or latent queries over a long video context, a decode step or a speculative chunk
+    over a padded KV cache (M = 1..1024, N = 16K..128K).  Nothing dispatches to it implicitly.
+
+    ``kv_lens`` (optional, int32 [B] on q's device, read on the device only: no host synchronisation, the call captures into a
+    HIP graph and a replay reads the lengths the tensor holds then) gives batch b its keys [0, len_b), ``len_b =
+    clamp(kv_lens[b], 0, N)``, with the statistics of ``sageattn_kvlen``: nothing in rows >= len_b of k or v influences any
+    output, NaN and Inf included; a batch without keys gives o = 0, lse = -inf.  Split s of a batch with ``ntk_b =
+    ceil(len_b/64)`` tiles owns the tiles ``[s * tps_b, min((s+1) * tps_b, ntk_b))``, ``tps_b = ceil(ntk_b / num_splits)``; the K
+    smoothing mean, the K scales and the FP8 V scale are those of the whole call.  The rule: include/sageattn_hip.h, split-KV
+    attention.
+
+    ``num_splits``: 1..16, or None for ``splitkv_num_splits(B, Hq, M, N)`` (from the shape only).  A resolved count of 1
+    makes exactly the launches of ``sageattn_kvlen`` (with ``kv_lens``) or ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (without)
+    and returns their bits.  ``pv`` ("fp16" | "fp8") is explicit; ``pv="fp8"`` with ``kv_lens`` wants k and v of one shape.
+
+    Non-causal, K smoothing always on, V not smoothed, ``per_warp`` or ``per_thread`` scales.  ``is_causal``, ``attn_mask``,
+    ``block_map`` / ``plan``, ``cu_seqlens_q`` / ``cu_seqlens_k``, ``smooth_k=False`` and ``smooth_v`` are refused by name
+    (ValueError): the library's causal mask is top-left aligned, and with M << N it would mask nearly every key.
+
+    Decode with grouped-query attention: with M = 1 a q-block holds one row of 128.  The operator is non-causal, so the
+    ``g = Hq // Hk`` query heads of a KV head may be folded into query rows first -- ``q.view(B, Hk, g, D)`` for a
+    ``[B, Hq, 1, D]`` query (HND) against the unchanged ``[B, Hk, N, D]`` cache, and ``o.view(B, Hq, 1, D)`` afterwards: K and V
+    are then read once per KV head instead of once per query head."""
+    neutral = {"is_causal": False, "attn_mask": None, "block_map": None, "plan": None, "cu_seqlens_q": None, "cu_seqlens_k": None,
+               "smooth_k": True, "smooth_v": False}  # what is not built, and the one value of each that asks for nothing
+    for name, value in refused.items():
+        if name not in neutral:
+            raise TypeError(f"sageattn_splitkv() got an unexpected keyword argument '{name}'")
+        if value is not neutral[name]:
+            raise ValueError(f"sageattn_splitkv does not take {name}={value!r}: it is non-causal, without a mask, a block "
+                             "map or packed sequences, K smoothing always on and V not smoothed")
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+    if kv_lens is not None:
+        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+        if pv == "fp8" and k.shape != v.shape:
+            raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if num_splits is not None:
+        if isinstance(num_splits, bool) or not isinstance(num_splits, int):
+            raise TypeError(f"num_splits must be an int in [1, {SPLITKV_MAX}] or None, got {type(num_splits).__name__}")
+        if not 1 <= num_splits <= SPLITKV_MAX:
+            raise ValueError(f"num_splits must be in [1, {SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    B, Hq, M, _ = L.dims(q, tensor_layout)
+    N = L.dims(k, tensor_layout)[2]
+    if num_splits is None:
+        num_splits = splitkv_num_splits(B, Hq, M, N)
+    if num_splits == 1:  # the operator this call names: its launches, its bits
+        if kv_lens is not None:
+            return sageattn_kvlen(q, k, v, kv_lens, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                  qk_quant_gran=qk_quant_gran, return_lse=return_lse)
+        dense = sageattn_qk_int8_pv_fp8_cuda if pv == "fp8" else sageattn_qk_int8_pv_fp16_cuda
+        return dense(q, k, v, tensor_layout=tensor_layout, is_causal=False, qk_quant_gran=qk_quant_gran, sm_scale=sm_scale,
+                     return_lse=return_lse)
+    _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
+        o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits)
         return _pack(o[..., :head_dim_og], lse, None, None)
 
 

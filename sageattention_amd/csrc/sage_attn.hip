@@ -43,7 +43,7 @@ template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8
 //  without scratch, but left alone hipcc settles a few registers above the line)
 __global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kernel(const AttnParams p) {
-  constexpr bool SPARSE = false, PVSKIP = false, KVLEN = false;
+  constexpr bool SPARSE = false, PVSKIP = false, KVLEN = false, SPLITKV = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -55,7 +55,7 @@ template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(256, (D == 64 && PV_FP8) ? 3 : 2)
 void attn_i8_blocksparse_kernel(const AttnParams p) {
   constexpr int NWAVES = 4;
-  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false, KVLEN = false;
+  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false, KVLEN = false, SPLITKV = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -152,6 +152,13 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     if (!a.kv_lens || ((uintptr_t)a.kv_lens & 3)) return SAGE_ERR_INVALID_ARGUMENT;
     if (sparse || a.mask || a.cu_q || a.cu_k || a.kvl) return SAGE_ERR_UNSUPPORTED;
   }
+  if (a.split_kv) {  // split-KV: the fused-Q dense padded form only; its workspace is read and written 16 bytes aligned
+    if (a.num_splits < 1 || a.num_splits > SAGE_MERGE_MAX || !a.split_workspace || !aligned16(a.split_workspace) ||
+        ((uintptr_t)a.split_kv_lens & 3))
+      return SAGE_ERR_INVALID_ARGUMENT;
+    if (sparse || a.key_lens || a.is_causal || a.mask || a.cu_q || a.cu_k || a.kvl || a.v_mean || a.q_dtype < 0 || !a.km)
+      return SAGE_ERR_UNSUPPORTED;
+  }
   if (a.mask && (a.mask_kind < 1 || a.mask_kind > 3 || !a.mask_strides || a.is_causal || a.pv_fp8 || a.cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
   const bool fusedq = a.q_dtype >= 0;  // a.q is then the fp16/bf16 query tensor
   if ((a.cu_q == nullptr) != (a.cu_k == nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
@@ -171,6 +178,7 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   // the integer row max and the -inf mask pattern rely on a positive, finite dequantisation scale
   if (!a.logit_mult_is_one && !(a.sm_scale > 0.f && a.sm_scale < 1.0e30f)) return SAGE_ERR_INVALID_ARGUMENT;
   if (const int s = dim_dtype_status(a.D, a.v_dtype)) return s;
+  if (a.split_kv && (int64_t)a.split_workspace_bytes < splitkv_bytes(a.B, a.Hq, a.M, a.D, a.num_splits)) return SAGE_ERR_INVALID_ARGUMENT;
   if (a.o_dtype != SAGE_F16 && a.o_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
   if (a.qk_gran < SAGE_GRAN_PER_BLOCK || a.qk_gran > SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;
   if (a.blkq != 64 && a.blkq != 128) return SAGE_ERR_INVALID_ARGUMENT;
@@ -233,7 +241,8 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   // co-resident 4-wave workgroups of a CU drift apart on a long stream until they no longer share K/V tiles in L2 (1.90x the
   // algorithmic HBM-side bytes with 4 waves, 1.00x with 8: profiles/r03_ab/fetch_by_geometry.md) -> 8 waves beyond 24K keys per row.
   // (block-sparse: always 4 waves -- a workgroup is one block row of the map; the tuning knobs do not apply)
-  const int nw = sparse                ? 4
+  // (split-KV: always 4 waves as well -- its workgroups are there to fill the chip, and the partials are defined by the 4-wave loop)
+  const int nw = (sparse || a.split_kv) ? 4
                  : a.nwaves            ? a.nwaves
                  : g_nwaves_override ? g_nwaves_override
                                      : ((a.D == 64 || (a.pv_fp8 && keys_per_row <= 24576) || keys_per_row <= 3072) ? 4 : 8);
@@ -245,6 +254,13 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   if (c.kvlen) p.kv_lens = a.kv_lens;  // (shares the word of cu_k, null here)
   c.sparse_kvlen = sparse && a.block_key_lens;
   if (c.sparse_kvlen) p.kv_lens = a.block_kv_lens;  // (the word of cu_k again: the block-sparse form has no packed sequences)
+  c.splitkv = a.split_kv;
+  if (c.splitkv) {  // (the words of mask, its first stride, mask_kind and cu_k, all unused here)
+    p.sk_o = (float*)a.split_workspace;
+    p.sk_lse = p.sk_o + (int64_t)a.num_splits * a.B * a.Hq * a.M * a.D;
+    p.num_splits = a.num_splits;
+    p.kv_lens = a.split_kv_lens;
+  }
   c.D = a.D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;
@@ -253,6 +269,7 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
 int attn_launch(const AttnCall& c, hipStream_t st) {
   if (c.sparse) return launch_blocksparse(c, st);
   if (c.kvlen) return launch_kvlen(c, st);
+  if (c.splitkv) return launch_splitkv(c, st);
   return by_dim(c.D, [&](auto d) {
     return c.nwaves == 8 ? launch_attn<decltype(d)::value, 8>(c, st) : launch_attn<decltype(d)::value, 4>(c, st);
   });

@@ -1,10 +1,12 @@
 // The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip),
 // attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip), attn_i8_kvlen_kernel (sage_attn_kvlen.hip),
 // attn_i8_blocksparse_kvlen_kernel (sage_attn_sparse_kvlen.hip) and attn_i8_blocksparse_pvskip_kvlen_kernel
-// (sage_attn_sparse_kvlen_pvskip.hip), not a header in the usual sense.  Expects in scope: the kernel
-// parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8, HAS_MASK, SPARSE, PVSKIP, KVLEN
+// (sage_attn_sparse_kvlen_pvskip.hip) and attn_i8_splitkv_kernel (sage_attn_splitkv.hip), not a header in the usual sense.
+// Expects in scope: the kernel parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8,
+// HAS_MASK, SPARSE, PVSKIP, KVLEN, SPLITKV
 // (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip; SPARSE && KVLEN: the tile lists
-// clipped at the batch's length, sage_attn_sparse_kvlen.hip).
+// clipped at the batch's length, sage_attn_sparse_kvlen.hip; SPLITKV: one workgroup per (b, h, q-block, split) walks the
+// split's range of key tiles and stores an fp32 partial result, sage_attn_splitkv.hip).
 #ifndef SAGE_ATTN_BODY_OF_KERNEL
 #error "sage_attn_body.h is the body of the attention kernels (sage_attn*.hip): included nowhere else"
 #endif
@@ -13,6 +15,8 @@
   static_assert(!SPARSE || (NWAVES == 4 && !CAUSAL && !HAS_MASK), "block-sparse: 4 waves = one block row of the map, non-causal");
   static_assert(!PVSKIP || SPARSE, "the P.V skip exists in the block-sparse form only");
   static_assert(!KVLEN || !HAS_MASK, "per-batch key lengths: the dense or the block-sparse kernel, without attn_mask");
+  static_assert(!SPLITKV || (!CAUSAL && !HAS_MASK && !SPARSE && !KVLEN && NWAVES == 4),
+                "split-KV: 4 waves, non-causal, no attn_mask, no block map (its optional lengths are its own: p.kv_lens may be null)");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -45,12 +49,20 @@
     const int orig = blockIdx.x, xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
     lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
   }
+  // split-KV: the splits of one (b, h, q-block) are neighbours -- they read the same Q rows -- and the id above them is that of
+  // the other kernels
+  int split = 0;
+  (void)split;
+  if constexpr (SPLITKV) {
+    split = lid % p.num_splits;
+    lid /= p.num_splits;
+  }
   int qb = lid % p.nqb;
   const int bh = lid / p.nqb;
   // (b, h) of the id: heads within a batch -- except with per-batch key lengths, where the batches alternate within a head.
   // An XCD runs one contiguous range of logical ids; batch-major, an XCD would hold whole batches, and the one with the
   // longest batch would finish last whatever the others save (lengths 8192 / 6144 / 4096 / 2048: 0.96x the dense time)
-  const int h = KVLEN ? bh / p.B : bh % p.Hq, b = KVLEN ? bh % p.B : bh / p.Hq;
+  const int h = (KVLEN || SPLITKV) ? bh / p.B : bh % p.Hq, b = (KVLEN || SPLITKV) ? bh % p.B : bh / p.Hq;
   // Causal: heaviest q-blocks of a head first (load balance at the end of the grid).  An XCD holds fewer workgroups than
   // a long head has q-blocks, so a head runs in two generations and the second starts again at key 0 (C4 reads 2.06x its
   // K/V + Q bytes from the HBM side, 1.72x with 8-wave workgroups: profiles/r03_ab/fetch_by_geometry.md; at 0.35 TB/s).
@@ -84,6 +96,23 @@
     // lse = -inf: attn_kvlen_empty_kernel writes them.  (Written here, the stores cost the head_dim-64 variants the registers
     // that keep them at three waves per SIMD, and FP8 PV with per-thread scales spilled -- as in the block-sparse form below.)
     if (N_ <= 0) return;
+  }
+  // split-KV: split s of a batch with ntk_b = ceil(len_b / 64) key tiles owns the tiles [s * tps_b, min((s + 1) * tps_b, ntk_b)),
+  // tps_b = ceil(ntk_b / S) (the rule: include/sageattn_hip.h, sage_attn_fusedq_pv_*_splitkv).  The workgroup is the dense
+  // kernel on that range: sk_t0 moves the K / V slice and the K scales to the range's first tile (below) and N_ becomes the keys
+  // from there to the range's end -- a multiple of 64 for every split but the one that holds the batch's last tile, whose tail
+  // mask and descriptors then end at len_b.  Tile indices, ring slots and the ragged-tail logic are those of the dense kernel
+  // on the moved operands.  Wave-uniform, before any barrier; a workgroup whose range is empty stores nothing.
+  int sk_t0 = 0;
+  (void)sk_t0;
+  if constexpr (SPLITKV) {
+    int len_b = p.N;
+    if (p.kv_lens) len_b = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
+    const int ntk_b = (len_b + 63) >> 6, tps_b = (ntk_b + p.num_splits - 1) / p.num_splits;
+    sk_t0 = split * tps_b;
+    const int t1 = min(sk_t0 + tps_b, ntk_b);
+    if (sk_t0 >= t1) return;
+    N_ = min(len_b, t1 << 6) - (sk_t0 << 6);
   }
   // block-sparse: the list row of this (b, h, q-block) = its count, then the ascending tile indices, padded with the last
   // valid one for kBlockListPad entries so that every read-ahead below is blind.  The first entries are requested together
@@ -184,6 +213,10 @@
     }
     // (the LSE correction q . k_mean is only computed when the caller asked for the LSE)
     const uint16_t* kmp = (p.km && p.lse) ? p.km + ((int64_t)b * p.Hk + hk) * D + 16 * hh : nullptr;
+    // (split-KV: the correction of a row is computed and parked once, by the workgroup of split 0 -- the merge consumes it)
+    if constexpr (SPLITKV) {
+      if (split != 0) kmp = nullptr;
+    }
     // Everything below is instantiated per element type (ONE uniform branch here instead of one per 8-element chunk) and
     // the numerics flavour is the kernel's KTHREAD (per-thread Q scales <=> the Triton quantizer's numerics, run_attn): with
     // both as run-time flags inside the unrolled loops hipcc emitted two scalar branches per ELEMENT -- ~500 scalar
@@ -216,7 +249,13 @@
     // LSE correction q . k_mean of the row: parked in the caller's LSE slot of this row until the epilogue (a register that
     // lives through the whole tile loop costs the head_dim-64 FP8 variants their third wave per SIMD)
     const float lse_corr = swap_sum(dot);
-    if (p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
+    // (the two forms are spelled out under `if constexpr`, as is the km pointer above: with `(!SPLITKV || split == 0)` as a term
+    //  of the one condition, the FP8 head_dim-64 block-sparse kernels came out with another instruction stream)
+    if constexpr (SPLITKV) {
+      if (split == 0 && p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
+    } else {
+      if (p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
+    }
     if constexpr (triton) {  // rows with equal r % 8 inside the 32-row block (quant_per_thread.py:27-36)
       amax = fmaxf(amax, __shfl_xor(amax, 8));
       amax = fmaxf(amax, __shfl_xor(amax, 16));
@@ -270,6 +309,7 @@
   }
   };
   const float* ksp = p.k_scale + b * p.ks_b + hk * p.ks_h;
+  if constexpr (SPLITKV) ksp += (int64_t)sk_t0 * p.ks_t;
 
   // ---- tile range
   const int kv_end = CAUSAL ? min(N_, (qb + 1) * QB) : N_;
@@ -284,6 +324,10 @@
   const uint8_t* vg = p.v + (v_boff + hk * p.vsh) * (PV_FP8 ? 1 : 2);
   const int k_tile_stride = p.k_tile_bytes;  // bytes per 64 keys (dense: 64 rows)
   const int v_tile_stride = p.v_tile_bytes;
+  if constexpr (SPLITKV) {  // the slice starts with the split's first tile
+    kg += (int64_t)sk_t0 * k_tile_stride;
+    vg += (int64_t)sk_t0 * v_tile_stride;
+  }
   // last valid byte + 1 of the (b, h_kv) slice: row N-1 = row (N-1)%64 of tile (N-1)/64 (dense layouts: (N-1)*stride_n)
   const int last_t = (N_ - 1) >> 6, last_r = (N_ - 1) & 63;
   const unsigned k_bytes = (unsigned)((int64_t)last_t * k_tile_stride + (int64_t)last_r * p.ksn + D);
@@ -1215,7 +1259,30 @@
   // ---- epilogue: normalise, (+ v_mean), convert, store; LSE (…sm80.cu:540-668)
   const float l_tot = MROW ? (((row_l - q0) & 16) ? l4[1] : l4[0]) : swap_sum(l_run);
   const float inv = 1.0f / l_tot;
-  if (row_l < M_) {
+  if constexpr (SPLITKV) {
+    // split-KV: the partial result of the split goes to its workspace slot -- the normalised row in fp32, BEFORE any rounding to
+    // the output type (rounded, it has the bits the epilogue below stores), and the raw base-2 LSE.  The workspace is dense:
+    // a lane's run of 4 channels is one 16-byte store.
+    if (row_l < M_) {
+      const int64_t srow = ((((int64_t)split * p.B + b) * p.Hq + h) * M_ + row_l);
+      float* const wp = p.sk_o + srow * D + 4 * hh_l;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int d0 = 32 * dt + 8 * g4;
+          float x[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[e] = acc_o[dt][4 * g4 + e] * inv;
+          if constexpr (PV_FP8) {
+            const float4 vs = *reinterpret_cast<const float4*>(p.v_scale + ((int64_t)b * p.Hk + hk) * D + d0 + 4 * hh_l);
+            x[0] *= vs.x; x[1] *= vs.y; x[2] *= vs.z; x[3] *= vs.w;
+          }
+          *reinterpret_cast<float4*>(wp + d0) = make_float4(x[0], x[1], x[2], x[3]);
+        }
+      if (hh_l == 0) p.sk_lse[srow] = m_run + log2f(l_tot) - kPOff;
+    }
+  } else if (row_l < M_) {
     uint16_t* op = p.o + o_boff + h * p.osh + (int64_t)row_l * p.osn;
     // A lane holds runs of 4 output channels (8 B); lane ^ 32 holds the neighbouring run of the same row.  The two halves
     // exchange words (v_permlane32_swap) so that each stores 16 contiguous bytes: 8 global_store_dwordx4 per lane instead

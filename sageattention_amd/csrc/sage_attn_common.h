@@ -38,13 +38,16 @@ struct AttnParams {
   //  dense kernels keeps its size and layout)
   // bs_lists / bs_row: the tile lists of sage_block_map_compact, one row of bs_row int32 per (b, h_q, 128-row q-block):
   // [count, tile_0 < tile_1 < ..., kBlockListPad copies of the last tile]
-  union { const uint8_t* mask; const int* bs_lists; };
+  // (split-KV attention -- attn_i8_splitkv_kernel, sage_attn_splitkv.hip -- has neither an attn_mask nor lists: its workspace
+  //  shares these words as well.  sk_o fp32 [S,B,Hq,M,D], the normalised partial outputs; sk_lse fp32 [S,B,Hq,M], their raw
+  //  base-2 LSEs; num_splits = S.  Its optional kv_lens is the word of cu_k above, null = every batch has N keys)
+  union { const uint8_t* mask; const int* bs_lists; float* sk_o; };
   // (the P.V skip of the block-sparse form -- attn_i8_blocksparse_pvskip_kernel -- keeps its two pointers in the first two
   //  mask strides: pv_thresh fp32 [Hq], pv_skipped int32 [B,Hq,nqb,4] or null)
-  union { int64_t msb; const float* pv_thresh; };
+  union { int64_t msb; const float* pv_thresh; float* sk_lse; };
   union { int64_t msh; int32_t* pv_skipped; };
   int64_t msm, msn;
-  union { int mask_kind; int bs_row; };
+  union { int mask_kind; int bs_row; int num_splits; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
   // (b, h_kv) in k8 and in v (always set by attn_check; the dense defaults are 64 rows), and the strides of k_scale
   // (floats) per batch, kv head and 64-key tile.  Sequence-parallel exchange buffers are tile-major: tile j of every

@@ -129,6 +129,15 @@ struct AttnArgs {
   // are clipped at ceil(len_b / 64) tiles by the kernel (sage_attn_sparse_kvlen.hip).  Same tensor: device, int32 [B]
   bool block_key_lens = false;
   const int32_t* block_kv_lens = nullptr;
+  // split-KV (sage_attn_fusedq_pv_*_splitkv, fused Q only): num_splits workgroups per (b, h, q-block), each on its range of
+  // key tiles, then the merge of their fp32 partial results out of the caller's workspace.  Its key lengths are a field of
+  // its own and OPTIONAL (null: every batch has N keys); with key_lens, a block map, causal, attn_mask, cu_seqlens, a
+  // kv_layout or v_mean: SAGE_ERR_UNSUPPORTED
+  bool split_kv = false;
+  const int32_t* split_kv_lens = nullptr;
+  int num_splits = 0;
+  void* split_workspace = nullptr;
+  size_t split_workspace_bytes = 0;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -140,6 +149,7 @@ struct AttnCall {
   bool pvskip;  // ... its twin attn_i8_blocksparse_pvskip_kernel
   bool kvlen;   // attn_i8_kvlen_kernel: the dense kernel with per-batch key lengths
   bool sparse_kvlen;  // attn_i8_blocksparse_kvlen_kernel / ..._pvskip_kvlen_kernel: sparse (and pvskip) with key lengths
+  bool splitkv;  // attn_i8_splitkv_kernel + splitkv_merge_kernel (always 4 waves)
 };
 int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
@@ -151,6 +161,12 @@ int launch_kvlen(const AttnCall& c, hipStream_t st);
 // kernel -- with c.pvskip the twin of sage_attn_sparse_kvlen_pvskip.hip, second function -- and the rows of the emptied q-blocks
 int launch_blocksparse_kvlen(const AttnCall& c, hipStream_t st);
 int launch_blocksparse_pvskip_kvlen(const AttnCall& c, hipStream_t st);
+// the launches of a split-KV call (c.splitkv; sage_attn_splitkv.hip): the attention kernel over the splits, then the merge
+int launch_splitkv(const AttnCall& c, hipStream_t st);
+// bytes of the workspace of a split-KV call: the partial outputs fp32 [S,B,Hq,M,D], then their base-2 LSEs fp32 [S,B,Hq,M]
+inline int64_t splitkv_bytes(int B, int Hq, int M, int D, int S) {
+  return (int64_t)S * B * Hq * M * ((int64_t)D + 1) * 4;
+}
 
 // ---- block-sparse tile lists (sage_misc.hip) ---------------------------------------------------------------------------
 // bytes of the lists of one call: a row of block_list_row(N) int32 per (b, h_q, 128-row q-block)

@@ -24,6 +24,8 @@ instead of breaking the graph.  The reference marks every entry
                                                          keep_last, kv_lens, ...) -> o             kv_lens in front of the layout)
     torch.ops.sageattention_amd.attn_sparge_select_lse_kvlen(...) -> (o, lse)
     torch.ops.sageattention_amd.attn_sparge_pv_kvlen / attn_sparge_pv_lse_kvlen(..., pvthreshd, kv_lens, ...) -> (o, [lse,] skipped)
+    torch.ops.sageattention_amd.attn_splitkv(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
+    torch.ops.sageattention_amd.attn_splitkv_lse(...) -> (o, lse)   (split-KV: kv_lens an optional tensor, num_splits 0 = automatic)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -35,7 +37,7 @@ import torch
 from . import core
 
 __all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable", "sageattn_sparge_compilable",
-           "sageattn_kvlen_compilable"]
+           "sageattn_kvlen_compilable", "sageattn_splitkv_compilable"]
 
 
 def _entry(pv: str):
@@ -494,6 +496,47 @@ def sageattn_kvlen_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         sm_scale = q.size(-1) ** -0.5
     op = torch.ops.sageattention_amd.attn_kvlen_lse if return_lse else torch.ops.sageattention_amd.attn_kvlen
     return op(q, k, v, kv_lens, tensor_layout, bool(is_causal), float(sm_scale), pv, qk_quant_gran)
+
+
+@torch.library.custom_op("sageattention_amd::attn_splitkv", mutates_args=())
+def attn_splitkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor], num_splits: int,
+                 tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_splitkv(q, k, v, kv_lens=kv_lens, num_splits=num_splits or None, tensor_layout=tensor_layout,
+                                 sm_scale=sm_scale, pv=pv, qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_splitkv.register_fake
+def _(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_splitkv_lse", mutates_args=())
+def attn_splitkv_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor], num_splits: int,
+                     tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_splitkv(q, k, v, kv_lens=kv_lens, num_splits=num_splits or None, tensor_layout=tensor_layout,
+                                   sm_scale=sm_scale, pv=pv, qk_quant_gran=qk_quant_gran, return_lse=True)
+    return o.contiguous(), lse
+
+
+@attn_splitkv_lse.register_fake
+def _(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
+
+
+def sageattn_splitkv_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor] = None,
+                                num_splits: Optional[int] = None, tensor_layout: str = "HND",
+                                sm_scale: Optional[float] = None, pv: str = "fp16", qk_quant_gran: str = "per_thread",
+                                return_lse: bool = False):
+    """``sageattn_splitkv`` (core.py) as a traceable custom op: ``kv_lens`` is an optional int32 [B] tensor argument of the op,
+    ``num_splits`` an int with 0 for the automatic choice (``core.splitkv_num_splits``)."""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if num_splits is not None and not 1 <= int(num_splits) <= core.SPLITKV_MAX:
+        raise ValueError(f"num_splits must be in [1, {core.SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    if sm_scale is None:
+        sm_scale = q.size(-1) ** -0.5
+    op = torch.ops.sageattention_amd.attn_splitkv_lse if return_lse else torch.ops.sageattention_amd.attn_splitkv
+    return op(q, k, v, kv_lens, int(num_splits or 0), tensor_layout, float(sm_scale), pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",
