@@ -2,7 +2,9 @@
 
 CPU only: nothing here imports the HIP library.  tests/test_constructed_cases.py proves on the CPU that the bound is sound
 (the oracle's restatement of the kernel stays inside it) and that it has teeth (a restatement with one deliberate mistake
-leaves it); tests/test_constructed_logits_gpu.py holds the kernels to it.
+leaves it); tests/test_constructed_logits_gpu.py holds the kernels that see every key to it, and
+tests/test_constructed_subsets_gpu.py those that see a subset (block maps, key lengths, split-KV: ``subcase``, the anchored
+forms for the fused-Q entry points, ``merged_bound``, ``restate_split64`` further down).
 
 Every case is a dict (``case(family, variant, D, N, causal, gran)``):
   q8 [1,2,M,D] / k8 [1,1,N,D] int8; q_scale [1,2,Gq] / k_scale [1,1,Gk] fp32 in the compact layout of the granularity
@@ -146,6 +148,80 @@ def _finish(c, M, N, gran):
     return c
 
 
+def cached_subcase(c, tiles=None, length=None):
+    """subcase, kept in the cache of ``c`` (shared by its regran copies, whose logits are the same): for callers that only
+    READ the result"""
+    key = ("sub", None if tiles is None else tuple(tiles), length)
+    cache = c.setdefault("_cache", {})
+    if key not in cache:
+        cache[key] = subcase(c, tiles, length)
+    return cache[key]
+
+
+def _anchor_scales(c):
+    """Move powers of two from k_scale into q_scale until the smallest q_scale is 2^1; every product stays what it was."""
+    shift = 2.0 ** (1 - int(torch.log2(c["q_scale"].min())))
+    for key, f in (("q_scale", shift), ("q_scale_rows", shift), ("k_scale", 1 / shift), ("k_scale_cols", 1 / shift)):
+        c[key] = c[key] * f
+    assert float(torch.log2(c["q_scale"]).min()) == 1.0 and torch.equal(torch.log2(c["q_scale"]), torch.log2(c["q_scale"]).round())
+    assert torch.equal(c["q8"][..., -1], torch.full_like(c["q8"][..., -1], 127)) and not c["k8"][..., -1].any()
+    c["anchored"], c["_cache"] = True, {}
+    return c
+
+
+def anchor(c):
+    """The ANCHORED form of a case, for the entry points that quantize Q themselves (fused Q): head-dim channel D - 1 is
+    reserved, k8 = 0 there for every key and q8 = 127 there for every row, so that every quantization group of Q = q8 * 2^e
+    has amax 127 * 2^e and the quantizer must return q8 and 2^e exactly (``q_real``; tests/test_constructed_cases.py asserts it
+    through the oracle's quantizers).  The per-thread numerics add 1e-7 to the scale, which fp32 absorbs only for e >= 1: the
+    q scales are moved up to 2^1 and above and k_scale, which the entry point is handed directly, absorbs the rest.  The
+    overwritten channel changes the scores (a rank-one family keeps its form with D - 1 in the place of D); the reference is
+    computed from the operands, as always.  ``ramp`` and ``offset`` build their anchored form themselves (their channel 0
+    carries the remainder digit)."""
+    assert c["family"] not in ("ramp", "offset") and c["gran"] != "per_block" and not c.get("anchored")
+    d = dict(c)
+    d["q8"], d["k8"] = c["q8"].clone(), c["k8"].clone()
+    d["q8"][..., -1] = 127
+    d["k8"][..., -1] = 0
+    return _anchor_scales(d)
+
+
+def q_real(c, dtype):
+    """Q = q8 * 2^e of an anchored case in fp16 / bf16, exact (|q8| <= 127 has 7 bits, 2^e is in range)"""
+    assert c.get("anchored")
+    q = c["q8"].float() * c["q_scale_rows"].unsqueeze(-1)
+    assert torch.equal(q.to(dtype).float(), q)
+    return q.to(dtype)
+
+
+def subcase(c, tiles=None, length=None):
+    """The case restricted to the listed 64-key tiles of ``c`` (default: all), the list clipped to the first ``length`` keys
+    (default: N) so that its last tile may be ragged: again an ordinary case -- k8, k_scale_cols and the three V gathered (the
+    e4m3 V^T zero-padded to a multiple of 64), the new N -- on which scores, scale_matrix, reference64, bound, ratios, oracle
+    and restate64 work unchanged.  Only the LAST tile of a case can be ragged and the list ascends, so the tiles of the
+    subcase are again whole except the last.  Causal is kept for prefix subsets only (the ``length`` form), where ``allowed``
+    stays correct: key n of the subcase is key n of the case.  The compact q_scale is kept, the compact k_scale dropped:
+    what a kernel is handed are the operands of ``c``."""
+    N = c["N"]
+    length = N if length is None else max(0, min(int(length), N))
+    ntk = O.cdiv(length, 64)
+    tiles = list(range(ntk)) if tiles is None else [int(t) for t in tiles if t < ntk]
+    assert tiles == sorted(set(tiles)) and len(tiles) > 0, "an empty subset has no softmax"
+    prefix = tiles == list(range(len(tiles)))
+    assert prefix or not c["causal"], "a causal case keeps its meaning under a prefix only"
+    idx = torch.cat([torch.arange(64 * t, min(64 * t + 64, length)) for t in tiles])
+    n = idx.numel()
+    d = {k: v for k, v in c.items() if k not in ("k_scale", "_cache")}
+    d["_cache"] = {}
+    d["k8"], d["k_scale_cols"] = c["k8"][:, :, idx].contiguous(), c["k_scale_cols"][:, :, idx].contiguous()
+    d["v_f16"], d["v_bf16"] = c["v_f16"][:, :, idx].contiguous(), c["v_bf16"][:, :, idx].contiguous()
+    v8 = torch.zeros(B, HK, c["D"], O.cdiv(n, 64) * 64, dtype=torch.uint8)
+    v8[..., :n] = c["v_f8t"].view(torch.uint8)[..., idx]
+    d["v_f8t"] = v8.view(torch.float8_e4m3fn)
+    d.update(N=n, tiles=tuple(tiles), length=length)
+    return d
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # families
 # ---------------------------------------------------------------------------------------------------------------------
@@ -190,12 +266,36 @@ def _ramp_levels(shape, ntiles):
         lv = list(range(ntiles))
     elif shape == "descending":
         lv = list(range(ntiles - 1, -1, -1))
+    elif shape == "peak":  # 0 2 4 6 7 5 3 1: the maximum in the MIDDLE (split-KV: the dominant split is a middle one)
+        lv = [2 * j if 2 * j < ntiles else 2 * (ntiles - 1 - j) + 1 for j in range(ntiles)]
     else:  # 0 1 0 2 1 3 2 4: the maximum grows by one step on every odd tile, a tile two steps below it follows
         lv = [(j + 1) // 2 if j % 2 else max(j // 2 - 1, 0) for j in range(ntiles)]
     return [x - 3 for x in lv]  # centred so that |K| stays inside the digits' range
 
 
-def ramp(D, N, causal, gran, step="6", shape="ascending"):
+def _rank_one(D, M, N, r, K, anchor):
+    """q8 [1,Hq,M,D], k8 [1,1,N,D] with q.k = r_m * K_n exactly (see ``ramp``).  ``anchor``: the digits use D - 1 channels and
+    the last channel is the anchor of ``anchor()``: q8 = 127, k8 = 0."""
+    Dd = D - 1 if anchor else D
+    u = _u(D)[:Dd]
+    w = torch.full((Dd,), 31, dtype=torch.int32)
+    w[0] = 1
+    q8 = (r.view(M, 1) * (w * u).view(1, Dd)).view(1, 1, M, Dd).expand(B, HQ, M, Dd)
+    A = torch.round(K.double() / 31).to(torch.int64)
+    rem = K - 31 * A
+    base = torch.div(A, Dd - 1, rounding_mode="floor")
+    extra = A - base * (Dd - 1)  # 0 .. Dd-2
+    dig = base.view(N, 1) + (torch.arange(Dd - 1).view(1, Dd - 1) < extra.view(N, 1)).to(torch.int64)
+    digits = torch.cat([rem.view(N, 1), dig], dim=1)
+    assert digits.abs().max() <= 127 and (q8.abs().max() <= 127)
+    k8 = (digits.to(torch.int32) * u.view(1, Dd)).view(B, HK, N, Dd)
+    if anchor:
+        q8 = torch.cat([q8, torch.full((B, HQ, M, 1), 127, dtype=q8.dtype)], dim=-1)
+        k8 = torch.cat([k8, torch.zeros(B, HK, N, 1, dtype=k8.dtype)], dim=-1)
+    return q8.to(torch.int8).contiguous(), k8.to(torch.int8).contiguous()
+
+
+def ramp(D, N, causal, gran, step="6", shape="ascending", anchor=False):
     """Rank-one integer scores S[m,n] = r_m * K_n, known in closed form.
 
     q8[m,:] = r_m * w * u and k8[n,:] = digits(K_n) * u with u a fixed +-1 vector and w = (1, 31, 31, ..., 31), so that
@@ -203,29 +303,41 @@ def ramp(D, N, causal, gran, step="6", shape="ascending"):
     r_m*u, c_n*u reaches only products of two int8, and the steps thr -+ 2^-10 need the 13-bit primes 6143 / 3071 (and
     5*1229, 7*439) as a factor.  K_n is a staircase over the 64-key tiles, K = level(tile) * units, r_m cycles through
     (4,-4,2,-2,1,-1,0) inside every wave.  With q_scale * k_scale * logit_mult = 2^-12 the steepest rows (r = 4) see their
-    tile maximum move by exactly units * 2^-10 per level."""
+    tile maximum move by exactly units * 2^-10 per level.  ``anchor``: the anchored form (``anchor()``), one digit channel
+    fewer."""
     M = N if causal else M_FULL
     units = RAMP_UNITS[step]
-    u = _u(D)
-    w = torch.full((D,), 31, dtype=torch.int32)
-    w[0] = 1
     r = torch.tensor([RAMP_R[m % 7] for m in range(M)], dtype=torch.int32)
-    q8 = (r.view(M, 1) * (w * u).view(1, D)).view(1, 1, M, D).expand(B, HQ, M, D)
     ntiles = O.cdiv(N, 64)
     K = torch.tensor(_ramp_levels(shape, ntiles), dtype=torch.int64).repeat_interleave(64)[:N] * units
-    A = torch.round(K.double() / 31).to(torch.int64)
-    rem = K - 31 * A
-    base = torch.div(A, D - 1, rounding_mode="floor")
-    extra = A - base * (D - 1)  # 0 .. D-2
-    dig = base.view(N, 1) + (torch.arange(D - 1).view(1, D - 1) < extra.view(N, 1)).to(torch.int64)
-    digits = torch.cat([rem.view(N, 1), dig], dim=1)
-    assert digits.abs().max() <= 127 and (q8.abs().max() <= 127)
-    k8 = (digits.to(torch.int32) * u.view(1, D)).view(B, HK, N, D)
+    q8, k8 = _rank_one(D, M, N, r, K, anchor)
     qs, ks = _uniform_scales(M, N, gran, -5, -4)  # 2^-5 * 2^-4 * 2^-3 = 2^-12
-    c = dict(q8=q8.to(torch.int8).contiguous(), k8=k8.to(torch.int8).contiguous(), q_scale=qs, k_scale=ks,
-             family="ramp", causal=causal, D=D, r=r, K=K, units=units)
+    c = dict(q8=q8, k8=k8, q_scale=qs, k_scale=ks, family="ramp", causal=causal, D=D, r=r, K=K, units=units)
     c.update(_v_triple(_v_normal(N, D, 400 + D)))
-    return _finish(c, M, N, gran)
+    c = _finish(c, M, N, gran)
+    return _anchor_scales(c) if anchor else c
+
+
+OFFSET_LEVEL = 140000  # * 2^-7: every logit of a row with r = +-1 is about +-1094 (base 2)
+
+
+def offset(D, N, gran):
+    """Anchored rank-one scores with a LARGE COMMON LEVEL and a coarser LSB (2^-7): K_n = 140000 + level(tile) + n % 3 (the
+    sawtooth levels, -3..4), r_m cycling through (4,-4,2,-2,1,-1) -- no zero row.  Every row's logits are |r| * 1094 or more in
+    magnitude while they differ by at most 4 * 9 * 2^-7 = 0.28 along the row: the LSEs of any two splits of equal key count
+    lie within 0.28 of each other, at 2^10 .. 2^12.  A merge that exponentiates before subtracting the maximum overflows or
+    returns 0 / 0, and the finish mx + log2(sum) rounds at 2^-13 .. 2^-11 absolute.  delta of ``bound`` is 0.75 * 2^-7 +
+    2^-24 * Smax * 2^-7 < 2^-6."""
+    M = M_FULL
+    r = torch.tensor([(4, -4, 2, -2, 1, -1)[m % 6] for m in range(M)], dtype=torch.int32)
+    n = torch.arange(N, dtype=torch.int64)
+    lv = torch.tensor(_ramp_levels("sawtooth", O.cdiv(N, 64)), dtype=torch.int64).repeat_interleave(64)[:N]
+    K = OFFSET_LEVEL + lv + n % 3
+    q8, k8 = _rank_one(D, M, N, r, K, True)
+    qs, ks = _uniform_scales(M, N, gran, 0, -4)  # 2^0 * 2^-4 * 2^-3 = 2^-7
+    c = dict(q8=q8, k8=k8, q_scale=qs, k_scale=ks, family="offset", causal=False, D=D, r=r, K=K)
+    c.update(_v_triple(_v_normal(N, D, 450 + D)))
+    return _anchor_scales(_finish(c, M, N, gran))
 
 
 def extreme_s(D, N, causal, gran, variant="corner"):
@@ -251,6 +363,8 @@ ONE_HOT_KEYS = ("first", "63", "ragged", "last")
 
 
 def one_hot_key(N, where):
+    if isinstance(where, int):
+        return where
     return {"first": 0, "63": 63, "ragged": 64 * (N // 64), "last": N - 1}[where]
 
 
@@ -361,7 +475,7 @@ def row_lsb(c):
     return sc.amax(-1)
 
 
-def bound(c, pv, D=None, delta_zero=False):
+def bound(c, pv, D=None, delta_zero=False, out_ulps=2):
     """Per-element tolerance of a kernel's (o, lse2) against reference64 -> (o_bound [1,Hq,M,D], lse_bound [1,Hq,M]).
 
     Every number is a format width or a constant of csrc/sage_attn_body.h:
@@ -394,7 +508,8 @@ def bound(c, pv, D=None, delta_zero=False):
     delta moves l by 2^(+-delta); N fp32 additions of positive terms each lose <= 2^-24 relative, log2(e) * N * 2^-24 in
     the logarithm (v_log_f32's own ulp is inside the 2 fp32 ulps).
     ``delta_zero``: for operands whose logits are all equal on a row no relative movement between tiles can change the
-    weights' ratios -- used by the degenerate-input operator tests, where the issue sets delta = 0."""
+    weights' ratios -- used by the degenerate-input operator tests, where the issue sets delta = 0.
+    ``out_ulps``: 0 for a result that is stored in fp32 (the split-KV partials in the workspace)."""
     D = c["D"] if D is None else D
     ref = reference64(c, pv)
     t = P_BITS[pv]
@@ -412,11 +527,21 @@ def bound(c, pv, D=None, delta_zero=False):
         sub = torch.zeros_like(ref["sumabsv"])
     else:
         sub = 2.0 ** -10 * 2.0 ** -(FP8_OFFSET - 3.0) * ref["sumabsv"]
-    o_b = rel.unsqueeze(-1) * ref["wabsv"] + sub + 2 * out_ulp(ref["o"], pv, c.get("out_dtype"))
+    o_b = rel.unsqueeze(-1) * ref["wabsv"] + sub + out_ulps * out_ulp(ref["o"], pv, c.get("out_dtype"))
     l_b = delta + K_LOG2E * c["N"] * 2.0 ** -24 + 2 * _ulp(ref["lse2"], 23, -126)
     if D == 64 and pv == "fp16":
         l_b = l_b + math.log2(1 + 2.0 ** -11)
     return o_b, l_b
+
+
+def ratio_tensors(c, pv, o, lse2, out_ulps=2):
+    """|o - o64| / bound [1,Hq,M,D] and |lse2 - lse2_64| / bound [1,Hq,M], element by element; non-finite -> inf"""
+    ref = reference64(c, pv)
+    o_b, l_b = bound(c, pv, out_ulps=out_ulps)
+    inf = torch.tensor(float("inf"), dtype=torch.float64)
+    o, lse2 = o.double(), lse2.double()
+    return (torch.where(torch.isfinite(o), (o - ref["o"]).abs() / o_b, inf),
+            torch.where(torch.isfinite(lse2), (lse2 - ref["lse2"]).abs() / l_b, inf))
 
 
 def ratios(c, pv, o, lse2):
@@ -566,3 +691,303 @@ def uniform_case(v, causal, M):
     return dict(q8=torch.zeros(B, HQ, M, D, dtype=torch.int8), k8=torch.zeros(B, HK, N, D, dtype=torch.int8),
                 q_scale_rows=torch.ones(B, HQ, M), k_scale_cols=torch.ones(B, HK, N), logit_mult=1.0, causal=causal,
                 M=M, N=N, D=D, family="degenerate", v_f16=v, v_bf16=v, v_f8t=v8t, v_scale=vsc, out_dtype=v.dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# split-KV: the key ranges, the bound of the merged result, and a float64 restatement that can make one deliberate mistake
+# ---------------------------------------------------------------------------------------------------------------------
+
+U32 = 2.0 ** -24
+
+
+def split_ranges(length, S):
+    """[(t0, t1)] of the NON-EMPTY splits of ``length`` keys under S splits (include/sageattn_hip.h, split-KV attention):
+    ntk = ceil(length / 64), tps = ceil(ntk / S), split s owns the tiles [s * tps, min((s + 1) * tps, ntk))"""
+    ntk = O.cdiv(length, 64)
+    tps = O.cdiv(ntk, S) if ntk else 0
+    return [(s * tps, min((s + 1) * tps, ntk)) for s in range(S) if tps and s * tps < ntk]
+
+
+def split_subcases(c, S, length=None):
+    """the subcase of every non-empty split, in split order"""
+    length = c["N"] if length is None else length
+    return [cached_subcase(c, range(t0, t1), length) for t0, t1 in split_ranges(length, S)]
+
+
+def _merge_eps(lmax):
+    """seqpar_ref.merge_eps on base-2 LSEs: the device's exp / log allowance EPS_EXP plus the fp32 roundings of l_s - mx and
+    of mx + log2(sum), each 2^-24 of at most max_s |l_s| (a rounding of the exponent by x moves the weight by 2^x - 1 <= x)"""
+    from seqpar_ref import EPS_EXP
+    return EPS_EXP + 3 * U32 * (1 + lmax)
+
+
+def merged_bound(c, pv, splits, out_dtype=None):
+    """Per-element tolerance of a split-KV result (the merged o in ``out_dtype`` and the merged RAW base-2 lse2) against
+    reference64 of ``c`` (the full case, or its ``length`` subcase) -> (o_bound [1,Hq,M,D], lse2_bound [1,Hq,M]).
+
+    With o_s, l_s the exact (fp64) partial results of the non-empty splits s, W_s = 2^(l_s - lse2) their exact weights
+    (sum_s W_s = 1, sum_s W_s o_s = o64), B_s / L_s the ``bound`` of split s's subcase WITHOUT output ulps (the workspace is
+    fp32; L_s keeps its two fp32 ulps, the partial LSE is stored in fp32) and x_s, k_s what the kernel stored:
+
+      |o - o64| <= (1 + rho) * sum_s W_s B_s  +  (rho + eps) * sum_s W_s (|o_s| + B_s)  +  half an output ulp
+      |lse2 - lse2_64| <= max_s L_s + log2(e) * eps + 2^-23 |lse2_64|
+
+    * |x_s - o_s| <= B_s and |k_s - l_s| <= L_s: ``bound`` on the subcase, proved sound there.
+    * rho = 2^(L_a + L_b) - 1, L_a and L_b the two largest L_s of the row (0 with one non-empty split, whose weight is 1):
+      the kernel's normalised weight of split s is 2^(k_s) / sum_r 2^(k_r); numerator and denominator move by at most
+      2^(+-L) each and two splits may err in opposite directions, so it lies within (1 +- rho) W_s.  First term: the
+      partials' own errors under the moved weights; second: the moved weights on the partials themselves.
+    * eps = seqpar_ref.EPS_EXP + 3 * 2^-24 * (1 + max_s |l_s|) + (S + 2) * 2^-24: the merge's own fp32 arithmetic -- the
+      project's allowance for the device's exp / log pair (no new measured constant), the roundings of l_s - mx and of
+      mx + log2(sum) as seqpar_ref.merge_eps counts them (in base-2 units), and one rounding per addition of the <= S terms of
+      sum_s w_s x_s, of the reciprocal and of the product with it, each at most 2^-24 of sum_s w_s |x_s|.
+    * half an output ulp: the ONE rounding to ``out_dtype``, taken at |o64| + (the rest of the bound): the result may lie a
+      binade above the reference (splitkv_util.merged_reference), never above that sum.
+    * LSE: log2 sum_s 2^(k_s) is 1-Lipschitz in the sup norm of k, hence max_s L_s; a relative error eps of the sum is
+      log2(e) * eps in its logarithm; 2^-23 |lse2_64| is the rounding of mx + log2f(sum) and log2f's own ulp.
+    The finished natural-log LSE (lse2 / log2(e) + (q.km) * sm_scale) gets ``finish_bound`` on top."""
+    out_dtype = OUT_DTYPE[pv] if out_dtype is None else out_dtype
+    key, cache = ("merged_bound", pv, splits, out_dtype), c.setdefault("_cache", {})
+    if key not in cache:
+        cache[key] = _merged_bound(c, pv, splits, out_dtype)
+    return cache[key]
+
+
+def _merged_bound(c, pv, splits, out_dtype):
+    ref = reference64(c, pv)
+    subs = split_subcases(c, splits)
+    if len(subs) == 1:
+        o_b, l_b = bound(subs[0], pv, out_ulps=0)
+        rest = o_b
+    else:
+        refs = [reference64(s, pv) for s in subs]
+        bnds = [bound(s, pv, out_ulps=0) for s in subs]
+        l = torch.stack([r["lse2"] for r in refs])                       # [S,1,Hq,M]
+        W = torch.exp2(l - ref["lse2"]).unsqueeze(-1)
+        Bs = torch.stack([b[0] for b in bnds])
+        Ls = torch.stack([b[1] for b in bnds])
+        top = Ls.topk(2, dim=0).values
+        rho = (torch.exp2(top[0] + top[1]) - 1).unsqueeze(-1)
+        eps = (_merge_eps(l.abs().amax(0)) + (len(subs) + 2) * U32).unsqueeze(-1)
+        wabs = (W * (torch.stack([r["o"] for r in refs]).abs() + Bs)).sum(0)
+        rest = (1 + rho) * (W * Bs).sum(0) + (rho + eps) * wabs
+        l_b = Ls.amax(0) + K_LOG2E * eps.squeeze(-1) + 2 * U32 * ref["lse2"].abs()
+    o_b = rest + 0.5 * out_ulp(ref["o"].abs() + rest, pv, out_dtype)
+    return o_b, l_b
+
+
+def finish_lse64(lse2, qkm):
+    """the natural-log LSE of the fused-Q entry points in float64: lse2 / log2(e) + (q . km) * sm_scale (``qkm`` holds the
+    product)"""
+    return lse2 / math.log2(math.e) + qkm
+
+
+def finish_bound(l2_b, lse2_64, qkm):
+    """bound of the FINISHED LSE given the bound of the raw lse2: ln 2 times it, plus the four fp32 roundings of the finish
+    lse2 / log2(e) + (q.km) * sm_scale (the constant, the product, the quotient, the sum), each at most 2^-24 of the largest
+    magnitude involved -- as test_operators_on_zero_q_rows_and_constant_k counts them"""
+    nat = lse2_64 / math.log2(math.e)
+    mag = torch.maximum(torch.maximum(nat.abs(), qkm.abs()), (nat + qkm).abs())
+    return l2_b * math.log(2) + 4 * U32 * mag
+
+
+def merged_ratios(c, pv, splits, o, lse, qkm, out_dtype=None):
+    """largest |o - o64| / merged_bound and |lse - lse64| / finish_bound(merged_bound) over ALL elements; ``lse`` is the
+    finished natural-log LSE, ``qkm`` the exact (q . km) * sm_scale [1,Hq,M]; non-finite -> inf"""
+    ref = reference64(c, pv)
+    o_b, l2_b = merged_bound(c, pv, splits, out_dtype)
+    o, lse = o.double(), lse.double()
+    if not (torch.isfinite(o).all() and torch.isfinite(lse).all()):
+        return float("inf"), float("inf")
+    l_b = finish_bound(l2_b, ref["lse2"], qkm)
+    return float(((o - ref["o"]).abs() / o_b).max()), float(((lse - finish_lse64(ref["lse2"], qkm)).abs() / l_b).max())
+
+
+SUBSET_MISTAKES = ("list_position_for_tile_index", "length_rounded_up_to_tile")
+SPLIT_MISTAKES = ("split_scales_from_tile0", "split_tail_unmasked", "merge_equal_weights", "merge_base_e_weights",
+                  "merge_drops_last_split", "correction_added_per_split", "length_rounded_up_to_tile")
+
+
+def _pad_keys(d):
+    """the subcase with the zero padding of its last tile admitted as keys: k8 = 0 (S = 0), V = 0, the last key's scale"""
+    n = d["N"]
+    pad = O.cdiv(n, 64) * 64 - n
+    if pad == 0:
+        return d
+    e = dict(d)
+    e["_cache"] = {}
+    z = lambda t: torch.cat([t, torch.zeros(B, HK, pad, t.shape[-1], dtype=t.dtype)], dim=2)
+    e["k8"], e["v_f16"], e["v_bf16"] = z(d["k8"]), z(d["v_f16"]), z(d["v_bf16"])
+    e["k_scale_cols"] = torch.cat([d["k_scale_cols"], d["k_scale_cols"][:, :, -1:].expand(B, HK, pad)], dim=-1)
+    e["N"] = n + pad
+    return e
+
+
+def restate_subset64(c, pv, tiles=None, length=None, mistake=None):
+    """restate64 (float64, no rounding) of a kernel that walks the listed tiles of ``c`` up to ``length`` keys -- without a
+    mistake it equals reference64 of subcase(c, tiles, length); ``mistake`` makes one of SUBSET_MISTAKES:
+    list_position_for_tile_index (the j-th listed tile takes the K scales of tile j), length_rounded_up_to_tile (the keys up
+    to the next multiple of 64 -- real keys of ``c``, not padding -- are admitted)."""
+    if mistake == "length_rounded_up_to_tile" and length is not None:
+        length = min(O.cdiv(length, 64) * 64, c["N"])
+    d = subcase(c, tiles, length)
+    if mistake == "list_position_for_tile_index":
+        d["k_scale_cols"] = c["k_scale_cols"][:, :, :O.cdiv(d["N"], 64) * 64][:, :, :d["N"]].contiguous()
+    return restate64(d, pv)
+
+
+def restate_split64(c, pv, S, lengths=None, mistake=None, qkm=None):
+    """Split-KV in float64 with no rounding: the tile range of every split by the rule of include/sageattn_hip.h, restate64
+    on each range, the merge in base 2 in split order (mx = max_s l_s, w_s = 2^(l_s - mx), o = sum w_s o_s / sum w_s, lse2 =
+    mx + log2 sum w_s).  Without a mistake it equals reference64 of subcase(c, length=...) to float64 accuracy; ``mistake``
+    makes exactly one of SPLIT_MISTAKES.  ``lengths``: None (all keys), one length, or a list (-> a list of results).
+    -> (o, lse2), or (o, lse2, lse) with ``qkm`` [1,Hq,M], the exact (q . km) * sm_scale: lse is the finished LSE."""
+    if isinstance(lengths, (list, tuple)):
+        return [restate_split64(c, pv, S, n, mistake, qkm) for n in lengths]
+    true_len = c["N"] if lengths is None else min(int(lengths), c["N"])
+    length = true_len
+    if mistake == "length_rounded_up_to_tile":
+        length = min(O.cdiv(length, 64) * 64, c["N"])
+    parts = []
+    ranges = split_ranges(length, S)
+    for i, (t0, t1) in enumerate(ranges):
+        d = subcase(c, range(t0, t1), length)
+        if mistake == "split_scales_from_tile0":
+            d["k_scale_cols"] = c["k_scale_cols"][:, :, :d["N"]].contiguous()
+        if mistake == "split_tail_unmasked" and i == len(ranges) - 1:
+            d = _pad_keys(d)
+        parts.append(restate64(d, pv))
+    if mistake == "merge_drops_last_split" and len(parts) > 1:
+        parts = parts[:-1]
+    o = torch.stack([p[0] for p in parts])
+    l = torch.stack([p[1] for p in parts])
+    mx = l.amax(0)
+    if mistake == "merge_equal_weights":
+        w = torch.ones_like(l)
+    elif mistake == "merge_base_e_weights":
+        w = torch.exp(l - mx)
+    else:
+        w = torch.exp2(l - mx)
+    sm = w.sum(0)
+    res = ((w.unsqueeze(-1) * o).sum(0) / sm.unsqueeze(-1), mx + torch.log2(sm))
+    if qkm is None:
+        return res
+    times = len(ranges) if mistake == "correction_added_per_split" else 1
+    return res + (res[1] / math.log2(math.e) + times * qkm,)
+
+
+def merge_fp32(o_parts, l2_parts):
+    """The merge kernel's arithmetic in numpy float32, in split order (sage_attn_splitkv.hip): for the CPU soundness test.
+    o_parts [S,...,D] and l2_parts [S,...] fp32 tensors -> (o fp32, lse2 fp32)"""
+    import numpy as np
+    o, l = o_parts.numpy().astype(np.float32), l2_parts.numpy().astype(np.float32)
+    mx = l.max(0)
+    acc, sm = np.zeros_like(o[0]), np.zeros_like(mx)
+    for s in range(l.shape[0]):
+        w = np.exp2(l[s] - mx).astype(np.float32)
+        sm = (sm + w).astype(np.float32)
+        acc = (acc + o[s] * w[..., None]).astype(np.float32)
+    inv = (np.float32(1) / sm).astype(np.float32)
+    return torch.from_numpy(acc * inv[..., None]), torch.from_numpy((mx + np.log2(sm)).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the subset configurations (shared by the CPU soundness test and tests/test_constructed_subsets_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+SUBSET_N = 456  # 7 whole tiles and a ragged one of 8 keys (tile 7); M = 150: two q-blocks
+# name -> tile lists [head][q-block]
+SUBSET_MAPS = {
+    "alternate": [[[1, 3, 5, 7]] * 2] * 2,
+    "ragged_only": [[[7]] * 2] * 2,
+    "first_last": [[[0, 7]] * 2] * 2,
+    "middle": [[[3]] * 2] * 2,
+    "mixed": [[[0, 2, 4, 6], [1, 3, 5, 7]], [[2, 3], [0, 5, 7]]],  # differs between the q-blocks and between the heads
+}
+KVLEN_LENGTHS = (SUBSET_N, 257, 64, 1)
+SPLIT_CONFIGS = ((512, (2, 3, 4, 5, 8, 9, 16)), (456, (2, 3, 7)))  # (N, the split counts run at it)
+SPLIT_LENGTHS = (None, 257, 0)  # per batch: all keys, 257, none
+
+
+def map_tensor(name, ntk=None):
+    """bool [1, Hq, 2, ntk] of a SUBSET_MAPS entry"""
+    ntk = O.cdiv(SUBSET_N, 64) if ntk is None else ntk
+    bm = torch.zeros(1, HQ, 2, ntk, dtype=torch.bool)
+    for h in range(HQ):
+        for qb in range(2):
+            bm[0, h, qb, SUBSET_MAPS[name][h][qb]] = True
+    return bm
+
+
+def subset_cases(family, D, pv, grans=("per_warp", "per_thread"), causal=False, N=SUBSET_N):
+    """Yield (label, case) of the families run through a block map or a key length, at N = 456.
+    scale_ladder per granularity; ramp ascending at the steps around the lazy threshold of the PV type and at 40, sawtooth at
+    40; one_hot with the hot key at 0 (tile 0), 200 (tile 3), 257 (tile 4: the first key past the length 257) and 448 (the
+    ragged tile): every map lists some of them and not the others; extreme_s corner and zero."""
+    tag = "causal" if causal else "full"
+    if family == "scale_ladder":
+        for gran in grans:
+            yield f"{tag}-{gran}", scale_ladder(D, N, causal, gran)
+        return
+    t = "6" if pv != "fp8" else "3"
+    base = {
+        "ramp": [(f"{shape}-step{st}", lambda st=st, shape=shape: ramp(D, N, causal, grans[0], st, shape))
+                 for st, shape in ((t + "-", "ascending"), (t, "ascending"), (t + "+", "ascending"), ("40", "ascending"),
+                                   ("40", "sawtooth"))],
+        "one_hot": [(f"hot{k}", lambda k=k: one_hot(D, N, causal, grans[0], k)) for k in (0, 200, 257, 448)],
+        "extreme_s": [(v, lambda v=v: extreme_s(D, N, causal, grans[0], v)) for v in ("corner", "zero")],
+    }[family]
+    for label, build in base:
+        c = build()
+        for gran in grans:
+            yield f"{label}-{tag}-{gran}", (c if gran == grans[0] else regran(c, gran))
+
+
+SUBSET_FAMILIES = ("scale_ladder", "ramp", "one_hot", "extreme_s")
+SPLIT_FAMILIES = ("ramp", "offset", "scale_ladder", "one_hot", "extreme_s")
+
+
+def split_cases(family, D, N, gran):
+    """Yield (label, anchored case) of the families run through split-KV at N keys (non-causal, M = 150).
+    ramp: step 40, ascending / descending / sawtooth and "peak" (levels 0 2 4 6 7 5 3 1) -- for the rows with r > 0 the dominant
+    split is the last, the first, the last and a MIDDLE one (the sawtooth's maximum is its last tile); ascending at step
+    0.5: weights within a factor of 2^14 of each other, where a merge in the wrong base shows; offset (N = 512 only);
+    scale_ladder; one_hot with the hot key in the first, a middle and the last split whatever S (keys 0, 200, N - 1);
+    extreme_s zero: uniform weights, the merged o is the mean over all keys."""
+    if family == "ramp":
+        for shape in RAMP_SHAPES + ("peak",):
+            yield f"{shape}-step40", ramp(D, N, False, gran, "40", shape, anchor=True)
+        yield "ascending-step0.5", ramp(D, N, False, gran, "0.5", "ascending", anchor=True)
+    elif family == "offset":
+        if N == 512:
+            yield "offset", offset(D, N, gran)
+    elif family == "scale_ladder":
+        yield "ladder", anchor(scale_ladder(D, N, False, gran))
+    elif family == "one_hot":
+        for k in (0, 200, N - 1):
+            yield f"hot{k}", anchor(one_hot(D, N, False, gran, k))
+    elif family == "extreme_s":
+        yield "zero", anchor(extreme_s(D, N, False, gran, "zero"))
+    else:
+        raise ValueError(family)
+
+
+def split_km(D, nonzero):
+    """km [1,1,D] fp32: zeros, or multiples of 1/8 in [-2, 2] (q . km is then exact in fp32 in any summation order: every
+    product q8 * 2^e * km is a multiple of 2^(e-3) below 2^(e+8), the sum of 128 of them below 2^24 such units)"""
+    if not nonzero:
+        return torch.zeros(1, HK, D)
+    g = torch.Generator().manual_seed(970 + D)
+    return torch.randint(-16, 17, (1, HK, D), generator=g).float() / 8
+
+
+def split_qkm(c, km):
+    """the exact (q . km) * sm_scale [1,Hq,M] in float64, sm_scale at its fp32 value"""
+    q = c["q8"].double() * c["q_scale_rows"].double().unsqueeze(-1)
+    return (q * km.double().repeat_interleave(HQ // HK, dim=1).unsqueeze(2)).sum(-1) * float(c["sm_scale"])
+
+
+def split_gaps(c, pv, S, length=None):
+    """largest difference between the fp64 LSEs (base 2) of two non-empty splits, per row [1,Hq,M]"""
+    l = torch.stack([reference64(d, pv)["lse2"] for d in split_subcases(c, S, length)])
+    return l.amax(0) - l.amin(0)

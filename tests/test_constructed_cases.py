@@ -153,3 +153,241 @@ def test_coarse_lsb_and_delta():
 
 def test_logit_mult_is_a_power_of_two_in_fp32():
     assert np.float32(C.SM_SCALE) * np.float32(1.4426950408889634) == np.float32(0.125) == np.float32(C.LOGIT_MULT)
+
+
+# ---- subsets of the keys: block maps, key lengths, split-KV ------------------------------------------------------------
+
+_SUB = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _sub_table():
+    yield
+    if _SUB:
+        print("\noracle (hip flavour) on the SUBCASES: largest |err| / bound   [o, lse2]")
+        for (what, fam, pv, D), (ro, rl) in sorted(_SUB.items()):
+            print(f"  {what:10s} {fam:13s} {pv:5s} D={D:<4d} {ro:6.3f} {rl:6.3f}")
+
+
+def _sub_record(what, fam, pv, D, ro, rl):
+    a, b = _SUB.get((what, fam, pv, D), (0.0, 0.0))
+    _SUB[(what, fam, pv, D)] = (max(a, ro), max(b, rl))
+
+
+def _oracle32(c, pv):
+    """the oracle's partial result as the split-KV workspace holds it: not rounded to an output type"""
+    return C.O.attn_tile_loop(c["q8"], c["k8"], C.v_of(c, pv), c["q_scale_rows"], c["k_scale_cols"], logit_mult=c["logit_mult"],
+                              is_causal=c["causal"], pv="fp8" if pv == "fp8" else "fp16",
+                              v_scale=c["v_scale"] if pv == "fp8" else None, out_dtype=torch.float32, flavor="hip")
+
+
+def _tile_lists():
+    seen = []
+    for m in C.SUBSET_MAPS.values():
+        for per_head in m:
+            for tiles in per_head:
+                if tiles not in seen:
+                    seen.append(tiles)
+    return seen
+
+
+def test_subcase_is_the_case_on_the_gathered_keys():
+    """subcase against a reference computed the long way: the full case with the unlisted keys masked out"""
+    c = C.scale_ladder(64, 456, False, "per_thread")
+    for tiles, length in (([0, 2, 4, 6], None), ([7], None), ([1, 3, 5, 7], 257), (None, 257), (None, 1)):
+        d = C.subcase(c, tiles, length)
+        n = torch.arange(456)
+        keep = (n < (456 if length is None else length))
+        if tiles is not None:
+            keep &= torch.isin(n // 64, torch.tensor(tiles))
+        assert d["N"] == int(keep.sum()) and d["v_f8t"].shape[-1] % 64 == 0
+        for pv in C.PVS:
+            t = (C.scores(c) * C.scale_matrix(c)).masked_fill(~keep.view(1, 1, 1, -1), float("-inf"))
+            W = torch.softmax(t * math.log(2), dim=-1)
+            ref = C.reference64(d, pv)
+            assert (W @ C.v64(c, pv) - ref["o"]).abs().max() < 1e-12
+            assert (torch.logsumexp(t * math.log(2), -1) / math.log(2) - ref["lse2"]).abs().max() < 1e-11
+    cc = C.subcase(C.scale_ladder(64, 456, True, "per_warp"), length=257)
+    assert cc["causal"] and cc["M"] == 456 and cc["N"] == 257
+    with pytest.raises(AssertionError):
+        C.subcase(C.scale_ladder(64, 456, True, "per_warp"), [1, 2])
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("pv", C.PVS)
+@pytest.mark.parametrize("family", C.SUBSET_FAMILIES)
+def test_oracle_within_bound_on_map_and_length_subcases(family, pv, D):
+    """every subcase tests/test_constructed_subsets_gpu.py checks a kernel against: each tile list of SUBSET_MAPS, each key
+    length (causal and not), and the lists clipped to the lengths"""
+    grans = ("per_warp", "per_thread") if family == "scale_ladder" else ("per_warp",)
+    for causal in (False, True):
+        for label, c in C.subset_cases(family, D, pv, grans, causal):
+            subs = [("length", None, n) for n in C.KVLEN_LENGTHS]
+            if not causal:
+                subs += [("map", t, None) for t in _tile_lists()]
+                subs += [("map+length", [x for x in t if 64 * x < n], n) for t in _tile_lists() for n in C.KVLEN_LENGTHS[1:]]
+            for what, tiles, n in subs:
+                if tiles is not None and not tiles:
+                    continue  # a q-block without a tile below the length: o = 0, lse = -inf, no softmax
+                d = C.subcase(c, tiles, n)
+                ro, rl = C.ratios(d, pv, *C.oracle(d, pv))
+                _sub_record(what, family, pv, D, ro, rl)
+                assert ro <= 1.0 and rl <= 1.0, (label, what, tiles, n, ro, rl)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("gran", ["per_warp", "per_thread"])
+def test_anchored_cases_come_back_from_the_quantizers(gran, D):
+    """Q = q8 * 2^e of every anchored case the GPU test uses, through the oracle's Q quantizers (per_warp: the CUDA numerics;
+    per_thread: the Triton numerics, scale + 1e-7): q8 and the scales 2^e exactly, in fp16 and in bf16; and every scale
+    product of the case is still a power of two"""
+    quant = C.O.per_warp_int8 if gran == "per_warp" else C.O.per_thread_int8
+    for family in C.SPLIT_FAMILIES:
+        for N, _ in C.SPLIT_CONFIGS:
+            for label, c in C.split_cases(family, D, N, gran):
+                assert float(c["q_scale"].min()) >= 2.0
+                sc = C.scale_matrix(c)
+                assert torch.equal(torch.log2(sc), torch.log2(sc).round()), label
+                for dt in (torch.float16, torch.bfloat16):
+                    q8, qs, _, _ = quant(C.q_real(c, dt), torch.zeros(1, 1, 64, D, dtype=dt))
+                    assert torch.equal(q8, c["q8"]), (label, dt)
+                    assert torch.equal(C.O.expand_q_scale(qs, c["M"], gran), c["q_scale_rows"]), (label, dt)
+    c0 = C.ramp(D, 512, False, gran, "40", anchor=True)
+    q0 = (c0["q8"].float() * 1.0).half()  # e = 0: the per-thread scale comes back as 1.0000001
+    _, qs, _, _ = C.O.per_thread_int8(q0, torch.zeros(1, 1, 64, D).half())
+    assert float(qs[0, 0, 0]) == float(np.float32(1.0000001)) != 1.0
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("pv", C.PVS)
+@pytest.mark.parametrize("family", C.SPLIT_FAMILIES)
+def test_oracle_partials_and_fp32_merge_within_merged_bound(family, pv, D):
+    """every split configuration the GPU test runs: the oracle's fp32 partial of each split inside ``bound`` (no output
+    ulps) of its subcase, and the merge kernel's arithmetic in numpy float32 over those partials, rounded once to fp16 and
+    to bf16, inside ``merged_bound`` -- o, the raw lse2 and the finished LSE with a non-zero q.km"""
+    km = C.split_km(D, True)
+    for N, splits in C.SPLIT_CONFIGS:
+        for label, c in C.split_cases(family, D, N, "per_warp"):
+            qkm_full = C.split_qkm(c, km)
+            for n in C.SPLIT_LENGTHS[:2]:
+                cn = c if n is None else C.subcase(c, length=n)
+                ref = C.reference64(cn, pv)
+                parts = {}
+                for S in splits:
+                    subs = C.split_subcases(cn, S)
+                    os_, ls = [], []
+                    for d in subs:
+                        if d["tiles"] not in parts:
+                            parts[d["tiles"]] = _oracle32(d, pv)
+                            o_b, l_b = C.bound(d, pv, out_ulps=0)
+                            r = C.reference64(d, pv)
+                            ro = float(((parts[d["tiles"]][0].double() - r["o"]).abs() / o_b).max())
+                            rl = float(((parts[d["tiles"]][1].double() - r["lse2"]).abs() / l_b).max())
+                            _sub_record("partial", family, pv, D, ro, rl)
+                            assert ro <= 1.0 and rl <= 1.0, (label, n, S, d["tiles"], ro, rl)
+                        os_.append(parts[d["tiles"]][0])
+                        ls.append(parts[d["tiles"]][1])
+                    o32, l32 = C.merge_fp32(torch.stack(os_), torch.stack(ls))
+                    lse = torch.from_numpy((l32.numpy() / np.float32(1.44269504)
+                                            + (qkm_full.numpy() / c["sm_scale"]).astype(np.float32) * np.float32(c["sm_scale"])).astype(np.float32))
+                    for dt in (torch.float16, torch.bfloat16):
+                        ro, rl = C.merged_ratios(cn, pv, S, o32.to(dt), lse, qkm_full, dt)
+                        _sub_record("merged", family, pv, D, ro, rl)
+                        assert ro <= 1.0 and rl <= 1.0, (label, n, S, dt, ro, rl)
+                    l2_b = C.merged_bound(cn, pv, S)[1]
+                    assert ((l32.double() - ref["lse2"]).abs() <= l2_b).all(), (label, n, S)
+
+
+def test_split_ramps_cover_the_regimes_of_the_merge():
+    """from the fp64 reference alone: over the step-40 ramps (ascending, descending, sawtooth, peak) and the split counts run at
+    N = 512, the largest LSE gap between two non-empty splits of a row lies below 1, in 1..24, in 24..126, in the window
+    126..149 where fp32 weights are subnormal, and above 150; the dominant split is the first, a middle one and the last"""
+    seen, dominant = set(), set()
+    for label, c in C.split_cases("ramp", 64, 512, "per_warp"):
+        for S in C.SPLIT_CONFIGS[0][1]:
+            g = C.split_gaps(c, "fp16", S)
+            for name, lo, hi in (("<1", -1, 1), ("1..24", 1, 24), ("24..126", 24, 126), ("126..149", 126, 149), (">150", 150, 1e9)):
+                if bool(((g > lo) & (g < hi)).any()):
+                    seen.add(name)
+            l = torch.stack([C.reference64(d, "fp16")["lse2"] for d in C.split_subcases(c, S)])
+            arg = l.argmax(0)[g > 150]
+            dominant |= {"first" if a == 0 else "last" if a == l.shape[0] - 1 else "middle" for a in arg.tolist()}
+    assert seen == {"<1", "1..24", "24..126", "126..149", ">150"}, seen
+    assert dominant == {"first", "middle", "last"}, dominant
+
+
+def test_offset_case_has_large_lses_small_gaps_and_a_small_delta():
+    for D in (64, 128):
+        c = C.offset(D, 512, "per_warp")
+        smax = float(C.scores(c).abs().max())
+        delta = (C.BIAS + smax) * 2.0 ** -24 * 2.0 ** -7 + 2.0 ** -24 * (smax * 2.0 ** -7 + C.FP8_OFFSET)
+        assert float(C.row_lsb(c).max()) == 2.0 ** -7 and delta < 2.0 ** -6
+        for S in C.SPLIT_CONFIGS[0][1]:
+            l = torch.stack([C.reference64(d, "fp16")["lse2"] for d in C.split_subcases(c, S)])
+            assert float(l.abs().min()) >= 2.0 ** 10 and float(C.split_gaps(c, "fp16", S).max()) < 1.0, S
+
+
+def test_zero_q_merged_reference_weighs_a_split_by_its_key_count():
+    c = C.anchor(C.extreme_s(64, 456, False, "per_warp", "zero"))
+    subs = C.split_subcases(c, 3)
+    l = torch.stack([C.reference64(d, "fp16")["lse2"] for d in subs])
+    assert [d["N"] for d in subs] == [192, 192, 72]
+    assert (torch.exp2(l - C.reference64(c, "fp16")["lse2"])[:, 0, 0, 0] - torch.tensor([192, 192, 72]).double() / 456).abs().max() < 1e-14
+
+
+_KM64 = lambda: C.split_km(64, True)
+# (mistake, family that must catch it, case builder, S, length, tiles)
+SPLIT_TEETH = [
+    ("split_scales_from_tile0", "scale_ladder", lambda: C.anchor(C.scale_ladder(64, 512, False, "per_warp")), 3, None),
+    ("split_scales_from_tile0", "scale_ladder", lambda: C.anchor(C.scale_ladder(128, 456, False, "per_thread")), 7, None),
+    ("split_tail_unmasked", "extreme_s", lambda: C.anchor(C.extreme_s(64, 456, False, "per_warp", "zero")), 3, None),
+    ("split_tail_unmasked", "extreme_s", lambda: C.anchor(C.extreme_s(64, 512, False, "per_warp", "zero")), 2, 257),
+    ("merge_equal_weights", "ramp", lambda: C.ramp(64, 512, False, "per_warp", "40", "ascending", anchor=True), 4, None),
+    ("merge_base_e_weights", "ramp", lambda: C.ramp(64, 512, False, "per_warp", "0.5", "ascending", anchor=True), 4, None),
+    ("merge_drops_last_split", "ramp", lambda: C.ramp(64, 512, False, "per_warp", "40", "ascending", anchor=True), 5, None),
+    ("correction_added_per_split", "ramp", lambda: C.ramp(64, 512, False, "per_warp", "40", "descending", anchor=True), 2, None),
+    ("correction_added_per_split", "scale_ladder", lambda: C.anchor(C.scale_ladder(128, 456, False, "per_thread")), 7, None),
+    ("length_rounded_up_to_tile", "extreme_s", lambda: C.anchor(C.extreme_s(64, 512, False, "per_warp", "zero")), 3, 257),
+    ("length_rounded_up_to_tile", "one_hot", lambda: C.anchor(C.one_hot(64, 512, False, "per_warp", 257)), 3, 257),
+]
+
+
+@pytest.mark.parametrize("i", range(len(SPLIT_TEETH)), ids=[f"{m}-{f}-{k}" for k, (m, f, *_) in enumerate(SPLIT_TEETH)])
+def test_merged_bound_has_teeth(i):
+    """each deliberate mistake of the split-KV restatement leaves merged_bound (ratio > 1); without it the restatement IS
+    the reference (< 1e-3)"""
+    mistake, family, build, S, n = SPLIT_TEETH[i]
+    c = build()
+    cn = c if n is None else C.subcase(c, length=n)
+    qkm = C.split_qkm(c, C.split_km(c["D"], True))
+    assert float(qkm.abs().max()) > 0.1
+    for pv in C.PVS:
+        o, _, lse = C.restate_split64(c, pv, S, n, None, qkm)
+        clean = max(C.merged_ratios(cn, pv, S, o, lse, qkm))
+        o, _, lse = C.restate_split64(c, pv, S, n, mistake, qkm)
+        r = max(C.merged_ratios(cn, pv, S, o, lse, qkm))
+        print(f"teeth: {mistake:28s} on {family:12s} D={c['D']:<3d} S={S:<2d} {pv:5s} ratio {r:12.1f}   (no mistake: {clean:.1e})")
+        assert clean < 1e-3, (pv, clean)
+        assert r > 1.0, (mistake, family, pv, r)
+
+
+SUBSET_TEETH = [
+    ("list_position_for_tile_index", "scale_ladder", lambda: C.scale_ladder(64, 456, False, "per_warp"), [1, 3, 5, 7], None),
+    ("list_position_for_tile_index", "scale_ladder", lambda: C.scale_ladder(128, 456, False, "per_thread"), [3], None),
+    ("length_rounded_up_to_tile", "extreme_s", lambda: C.extreme_s(64, 456, False, "per_warp", "zero"), None, 257),
+    ("length_rounded_up_to_tile", "one_hot", lambda: C.one_hot(64, 456, True, "per_warp", 257), None, 257),
+    ("length_rounded_up_to_tile", "one_hot", lambda: C.one_hot(64, 456, False, "per_warp", 257), [0, 2, 4], 257),
+]
+
+
+@pytest.mark.parametrize("i", range(len(SUBSET_TEETH)), ids=[f"{m}-{f}-{k}" for k, (m, f, *_) in enumerate(SUBSET_TEETH)])
+def test_subcase_bound_has_teeth(i):
+    mistake, family, build, tiles, n = SUBSET_TEETH[i]
+    c = build()
+    d = C.subcase(c, tiles, n)
+    for pv in C.PVS:
+        clean = max(C.ratios(d, pv, *C.restate_subset64(c, pv, tiles, n)))
+        r = max(C.ratios(d, pv, *C.restate_subset64(c, pv, tiles, n, mistake)))
+        print(f"teeth: {mistake:28s} on {family:12s} D={c['D']:<3d} {pv:5s} ratio {r:12.1f}   (no mistake: {clean:.1e})")
+        assert clean < 1e-3, (pv, clean)
+        assert r > 1.0, (mistake, family, pv, r)

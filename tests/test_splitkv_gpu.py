@@ -108,8 +108,9 @@ CONFIGS = [(D, pv, gran, dtype) for D in (64, 128) for pv in ("fp16", "fp8") for
            for dtype in (torch.float16, torch.bfloat16)]
 IDS = [f"d{d}-{pv}-{g}-{'bf16' if dt == torch.bfloat16 else 'fp16'}" for d, pv, g, dt in CONFIGS]
 # N = 1000: 16 tiles with a ragged tail (tps 8, 6, 4, 1: S = 3 ends with a short split, S = 5 leaves the fifth empty,
-# S = 16 gives every tile its own workgroup); N = 130 with S = 8: more splits than tiles
-SPLITS = [(1000, 2), (1000, 3), (1000, 5), (1000, 16), (130, 8)]
+# S = 16 gives every tile its own workgroup; S = 4 and 8: tps 4 and 2, every slot of MAXC = 4 / 8 in use; S = 9: tps 2, so
+# MAXC = 16 with 8 non-empty slots); N = 130 with S = 8: more splits than tiles
+SPLITS = [(1000, 2), (1000, 3), (1000, 4), (1000, 5), (1000, 8), (1000, 9), (1000, 16), (130, 8)]
 
 
 @pytest.mark.parametrize("M", [1, 70, 200])
