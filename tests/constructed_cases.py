@@ -4,7 +4,9 @@ CPU only: nothing here imports the HIP library.  tests/test_constructed_cases.py
 (the oracle's restatement of the kernel stays inside it) and that it has teeth (a restatement with one deliberate mistake
 leaves it); tests/test_constructed_logits_gpu.py holds the kernels that see every key to it, and
 tests/test_constructed_subsets_gpu.py those that see a subset (block maps, key lengths, split-KV: ``subcase``, the anchored
-forms for the fused-Q entry points, ``merged_bound``, ``restate_split64`` further down).
+forms for the fused-Q entry points, ``merged_bound``, ``restate_split64`` further down), and
+tests/test_constructed_masks_gpu.py the attn_mask kernel under structured masks (a case may carry ``c["mask"]``: ``with_mask``,
+``mask_pattern``, ``restate_mask64`` and ``public_form`` at the end).
 
 Every case is a dict (``case(family, variant, D, N, causal, gran)``):
   q8 [1,2,M,D] / k8 [1,1,N,D] int8; q_scale [1,2,Gq] / k_scale [1,1,Gk] fp32 in the compact layout of the granularity
@@ -420,8 +422,26 @@ def scale_matrix(c, q_rows=None, k_cols=None):
     return sc.double()
 
 
+def additive(c):
+    """the additive attn_mask of the case in float64 [Bm,Hq,M,N], or None (no mask, a bool mask)"""
+    mask = c.get("mask")
+    return None if mask is None or mask.dtype == torch.bool else mask.double()
+
+
+def logits64(c):
+    """base-2 logits t = S * scale (+ the additive attn_mask) in float64, nothing masked out yet"""
+    t, add = scores(c) * scale_matrix(c), additive(c)
+    return t if add is None else t + add
+
+
 def allowed(c, M=None, N=None):
+    """the keys each row attends: [1,1,M,N], or [Bm,Hq,M,N] under ``c["mask"]`` -- a bool mask itself, the keys of an additive
+    mask whose term is not -inf"""
     M, N = c["M"] if M is None else M, c["N"] if N is None else N
+    mask = c.get("mask")
+    if mask is not None:
+        assert not c["causal"] and tuple(mask.shape[1:]) == (HQ, M, N), "attn_mask: non-causal, [Bm,Hq,M,N]"
+        return mask.clone() if mask.dtype == torch.bool else mask.float() > float("-inf")
     if c["causal"]:
         return (torch.arange(N).view(1, 1, 1, N) <= torch.arange(M).view(1, 1, M, 1))
     return torch.ones(1, 1, M, N, dtype=torch.bool)
@@ -441,11 +461,12 @@ def v64(c, pv):
 def reference64(c, pv):
     """fp64 softmax (base 2) of the dequantised integers times the dequantised V.
     -> dict(o [1,Hq,M,D], lse2 [1,Hq,M], W normalised weights [1,Hq,M,N], wabsv = W @ |V|, sumabsv = sum_j |V_jd| over the
-    keys the row attends)."""
+    keys the row attends).  Under ``c["mask"]`` [Bm,Hq,M,N] every result has Bm batch slices (the operands are the same, the
+    masks differ); an additive mask is added to t in float64 before the softmax.  A row that keeps no key is NaN."""
     key, cache = ("ref", pv), c.setdefault("_cache", {})
     if key in cache:
         return cache[key]
-    t = scores(c) * scale_matrix(c)
+    t = logits64(c)
     ok = allowed(c)
     t = t.masked_fill(~ok, float("-inf"))
     m = t.amax(-1, keepdim=True)
@@ -454,7 +475,7 @@ def reference64(c, pv):
     W = p / l
     V = v64(c, pv)
     out = dict(o=W @ V, lse2=(m + torch.log2(l)).squeeze(-1), W=W, wabsv=W @ V.abs(),
-               sumabsv=ok.double().expand(1, HQ, -1, -1) @ V.abs())
+               sumabsv=ok.double().expand(-1, HQ, -1, -1) @ V.abs())
     cache[key] = out
     return out
 
@@ -507,6 +528,16 @@ def bound(c, pv, D=None, delta_zero=False, out_ulps=2):
     LSE: log2(1 + 2^-11) is the relative error of a sum of fp16-rounded P (conftest.LSE2_TOL_ROUNDED_P's first term);
     delta moves l by 2^(+-delta); N fp32 additions of positive terms each lose <= 2^-24 relative, log2(e) * N * 2^-24 in
     the logarithm (v_log_f32's own ulp is inside the 2 fp32 ulps).
+    * attn_mask (``c["mask"]``; sage_attn_body.h, the HAS_MASK loop).  A bool mask needs no new term: a masked score is the bit
+      pattern of -inf, p = exp2(fma(-inf, sc, c0)) is exactly 0, and the keys a row keeps go through the arithmetic above;
+      ``allowed`` (hence sumabsv, the row LSB) follows the mask.  An ADDITIVE mask adds to delta
+          2^-24 * (Tmax + 3 * Umax),
+      Tmax the row's largest |t| and Umax its largest |t + mask| over the keys it keeps (term not -inf).  The kernel
+      (to_float_logits, then the MASKED && fmask branch of prob) forms, in this order, t32 = fl(fma(as_float(bias + S), sc,
+      -bias * sc)), u = fl(t32 + mask) and fl(u - m_run) (+ kPOff = 0: the operator has no FP8 PV): three roundings of half an
+      ulp of their results, 2^-24 |t|, 2^-24 |u| and 2^-24 |u - m_run| <= 2^-24 * 2 Umax, since m_run is itself some u of the
+      row.  (The c0 of the bullet above is not formed on this path; its term is kept, so one delta holds for both.)  The sum
+      enters rel and the LSE bound as delta does.  A key at -inf has u = -inf and p = 0 exactly.
     ``delta_zero``: for operands whose logits are all equal on a row no relative movement between tiles can change the
     weights' ratios -- used by the degenerate-input operator tests, where the issue sets delta = 0.
     ``out_ulps``: 0 for a result that is stored in fp32 (the split-KV partials in the workspace)."""
@@ -518,6 +549,12 @@ def bound(c, pv, D=None, delta_zero=False, out_ulps=2):
     delta = (BIAS + smax) * 2.0 ** -24 * s
     if pv == "fp8":
         delta = delta + 2.0 ** -24 * (smax * s + FP8_OFFSET)
+    add = additive(c)
+    if add is not None:
+        ok, tl = allowed(c), scores(c) * scale_matrix(c)
+        tmax = tl.abs().expand_as(ok).masked_fill(~ok, 0.0).amax(-1)
+        umax = (tl + add).abs().masked_fill(~ok, 0.0).amax(-1)
+        delta = delta + 2.0 ** -24 * (tmax + 3 * umax)
     if delta_zero:
         delta = torch.zeros_like(delta)
     rel = 2 * 2.0 ** -t + (torch.exp2(2 * delta) - 1) + 2.0 ** -18
@@ -566,9 +603,12 @@ def oracle(c, pv):
     """oracle.sage_oracle.attn_tile_loop, "hip" flavour, on the case -> (o in the output dtype, lse2 fp32)"""
     key, cache = ("oracle", pv), c.setdefault("_cache", {})
     if key not in cache:
-        cache[key] = O.attn_tile_loop(c["q8"], c["k8"], v_of(c, pv), c["q_scale_rows"], c["k_scale_cols"],
-                                  logit_mult=c["logit_mult"], is_causal=c["causal"], pv="fp8" if pv == "fp8" else "fp16",
-                                  v_scale=c["v_scale"] if pv == "fp8" else None, out_dtype=OUT_DTYPE[pv], flavor="hip")
+        mask = c.get("mask")
+        rep = (lambda t: t) if mask is None else (lambda t: t.expand(mask.shape[0], *t.shape[1:]))
+        cache[key] = O.attn_tile_loop(rep(c["q8"]), rep(c["k8"]), rep(v_of(c, pv)), rep(c["q_scale_rows"]),
+                                  rep(c["k_scale_cols"]), logit_mult=c["logit_mult"], is_causal=c["causal"],
+                                  pv="fp8" if pv == "fp8" else "fp16", v_scale=c["v_scale"] if pv == "fp8" else None,
+                                  out_dtype=OUT_DTYPE[pv], flavor="hip", attn_mask=mask)
     return cache[key]
 
 
@@ -605,11 +645,17 @@ def restate64(c, pv, mistake=None):
     elif mistake == "wrap_2_21":          # a 22-bit accumulator: +2^21 becomes -2^21
         S = torch.remainder(S + 2.0 ** 21, 2.0 ** 22) - 2.0 ** 21
     t_all = (S * scale_matrix(c, q_rows, k_cols)).masked_fill(~ok, float("-inf"))
+    return _lazy_loop64(t_all, V, pv, clamp=32.0 if mistake == "clamp_p_2_5" else None)
+
+
+def _lazy_loop64(t_all, V, pv, clamp=None):
+    """the tile loop of restate64 on the float64 logits t_all [..,Hq,M,N] (-inf = not attended) -> (o, lse2)"""
+    M = t_all.shape[-2]
     thr = LAZY_THR[pv]
     NEG = float("-inf")
-    m_run = torch.full((1, HQ, M), NEG, dtype=torch.float64)
-    l = torch.zeros(1, HQ, M, dtype=torch.float64)
-    acc = torch.zeros(1, HQ, M, V.shape[-1], dtype=torch.float64)
+    m_run = torch.full(t_all.shape[:-1], NEG, dtype=torch.float64)
+    l = torch.zeros(t_all.shape[:-1], dtype=torch.float64)
+    acc = torch.zeros(t_all.shape[:-1] + (V.shape[-1],), dtype=torch.float64)
     wave = torch.arange(M) // 32
     nw = int(wave.max()) + 1
     for n0 in range(0, t_all.shape[-1], 64):
@@ -623,8 +669,8 @@ def restate64(c, pv, mistake=None):
                             torch.exp2(torch.where(torch.isinf(m_run), torch.full_like(m_run, NEG), m_run - m_new)))
         safe = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
         p = torch.exp2(t - safe.unsqueeze(-1))
-        if mistake == "clamp_p_2_5":
-            p = p.clamp(max=32.0)
+        if clamp is not None:
+            p = p.clamp(max=clamp)
         l = l * alpha + p.sum(-1)
         acc = acc * alpha.unsqueeze(-1) + p @ V[:, :, n0:n0 + 64]
         m_run = m_new
@@ -991,3 +1037,262 @@ def split_gaps(c, pv, S, length=None):
     """largest difference between the fp64 LSEs (base 2) of two non-empty splits, per row [1,Hq,M]"""
     l = torch.stack([reference64(d, pv)["lse2"] for d in split_subcases(c, S, length)])
     return l.amax(0) - l.amin(0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# attn_mask: structured masks as part of a case (the CPU soundness test and tests/test_constructed_masks_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+MASK_BM = 2
+MASK_SMALL_SHAPES = ((1, 1), (5, 3), (33, 65), (128, 64))  # N = 3: every run of four keys crosses N; 65: one key in tile 1
+BOOL_PATTERNS = ("late_first_key", "wave_tile_skip", "single_key", "ragged_only", "key_padding", "first_tile_off", "row_switch")
+ADD_PATTERNS = ("grid", "pad_1e4", "neg_inf", "rows_1e4", "row_const")
+SMALL_PATTERNS = ("late_first_key", "neg_inf")  # one bool and one additive pattern defined at every (M, N)
+KEY_PAD_LEN = 257
+
+
+def with_mask(c, mask, name=None):
+    """A copy of the case that carries ``mask`` [Bm,Hq,M,N] (bool, or fp16 / bf16 additive base-2 terms), with a fresh cache.
+    ``name``: the copy's cache is kept in the cache of ``c`` under that name, so that the regran copies of ``c`` (same logits)
+    share the masked reference as they share the plain one."""
+    assert not c["causal"] and tuple(mask.shape[1:]) == (HQ, c["M"], c["N"]) and mask.shape[0] in (1, 2)
+    assert mask.dtype in (torch.bool, torch.float16, torch.bfloat16)
+    d = dict(c)
+    d["mask"] = mask
+    d["_cache"] = {} if name is None else c.setdefault("_cache", {}).setdefault(("mask", name, mask.dtype), {})
+    return d
+
+
+def cut_case(c, M, N):
+    """the case cut to its first M rows and N keys, compact scales included (both layouts are prefix-compatible)"""
+    assert not c["causal"] and M <= c["M"] and N <= c["N"]
+    d = subcase(c, length=N)
+    _, gq = _gid_q(M, c["gran"])
+    _, gk = _gid_k(N, c["gran"])
+    d.update(q8=c["q8"][:, :, :M].contiguous(), q_scale=c["q_scale"][..., :gq].contiguous(),
+             q_scale_rows=c["q_scale_rows"][..., :M].contiguous(), k_scale=c["k_scale"][..., :gk].contiguous(), M=M)
+    assert torch.equal(O.expand_q_scale(d["q_scale"], M, c["gran"]), d["q_scale_rows"])
+    assert torch.equal(O.expand_k_scale(d["k_scale"], N, c["gran"]), d["k_scale_cols"])
+    return d
+
+
+def _mask_index(M, N, Bm):
+    b, h = torch.arange(Bm).view(Bm, 1, 1, 1), torch.arange(HQ).view(1, HQ, 1, 1)
+    return b, h, torch.arange(M).view(1, 1, M, 1), torch.arange(N).view(1, 1, 1, N), 3 * b + h
+
+
+def lone_row_tile(s):
+    """wave_tile_skip: the kept tile of wave 0 in which row 31 alone keeps keys, for the slice shift s = 3 b + h"""
+    return 1 if (1 + s) % 3 else 2
+
+
+def mask_pattern(name, M=M_FULL, N=SUBSET_N, dtype=torch.float16, Bm=MASK_BM):
+    """One named mask [Bm,Hq,M,N]: bool for BOOL_PATTERNS, ``dtype`` (fp16 / bf16, every value exact in both) for ADD_PATTERNS.
+    The broadcastable patterns (key_padding, row_switch, row_const) are EXPANDED VIEWS of their compact tensor (stride 0).
+    s = 3 b + h is the shift of slice (b, h): it enters every bool pattern that depends on the key, so no two slices are equal
+    (row_switch names rows only and is the same on every slice; key_padding is [Bm,1,1,N] and differs between the batches).
+
+    late_first_key  row r's first key is (37 r + s) % N; beyond it the row keeps the keys with (n + r + s) % 3 != 0
+    wave_tile_skip  the 32x64 tile (g, j) is off iff (g + j + s) % 3 == 0 (waves of one q-block skip different tiles, some
+                    wave has tile 0 off); kept tiles hold the checkerboard (r + n + s) % 2 == 0; in tile lone_row_tile(s) of
+                    wave 0 rows 0..30 are off and row 31 alone is on
+    single_key      row r keeps key (61 r + s) % N only
+    ragged_only     rows of odd waves keep the keys >= 64 * ((N - 1) // 64) + s only (N = 456: 448 + s .. 455); even waves all
+    key_padding     keys >= 257 - 3 b off for every row, [Bm,1,1,N] expanded
+    first_tile_off  keys below 64 + (r + s) % 5 off
+    row_switch      [Bm,Hq,M,1] expanded over the keys: rows with r % 16 == 5 off entirely -- the only rows of any pattern
+                    that keep no key -- the others fully on
+    grid            multiples of 1/16 in [-8, 8]: ((7 r + 13 n + 29 h + 53 b) % 257 - 128) / 16
+    pad_1e4         grid, keys >= 257 at -1e4 (in the mask dtype: bf16 holds -9984)
+    neg_inf         grid, the keys with (n + r) % 3 == 0 and those below (64 + r % 5) % N at -inf; a row that would keep no key
+                    (possible for N < 70 only) keeps key N - 1
+    rows_1e4        grid, rows with r % 7 == 3 entirely at -1e4
+    row_const       3 * ((r + s) % 11) - 15, [Bm,Hq,M,1] expanded"""
+    b, h, r, n, s = _mask_index(M, N, Bm)
+    full = (Bm, HQ, M, N)
+    if name == "late_first_key":
+        first = (37 * r + s) % N
+        return ((n == first) | ((n > first) & ((n + r + s) % 3 != 0))).expand(full).contiguous()
+    if name == "wave_tile_skip":
+        g, j = r // 32, n // 64
+        ok = ((g + j + s) % 3 != 0) & ((r + n + s) % 2 == 0)
+        lone = torch.where((1 + s) % 3 != 0, 1, 2)
+        ok = ok & ~((g == 0) & (j == lone) & (r < 31))
+        return ok.expand(full).contiguous()
+    if name == "single_key":
+        return (n == (61 * r + s) % N).expand(full).contiguous()
+    if name == "ragged_only":
+        start = 64 * ((N - 1) // 64) + s
+        assert int(start.max()) < N
+        return (((r // 32) % 2 == 0) | (n >= start)).expand(full).contiguous()
+    if name == "key_padding":
+        assert N > KEY_PAD_LEN
+        return (n < KEY_PAD_LEN - 3 * b).contiguous().expand(full)
+    if name == "first_tile_off":
+        assert N > 69
+        return (n >= 64 + (r + s) % 5).expand(full).contiguous()
+    if name == "row_switch":
+        return (r % 16 != 5).expand(Bm, HQ, M, 1).contiguous().expand(full)
+    assert name in ADD_PATTERNS, name
+    assert dtype in (torch.float16, torch.bfloat16)
+    if name == "row_const":
+        m = (3 * ((r + s) % 11) - 15).to(dtype).expand(Bm, HQ, M, 1).contiguous()
+        return m.expand(full)
+    grid = (((7 * r + 13 * n + 29 * h + 53 * b) % 257 - 128).double() / 16).expand(full).clone()
+    assert torch.equal(grid.to(dtype).double(), grid) and float(grid.abs().max()) <= 8.0
+    if name == "pad_1e4":
+        assert N > KEY_PAD_LEN
+        grid[..., KEY_PAD_LEN:] = -1.0e4
+    elif name == "neg_inf":
+        off = (((n + r) % 3 == 0) | (n < (64 + r % 5) % N)).expand(full).clone()
+        empty = off.all(-1)
+        off[..., N - 1] &= ~empty
+        grid = grid.masked_fill(off, float("-inf"))
+    elif name == "rows_1e4":
+        grid = torch.where((r % 7 == 3).expand(full), torch.full_like(grid, -1.0e4), grid)
+    return grid.to(dtype)
+
+
+def mask_patterns(M=M_FULL, N=SUBSET_N, dtype=torch.float16, Bm=MASK_BM, names=None):
+    """yield (name, mask) of every pattern (``names``: of those) at M rows and N keys; M = 150, N = 456 is two q-blocks, five
+    32-row waves of which the last holds 22 valid rows, seven whole tiles and a ragged one of 8 keys"""
+    for name in (BOOL_PATTERNS + ADD_PATTERNS if names is None else names):
+        yield name, mask_pattern(name, M, N, dtype, Bm)
+
+
+def no_key_rows(c):
+    """bool [Bm,Hq,M]: the rows that keep no key (row_switch only)"""
+    return ~allowed(c).any(-1)
+
+
+def mask_ratio_tensors(c, pv, o, lse2):
+    """ratio_tensors of a masked case with reference and bound kept in the case's cache; the rows that keep no key hold 0
+    (they are undefined: include/sageattn_hip.h) -> (ro [Bm,Hq,M,D], rl [Bm,Hq,M], rows without a key [Bm,Hq,M])"""
+    cache = c.setdefault("_cache", {})
+    if ("bound", pv) not in cache:
+        cache[("bound", pv)] = bound(c, pv) + (no_key_rows(c),)
+    o_b, l_b, dead = cache[("bound", pv)]
+    ref = reference64(c, pv)
+    inf = torch.tensor(float("inf"), dtype=torch.float64)
+    o, lse2 = o.double(), lse2.double()
+    ro = torch.where(torch.isfinite(o), (o - ref["o"]).abs() / o_b, inf)
+    rl = torch.where(torch.isfinite(lse2), (lse2 - ref["lse2"]).abs() / l_b, inf)
+    zero = torch.zeros((), dtype=torch.float64)
+    return torch.where(dead.unsqueeze(-1), zero, ro), torch.where(dead, zero, rl), dead
+
+
+def mask_ratios(c, pv, o, lse2):
+    """largest ratio over every element of every row that keeps a key -> (o, lse2); NaN (a broken reference) -> inf"""
+    ro, rl, _ = mask_ratio_tensors(c, pv, o, lse2)
+    f = lambda x: float("inf") if bool(torch.isnan(x).any()) else float(x.max())
+    return f(ro), f(rl)
+
+
+MASK_MISTAKES = ("mask_next_row", "mask_next_key", "mask_head_zero", "mask_batch_zero", "skip_by_first_row", "tail_run_unread",
+                 "run_reversed", "additive_times_scale", "additive_in_nats", "bf16_read_as_fp16")
+
+
+def restate_mask64(c, pv, mistake=None):
+    """restate64 (float64, no rounding) of the attn_mask loop on a case that carries a mask: the mask is read, applied to the
+    logits, and the tile loop runs.  Without a mistake it equals reference64 to float64 accuracy; ``mistake`` makes exactly
+    one of MASK_MISTAKES:
+      mask_next_row / mask_next_key  row r reads the mask of row r + 1 / key n that of key n + 1 (the last one its own)
+      mask_head_zero / mask_batch_zero  every head reads head 0's slice / every batch batch 0's
+      skip_by_first_row   a 32-row wave skips a 64-key tile when its FIRST row keeps no key there
+      tail_run_unread     the keys of the run of four that crosses N count as allowed (additive: term 0)
+      run_reversed        the four mask values of every whole run of four keys in reverse order
+      additive_times_scale  the additive term multiplied by the key's dequantisation scale
+      additive_in_nats    the additive term taken as natural-log units (times log2 e)
+      bf16_read_as_fp16   the 16 bits of a bf16 term read as fp16"""
+    mask = c["mask"]
+    M, N = c["M"], c["N"]
+    is_bool = mask.dtype == torch.bool
+    mk = mask.clone()
+    if mistake == "mask_next_row":
+        mk = mk[:, :, (torch.arange(M) + 1).clamp(max=M - 1)]
+    elif mistake == "mask_next_key":
+        mk = mk[..., (torch.arange(N) + 1).clamp(max=N - 1)]
+    elif mistake == "mask_head_zero":
+        mk = mk[:, :1].expand_as(mk).clone()
+    elif mistake == "mask_batch_zero":
+        mk = mk[:1].expand_as(mk).clone()
+    elif mistake == "tail_run_unread":
+        mk[..., 4 * (N // 4):] = True if is_bool else 0.0
+    elif mistake == "run_reversed":
+        n = torch.arange(4 * (N // 4))
+        mk[..., :n.numel()] = mk[..., 4 * (n // 4) + 3 - n % 4]
+    elif mistake == "bf16_read_as_fp16":
+        assert mask.dtype == torch.bfloat16
+        mk = mk.view(torch.int16).view(torch.float16)
+    ok = mk if is_bool else mk.float() > float("-inf")
+    if mistake == "skip_by_first_row":
+        ok = ok.clone()
+        for r0 in range(0, M, 32):
+            for n0 in range(0, N, 64):
+                dead = ~ok[:, :, r0, n0:n0 + 64].any(-1)
+                ok[:, :, r0:r0 + 32, n0:n0 + 64] &= ~dead.view(*dead.shape, 1, 1)
+    t = scores(c) * scale_matrix(c)
+    if not is_bool:
+        add = torch.where(torch.isinf(mk.double()), torch.zeros((), dtype=torch.float64), mk.double())  # -inf lives in ``ok``
+        if mistake == "additive_times_scale":
+            add = add * scale_matrix(c)
+        elif mistake == "additive_in_nats":
+            add = add * math.log2(math.e)
+        t = t + add
+    t = t.expand(ok.shape).masked_fill(~ok, float("-inf"))
+    return _lazy_loop64(t, v64(c, pv), pv)
+
+
+PUBLIC_BACKENDS = {"triton": "per_thread", "cuda": "per_block"}  # quantization_backend -> the granularity it quantizes with
+PUBLIC_PATTERNS = ("key_padding", "late_first_key", "neg_inf")
+
+
+def public_form(c, backend):
+    """The case in the form sageattn_qk_int8_pv_fp16_triton(q, k, v, attn_mask=..., smooth_k=False) reproduces from REAL
+    q and k: BOTH quantizers must return the case's int8 operands and scales.  Two head-dim channels are reserved: D - 1 holds
+    q8 = 127 / k8 = 0 (``anchor``) and D - 2 holds k8 = 127 / q8 = 0, so every quantization group of Q and of K has amax
+    127 * 2^e and neither channel adds to a score.  The smallest q and k scale are moved to 2^1 (the per-thread numerics add
+    1e-7 to a scale, which fp32 absorbs from 2^1 up) and logit_mult takes the rest, as a power of two again:
+      "triton"  per-thread scales; ``sm_scale`` with fp32(sm_scale) * kLog2e = 2^x exactly (the kernel forms that product)
+      "cuda"    per-block scales with sm_scale * 1.44269504 folded into Q by the quantizer: ``sm_scale`` = 2^x / 1.44269504 in
+                double precision, whose product with the constant rounds to 2^x in fp32; the case's q_scale is the FOLDED scale
+                the quantizer returns and its logit_mult is 1 (the kernel is told logit_mult_is_one)
+    ``q_real_rows`` / ``k_scale_cols``: what Q = q8 * 2^e and K = k8 * 2^e are formed with (``public_qk``).  K smoothing would
+    subtract the key mean and lose the integers: the call must pass smooth_k=False."""
+    gran = PUBLIC_BACKENDS[backend]
+    assert c["gran"] == gran and not c["causal"] and not c.get("anchored")
+    d = dict(c)
+    d["q8"], d["k8"] = c["q8"].clone(), c["k8"].clone()
+    d["q8"][..., -1], d["k8"][..., -1] = 127, 0
+    d["q8"][..., -2], d["k8"][..., -2] = 0, 127
+    fq = 2.0 ** (1 - int(torch.log2(c["q_scale"].min())))
+    fk = 2.0 ** (1 - int(torch.log2(c["k_scale"].min())))
+    for key, f in (("q_scale", fq), ("q_scale_rows", fq), ("k_scale", fk), ("k_scale_cols", fk)):
+        d[key] = c[key] * f
+    x = int(round(math.log2(c["logit_mult"] / (fq * fk))))
+    d["q_real_rows"] = d["q_scale_rows"]
+    if backend == "triton":
+        d["sm_scale"], d["logit_mult"] = _pow2_logit_mult(x)
+    else:
+        d["sm_scale"], d["logit_mult"] = 2.0 ** x / 1.44269504, 1.0
+        assert float(np.float32(d["sm_scale"] * 1.44269504)) == 2.0 ** x
+        d["q_scale"], d["q_scale_rows"] = d["q_scale"] * 2.0 ** x, d["q_scale_rows"] * 2.0 ** x
+    d["public"], d["_cache"] = backend, {}
+    assert torch.equal(scale_matrix(d), scale_matrix(c))  # every logit scale is what it was
+    return d
+
+
+def public_qk(d, dtype):
+    """Q = q8 * 2^e and K = k8 * 2^e of a ``public_form`` case in fp16 / bf16, exact -> (q [1,Hq,M,D], k [1,Hk,N,D])"""
+    q = d["q8"].float() * d["q_real_rows"].unsqueeze(-1)
+    k = d["k8"].float() * d["k_scale_cols"].unsqueeze(-1)
+    assert torch.equal(q.to(dtype).float(), q) and torch.equal(k.to(dtype).float(), k)
+    return q.to(dtype), k.to(dtype)
+
+
+def public_cases(D, backend):
+    """Yield (label, public_form case) run through the public entry: scale_ladder, one_hot (hot key 200), extreme_s zero"""
+    gran = PUBLIC_BACKENDS[backend]
+    yield "ladder", public_form(scale_ladder(D, SUBSET_N, False, gran), backend)
+    yield "hot200", public_form(one_hot(D, SUBSET_N, False, gran, 200), backend)
+    yield "zero", public_form(extreme_s(D, SUBSET_N, False, gran, "zero"), backend)

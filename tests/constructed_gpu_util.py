@@ -1,5 +1,5 @@
 """Device-side helpers shared by the constructed-operand GPU tests (tests/test_constructed_logits_gpu.py,
-tests/test_constructed_subsets_gpu.py): a case's operands in the form the C entry points take."""
+tests/test_constructed_subsets_gpu.py, tests/test_constructed_masks_gpu.py): a case's operands in the form the C entry points take."""
 import torch
 
 import constructed_cases as C

@@ -391,3 +391,192 @@ def test_subcase_bound_has_teeth(i):
         print(f"teeth: {mistake:28s} on {family:12s} D={c['D']:<3d} {pv:5s} ratio {r:12.1f}   (no mistake: {clean:.1e})")
         assert clean < 1e-3, (pv, clean)
         assert r > 1.0, (mistake, family, pv, r)
+
+
+# ---- attn_mask: structured masks as part of a case ----------------------------------------------------------------------
+
+_MASK = {}
+_MASK_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _mask_table():
+    yield
+    if _MASK:
+        print("\noracle (hip flavour, attn_mask) on the masked cases: largest |err| / bound   [o, lse2]")
+        for (name, fam, pv, D), (ro, rl) in sorted(_MASK.items()):
+            print(f"  {name:15s} {fam:13s} {pv:5s} D={D:<4d} {ro:6.3f} {rl:6.3f}")
+
+
+def _small_masked(c, pv, M, N):
+    """the case cut to (M, N) under each pattern of SMALL_PATTERNS at that size"""
+    d = C.cut_case(c, M, N)
+    for name, mask in C.mask_patterns(M, N, _MASK_DTYPE[pv], names=C.SMALL_PATTERNS):
+        yield name, C.with_mask(d, mask)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("pv", ["fp16", "bf16"])
+@pytest.mark.parametrize("family", C.SUBSET_FAMILIES)
+def test_oracle_within_bound_under_masks(family, pv, D):
+    """every masked case tests/test_constructed_masks_gpu.py checks the kernel against: the oracle called with attn_mask stays
+    within the bound on every element of every row that keeps a key, under every pattern at N = 456 and under the two small
+    patterns at MASK_SMALL_SHAPES.  Only row_switch has rows without a key, ceil((M - 5) / 16) per slice."""
+    masks = dict(C.mask_patterns(dtype=_MASK_DTYPE[pv]))
+    for label, c in C.subset_cases(family, D, pv, grans=C.GRANS):
+        todo = [(name, C.with_mask(c, mask, name)) for name, mask in masks.items()]
+        if label.endswith(C.GRANS[0]):
+            todo += [(f"{name}", d) for M, N in C.MASK_SMALL_SHAPES for name, d in _small_masked(c, pv, M, N)]
+        for name, d in todo:
+            dead = C.no_key_rows(d)
+            want = -(-(d["M"] - 5) // 16) if name == "row_switch" else 0
+            assert bool((dead.sum(-1) == want).all()), (label, name)
+            ro, rl = C.mask_ratios(d, pv, *C.oracle(d, pv))
+            a, b = _MASK.get((name, family, pv, D), (0.0, 0.0))
+            _MASK[(name, family, pv, D)] = (max(a, ro), max(b, rl))
+            assert ro <= 1.0 and rl <= 1.0, (label, name, d["M"], d["N"], ro, rl)
+
+
+def test_mask_patterns_are_what_they_say():
+    """structure of the patterns at M = 150, N = 456: no two (batch, head) slices of a key-dependent pattern are equal; waves of
+    one q-block skip different tiles and some wave has tile 0 off; the lone row; first keys beyond tile 0; the broadcast
+    patterns are expanded views; the additive values are exact in fp16 and in bf16"""
+    for name, m in C.mask_patterns():
+        assert tuple(m.shape) == (2, 2, 150, 456), name
+        sl = [m[b, h] for b in range(2) for h in range(2)]
+        if name not in ("row_switch", "key_padding"):
+            assert all(not torch.equal(sl[i], sl[j]) for i in range(4) for j in range(i)), name
+        if m.dtype != torch.bool:
+            if name not in ("pad_1e4", "rows_1e4"):  # (-1e4 is -9984 in bf16)
+                assert torch.equal(C.mask_pattern(name, dtype=torch.bfloat16).double(), m.double()), name
+    assert not torch.equal(*C.mask_pattern("key_padding")[:, 0])
+    assert C.mask_pattern("key_padding").stride()[1:3] == (0, 0) and C.mask_pattern("row_switch").stride(3) == 0
+    assert C.mask_pattern("row_const").stride(3) == 0
+    assert float(C.mask_pattern("pad_1e4", dtype=torch.bfloat16)[0, 0, 0, 300]) == -9984.0
+    wts = C.mask_pattern("wave_tile_skip")
+    tiles = torch.stack([wts[:, :, 32 * g:32 * g + 32, 64 * j:64 * j + 64].flatten(2).any(-1) for g in range(5)
+                         for j in range(8)], -1).view(2, 2, 5, 8)                # [b,h,wave,tile]: does the wave compute the tile
+    for b in range(2):
+        for h in range(2):
+            s = 3 * b + h
+            assert torch.equal(tiles[b, h], (torch.arange(5).view(5, 1) + torch.arange(8).view(1, 8) + s) % 3 != 0)
+            assert not torch.equal(tiles[b, h, 0], tiles[b, h, 1]) and not tiles[b, h, :, 0].all()
+            j = C.lone_row_tile(s)
+            blk = wts[b, h, 0:32, 64 * j:64 * j + 64]
+            assert not blk[:31].any() and blk[31].any()
+            assert wts[b, h, :31].any(-1).all()                                # the switched-off rows keep keys elsewhere
+    first = C.mask_pattern("late_first_key").float().argmax(-1)
+    assert torch.equal(first[0, 0], (37 * torch.arange(150)) % 456)
+    for g in range(5):
+        assert len(set((first[0, 0, 32 * g:32 * g + 32] // 64).tolist())) >= 4  # the rows of a wave start in different tiles
+    assert float((first >= 64).double().mean()) > 0.8
+    ro = C.mask_pattern("ragged_only")
+    assert ro[:, :, 32:64, :448].sum() == 0 and bool(ro[:, :, 32:64, 452:].all()) and bool(ro[:, :, :32].all())
+    assert bool(C.mask_pattern("single_key").sum(-1).eq(1).all())
+    ni = C.mask_pattern("neg_inf")
+    assert bool(torch.isinf(ni[:, :, :, :64]).all()) and bool((~torch.isinf(ni)).any(-1).all())
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_masked_reference_identities(D):
+    """three closed forms of the masked fp64 reference.  single_key: o is the V row of the row's key and lse2 its logit.
+    key_padding: batch slice b equals the reference of the first 257 - 3 b keys (cached_subcase).  row_const: the unmasked o,
+    lse2 shifted by the row's constant."""
+    c = C.scale_ladder(D, C.SUBSET_N, False, "per_thread")
+    t = C.scores(c) * C.scale_matrix(c)
+    b, h, r, n, s = C._mask_index(c["M"], c["N"], 2)
+    for pv in ("fp16", "bf16"):
+        plain, V = C.reference64(c, pv), C.v64(c, pv)
+        d = C.with_mask(c, C.mask_pattern("single_key"))
+        ref = C.reference64(d, pv)
+        key = ((61 * r + s) % c["N"]).expand(2, 2, c["M"], 1)
+        assert torch.equal(ref["o"], torch.gather(V.expand(2, -1, -1, -1), 2, key.expand(-1, -1, -1, D)))
+        assert torch.equal(ref["lse2"], torch.gather(t.expand(2, -1, -1, -1), 3, key).squeeze(-1))
+        d = C.with_mask(c, C.mask_pattern("key_padding"))
+        ref = C.reference64(d, pv)
+        for bb in range(2):
+            sub = C.reference64(C.cached_subcase(c, length=C.KEY_PAD_LEN - 3 * bb), pv)
+            assert (ref["o"][bb:bb + 1] - sub["o"]).abs().max() < 1e-13 and (ref["lse2"][bb:bb + 1] - sub["lse2"]).abs().max() < 1e-11
+            assert (ref["sumabsv"][bb:bb + 1] / sub["sumabsv"] - 1).abs().max() < 1e-13
+        d = C.with_mask(c, C.mask_pattern("row_const", dtype=_MASK_DTYPE[pv]))
+        ref = C.reference64(d, pv)
+        const = (3 * ((r + s) % 11) - 15).double().expand(2, 2, c["M"], 1).squeeze(-1)
+        assert (ref["o"] - plain["o"]).abs().max() < 1e-13 and (ref["lse2"] - (plain["lse2"] + const)).abs().max() < 1e-11
+        assert const.abs().max() == 15 and not torch.equal(const[0, 0], const[1, 1])
+
+
+_SL = lambda D=64, gran="per_thread": C.scale_ladder(D, C.SUBSET_N, False, gran)
+# (mistake, family that must catch it, pattern, case builder, (M, N) or None for 150 x 456)
+MASK_TEETH = [
+    ("mask_next_row", "scale_ladder", "late_first_key", _SL, None),
+    ("mask_next_row", "ramp", "rows_1e4", lambda: C.ramp(64, 456, False, "per_warp", "40", "sawtooth"), None),
+    ("mask_next_key", "scale_ladder", "first_tile_off", _SL, None),
+    ("mask_next_key", "one_hot", "neg_inf", lambda: C.one_hot(64, 456, False, "per_warp", 200), None),
+    ("mask_head_zero", "scale_ladder", "wave_tile_skip", _SL, None),
+    ("mask_head_zero", "extreme_s", "row_const", lambda: C.extreme_s(64, 456, False, "per_warp", "zero"), None),
+    ("mask_batch_zero", "scale_ladder", "key_padding", _SL, None),
+    ("mask_batch_zero", "scale_ladder", "grid", lambda: _SL(128, "per_warp"), None),
+    ("skip_by_first_row", "scale_ladder", "wave_tile_skip", _SL, None),
+    ("skip_by_first_row", "one_hot", "late_first_key", lambda: C.one_hot(64, 456, False, "per_warp", 200), None),
+    ("tail_run_unread", "scale_ladder", "late_first_key", _SL, (33, 65)),
+    ("tail_run_unread", "scale_ladder", "neg_inf", _SL, (5, 3)),
+    ("run_reversed", "scale_ladder", "single_key", _SL, None),
+    ("run_reversed", "extreme_s", "pad_1e4", lambda: C.extreme_s(64, 456, False, "per_warp", "zero"), None),
+    ("additive_times_scale", "scale_ladder", "grid", _SL, None),
+    ("additive_in_nats", "ramp", "row_const", lambda: C.ramp(64, 456, False, "per_warp", "6", "ascending"), None),
+    ("additive_in_nats", "scale_ladder", "neg_inf", _SL, None),
+    ("bf16_read_as_fp16", "scale_ladder", "grid", _SL, None),
+    ("bf16_read_as_fp16", "one_hot", "pad_1e4", lambda: C.one_hot(64, 456, False, "per_warp", 200), None),
+]
+
+
+def test_every_mask_mistake_has_a_tooth():
+    assert {m for m, *_ in MASK_TEETH} == set(C.MASK_MISTAKES)
+
+
+@pytest.mark.parametrize("i", range(len(MASK_TEETH)), ids=[f"{m}-{f}-{p}" for m, f, p, *_ in MASK_TEETH])
+def test_mask_bound_has_teeth(i):
+    """each deliberate mistake of the attn_mask restatement leaves the bound (ratio > 1) on the named (family, pattern);
+    without it the restatement IS the reference (< 1e-3)"""
+    mistake, family, pattern, build, shape = MASK_TEETH[i]
+    c = build()
+    if shape is not None:
+        c = C.cut_case(c, *shape)
+    additive = pattern in C.ADD_PATTERNS
+    for pv in ("fp16", "bf16"):
+        if mistake == "bf16_read_as_fp16" and pv != "bf16":
+            continue
+        d = C.with_mask(c, C.mask_pattern(pattern, c["M"], c["N"], _MASK_DTYPE[pv]))
+        assert (d["mask"].dtype != torch.bool) == additive
+        clean = max(C.mask_ratios(d, pv, *C.restate_mask64(d, pv)))
+        r = max(C.mask_ratios(d, pv, *C.restate_mask64(d, pv, mistake)))
+        print(f"teeth: {mistake:22s} on {family:12s} {pattern:15s} D={c['D']:<3d} {pv:5s} ratio {r:12.1f}   (no mistake: {clean:.1e})")
+        assert clean < 1e-3, (pv, clean)
+        assert r > 1.0, (mistake, family, pattern, pv, r)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("backend", list(C.PUBLIC_BACKENDS))
+def test_public_forms_come_back_from_the_quantizers(backend, D):
+    """Q and K of every public_form case, through the oracle's quantizers of the backend ("triton": per-thread, scale + 1e-7;
+    "cuda": per-block with sm_scale * log2e folded into Q, the CUDA rounding) without K smoothing: q8, k8 and both compact
+    scales come back exactly, in fp16 and in bf16, and the oracle with a mask stays inside the bound on the form"""
+    for label, d in C.public_cases(D, backend):
+        sc = C.scale_matrix(d)
+        assert torch.equal(torch.log2(sc), torch.log2(sc).round()), label
+        assert float(d["q_real_rows"].min()) >= 2.0 and float(d["k_scale"].min()) >= 2.0
+        for dt in (torch.float16, torch.bfloat16):
+            q, k = C.public_qk(d, dt)
+            if backend == "triton":
+                q8, qs, k8, ks = C.O.per_thread_int8(q, k)
+            else:
+                q8, qs, k8, ks = C.O.per_block_int8(q, k, sm_scale=d["sm_scale"], rounding="cuda")
+            assert torch.equal(q8, d["q8"]) and torch.equal(k8, d["k8"]), (label, dt)
+            gran = C.PUBLIC_BACKENDS[backend]  # (the groups of rows >= M hold no row: compare the scales row by row)
+            assert torch.equal(C.O.expand_q_scale(qs, d["M"], gran), d["q_scale_rows"]), (label, dt)
+            assert torch.equal(C.O.expand_k_scale(ks, d["N"], gran), d["k_scale_cols"]), (label, dt)
+        for pv in ("fp16", "bf16"):
+            for name, mask in C.mask_patterns(dtype=_MASK_DTYPE[pv], names=C.PUBLIC_PATTERNS):
+                m = C.with_mask(d, mask)
+                ro, rl = C.mask_ratios(m, pv, *C.oracle(m, pv))
+                assert ro <= 1.0 and rl <= 1.0, (label, name, pv, ro, rl)
