@@ -793,6 +793,42 @@ int sage_attn_fusedq_pv_f8_splitkv(const sage_tensor* q, int q_dtype, const sage
                                    int N, int D, int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens,
                                    int num_splits, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
+/* ==== causal split-KV attention (new: a speculative chunk, a multi-token decode step, a chunk of a chunked prefill over a
+ * padded KV cache.  The causal mask of every other entry point is top-left aligned -- row i sees keys 0..i -- which with
+ * M << N masks nearly every key.  Here the M query rows are the LAST tokens of the batch's valid keys: the alignment that
+ * FlashAttention calls bottom-right, with a diagonal that moves with kv_lens[b] on the device) ====
+ * Inputs and workspace: those of sage_attn_fusedq_pv_{f16,f8}_splitkv, and a fold q_fold = g >= 1 that divides M.  The rule:
+ *   - len_b = clamp(kv_lens[b], 0, N), or N without kv_lens.  The M rows are T = M / g tokens of g rows each, token-major:
+ *     row r is token t = r / g (with grouped-query attention, the g = Hq / Hk query heads of a KV head folded into rows:
+ *     [B,Hq,T,D] -> [B,Hk,T*g,D], row t*g + i = head i of token t).  off_b = len_b - T; it may be negative.
+ *   - Row r attends the keys j with 0 <= j <= t + off_b (which implies j < len_b).  A row with t + off_b < 0 has no key --
+ *     the chunk is longer than what the cache holds -- and gets o = 0, lse = -inf.  len_b == 0: o = 0, lse = -inf everywhere.
+ *   - Split ranges, statistics, partial results and the merge arithmetic are exactly those of the non-causal form above:
+ *     split s owns the tiles [s * tps_b, min((s + 1) * tps_b, ntk_b)); km, the K scales and the FP8 v_scale are those of the
+ *     length-aware pre-pass of the whole call (padding rows influence nothing, NaN included); the merge runs in split order
+ *     without atomics, and two calls give the same bits.  A split in which a row keeps no key takes no part in that row's sums.
+ *   - Which workgroups run.  For q-block qb (128 rows) let end_qb = min(len_b, floor(min(128 qb + 127, M - 1) / g) + off_b + 1),
+ *     the key bound of its last row.  Workgroup (b, h, qb, s) runs iff 64 * s * tps_b < end_qb.  The merge derives the same
+ *     count per q-block, min(ceil(ntk_b / tps_b), ceil(ceil(end_qb / 64) / tps_b)) (0 for end_qb <= 0), and loads no slot at
+ *     or beyond it; a q-block with count 0 gets o = 0, lse = -inf, and the merge reads neither the workspace nor the parked
+ *     q . km correction for it.
+ *   - num_splits = 1 is valid and runs this kernel with one split: there is no dense operator with this alignment.
+ *   - T = 1, g = 1 is the non-causal form: the one token sees every valid key, and o and lse have its bits.
+ * The arguments of sage_attn_fusedq_pv_{f16,f8}_splitkv with q_fold inserted after num_splits.  q_fold < 1 or M % q_fold != 0
+ * -> SAGE_ERR_INVALID_ARGUMENT; everything the non-causal form refuses is refused here with the same status. */
+int sage_attn_fusedq_pv_f16_splitkv_causal(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v,
+                                           int v_dtype, const sage_tensor* o, int o_dtype, const float* k_scale,
+                                           const void* km, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                           int N, int D, int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens,
+                                           int num_splits, int q_fold, void* workspace, size_t workspace_bytes,
+                                           sage_stream_t stream);
+int sage_attn_fusedq_pv_f8_splitkv_causal(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v_fp8,
+                                          const sage_tensor* o, int o_dtype, const float* k_scale, const void* km,
+                                          const float* v_scale, const float* v_mean, float* lse, int B, int Hq, int Hk, int M,
+                                          int N, int D, int qk_gran, int warpq, float sm_scale, const int32_t* kv_lens,
+                                          int num_splits, int q_fold, void* workspace, size_t workspace_bytes,
+                                          sage_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

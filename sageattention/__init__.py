@@ -16,7 +16,7 @@ __all__ = ["qattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp8_cu
            "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_qk_int8_pv_fp16_triton"]
 
 _LAZY = {"sageattn": ".core", "sageattn_varlen": ".core", "ring_sageattn": ".core", "ulysses_sageattn": ".core",
-         "sageattn_splitkv": ".core", "splitkv_num_splits": ".core"}
+         "sageattn_splitkv": ".core", "splitkv_num_splits": ".core", "sageattn_splitkv_causal": ".core"}
 
 
 def __getattr__(name):

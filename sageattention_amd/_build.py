@@ -27,6 +27,8 @@ SOURCES = [
                                            "-structurizecfg-skip-uniform-regions"]),
     # the split-KV kernels (the same body and flags) and their merge
     ("sage_attn_splitkv.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # ... and their causal twins (the diagonal aligned to the end of the batch's keys)
+    ("sage_attn_splitkv_causal.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -69,6 +71,7 @@ def _check_occupancy(src, compiler_output):
                             re.search(r"attn_i8_blocksparse_kernelILi64E(Lb[01]E){3}EE", name) or  # the block-sparse twins
                             re.search(r"attn_i8_kvlen_kernelILi64ELi4E(Lb[01]E){4}EE", name) or     # ... with key lengths
                             re.search(r"attn_i8_splitkv_kernelILi64E(Lb[01]E){3}EE", name) or       # ... over splits of the keys
+                            re.search(r"attn_i8_splitkv_causal_kernelILi64E(Lb[01]E){3}EE", name) or  # ... with the diagonal
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
                             re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name) or
                             # the block-sparse kernels with key lengths, held to the lines of their twins above
@@ -177,6 +180,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_sparse_kvlen.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_sparse_kvlen_pvskip.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_causal.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

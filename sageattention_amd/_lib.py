@@ -196,6 +196,13 @@ SIGNATURES = {
     "sage_attn_fusedq_pv_f8_splitkv": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                                c_int, c_void_p, c_size_t, c_void_p]),
+    # ... causal, the chunk aligned to the end of the keys: the same arguments with q_fold behind num_splits
+    "sage_attn_fusedq_pv_f16_splitkv_causal": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                       c_float, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "sage_attn_fusedq_pv_f8_splitkv_causal": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                      c_float, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -24,7 +24,8 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen",
            "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge", "sparge_plan",
            "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen",
-           "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits"]
+           "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits",
+           "sageattn_splitkv_causal"]
 
 
 def _common_checks(q, k, v):
@@ -591,11 +592,13 @@ def splitkv_num_splits(B: int, Hq: int, M: int, N: int) -> int:
     return max(1, min(SPLITKV_MAX, -(-ntk // SPLITKV_MIN_TILES), -(-SPLITKV_SLOTS // max(grid, 1))))
 
 
-def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, num_splits, workspace=None, out=None):
+def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, num_splits, workspace=None, out=None,
+                  q_fold=None):
     """sage_attn_fusedq_pv_{f16,f8}_splitkv on the operands ``kv`` of ``_prepass``: the workspace (the fp32 partial results of
     the splits), the attention launch over the splits and the merge.  ``workspace`` (uint8, on q's device) and ``out`` (a
     tensor or view of q's shape and dtype with a contiguous last dim) are the caller's where given: afterwards the workspace
-    holds the partials, [S,B,Hq,M,D] fp32 and behind them [S,B,Hq,M] fp32.  -> (o, lse or None)"""
+    holds the partials, [S,B,Hq,M,D] fp32 and behind them [S,B,Hq,M] fp32.  With ``q_fold`` (an int): the causal entry points
+    sage_attn_fusedq_pv_{f16,f8}_splitkv_causal.  -> (o, lse or None)"""
     k8, ks, km, v, v_scale, _ = kv
     qk_quant_gran, warpq = q_quant
     B, Hq, M, D = L.dims(q, tensor_layout)
@@ -610,6 +613,8 @@ def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, 
     nbytes = ws.numel()
     shape = (B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
     tail = (L.ptr(kv_lens), num_splits, ws.data_ptr(), nbytes, L.stream_ptr(q.device))
+    if q_fold is not None:
+        tail = tail[:2] + (int(q_fold),) + tail[2:]
     if v_scale is not None:
         name = "sage_attn_fusedq_pv_f8_splitkv"
         args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc_vt(v, tensor_layout),
@@ -620,6 +625,8 @@ def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, 
         args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc(v, tensor_layout),
                 L.dtype_code(v.dtype), L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), None,
                 L.ptr(lse))
+    if q_fold is not None:
+        name += "_causal"
     L.check(getattr(lib, name)(*args, *shape, *tail), name)
     return o, lse
 
@@ -701,6 +708,86 @@ def sageattn_splitkv(
             sm_scale = head_dim_og ** -0.5
         kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
         o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits)
+        return _pack(o[..., :head_dim_og], lse, None, None)
+
+
+@torch.compiler.disable
+def sageattn_splitkv_causal(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    kv_lens: Optional[torch.Tensor] = None,
+    num_splits: Optional[int] = None,
+    q_fold: int = 1,
+    tensor_layout: str = "HND",
+    sm_scale: Optional[float] = None,
+    pv: str = "fp16",
+    qk_quant_gran: str = "per_thread",
+    return_lse: bool = False,
+    **refused: Any,
+):
+    """Causal ``sageattn_splitkv`` for a chunk of new tokens at the END of a padded KV cache: a speculative chunk, a
+    multi-token decode step, a chunk of a chunked prefill.  The query rows are the last tokens of batch b's ``len_b =
+    clamp(kv_lens[b], 0, N)`` valid keys (N without ``kv_lens``) -- the alignment FlashAttention calls bottom-right, where the
+    ``is_causal`` of the other operators is top-left aligned.  The rule (include/sageattn_hip.h, causal split-KV attention):
+
+    * ``g = q_fold >= 1`` divides the M query rows: they are ``T = M / g`` tokens, and row r is token ``t = r // g``.
+    * ``off_b = len_b - T`` (it may be negative).  Row r attends the keys ``0 <= j <= t + off_b`` and nothing later.
+    * A row with ``t + off_b < 0`` has no key -- the chunk is longer than the cache holds -- and gets o = 0, lse = -inf, as
+      does every row of a batch with ``len_b = 0``.
+    * Split ranges, the statistics of the whole call (K smoothing mean, K scales and FP8 V scale from the length-aware
+      pre-pass: nothing in rows >= len_b of k or v influences any output, NaN included) and the deterministic merge in split
+      order are those of ``sageattn_splitkv``.  A (batch, head, 128-row q-block, split) none of whose rows has a key in the
+      split launches a workgroup that returns at once; the merge derives the same count and does not read its slot.
+
+    The fold is for grouped-query attention: the ``g = Hq // Hk`` query heads of a KV head become query rows, TOKEN-MAJOR --
+    ``[B, Hq, T, D] -> [B, Hk, T*g, D]`` (HND), row ``t*g + i`` is head i of token t, i.e. ``q.view(B, Hk, g, T,
+    D).transpose(2, 3).reshape(B, Hk, T*g, D)`` and the inverse on o -- so that K and V are read once per KV head and 4
+    speculative tokens of 8 heads fill one wave.  All g rows of a token see the same keys.
+
+    ``kv_lens`` (optional int32 [B] on q's device) is read on the device only: no host synchronisation, the call captures into
+    a HIP graph and a replay moves the diagonal with the lengths the tensor holds then.  ``num_splits``: 1..16, or None for
+    ``splitkv_num_splits(B, Hq, M, N)``; 1 is valid and runs the same kernel with one split (there is no dense operator with
+    this alignment to hand over to).  ``pv`` ("fp16" | "fp8") is explicit; ``pv="fp8"`` with ``kv_lens`` wants k and v of one
+    shape.  With T = 1 and g = 1 the one token sees every valid key and the result has the bits of ``sageattn_splitkv``.
+
+    K smoothing always on, V not smoothed, ``per_warp`` or ``per_thread`` scales.  ``attn_mask``, ``block_map`` / ``plan``,
+    ``cu_seqlens_q`` / ``cu_seqlens_k``, ``smooth_k=False`` and ``smooth_v`` are refused by name (ValueError), and so is
+    ``is_causal=False``: the operator has no non-causal form to offer, that is ``sageattn_splitkv``."""
+    neutral = {"is_causal": True, "attn_mask": None, "block_map": None, "plan": None, "cu_seqlens_q": None, "cu_seqlens_k": None,
+               "smooth_k": True, "smooth_v": False}  # what is not built, and the one value of each that asks for nothing
+    for name, value in refused.items():
+        if name not in neutral:
+            raise TypeError(f"sageattn_splitkv_causal() got an unexpected keyword argument '{name}'")
+        if value is not neutral[name]:
+            raise ValueError(f"sageattn_splitkv_causal does not take {name}={value!r}: it is causal, without a mask, a block "
+                             "map or packed sequences, K smoothing always on and V not smoothed")
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+    if kv_lens is not None:
+        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+        if pv == "fp8" and k.shape != v.shape:
+            raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if num_splits is not None:
+        if isinstance(num_splits, bool) or not isinstance(num_splits, int):
+            raise TypeError(f"num_splits must be an int in [1, {SPLITKV_MAX}] or None, got {type(num_splits).__name__}")
+        if not 1 <= num_splits <= SPLITKV_MAX:
+            raise ValueError(f"num_splits must be in [1, {SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    if isinstance(q_fold, bool) or not isinstance(q_fold, int):
+        raise TypeError(f"q_fold must be an int >= 1, got {type(q_fold).__name__}")
+    B, Hq, M, _ = L.dims(q, tensor_layout)
+    N = L.dims(k, tensor_layout)[2]
+    if q_fold < 1 or M % q_fold != 0:
+        raise ValueError(f"q_fold must be >= 1 and divide the {M} query rows, got {q_fold}")
+    if num_splits is None:
+        num_splits = splitkv_num_splits(B, Hq, M, N)
+    _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
+        o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits,
+                               q_fold=q_fold)
         return _pack(o[..., :head_dim_og], lse, None, None)
 
 

@@ -154,7 +154,7 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   }
   if (a.split_kv) {  // split-KV: the fused-Q dense padded form only; its workspace is read and written 16 bytes aligned
     if (a.num_splits < 1 || a.num_splits > SAGE_MERGE_MAX || !a.split_workspace || !aligned16(a.split_workspace) ||
-        ((uintptr_t)a.split_kv_lens & 3))
+        ((uintptr_t)a.split_kv_lens & 3) || (a.split_causal && (a.q_fold < 1 || a.M % a.q_fold != 0)))
       return SAGE_ERR_INVALID_ARGUMENT;
     if (sparse || a.key_lens || a.is_causal || a.mask || a.cu_q || a.cu_k || a.kvl || a.v_mean || a.q_dtype < 0 || !a.km)
       return SAGE_ERR_UNSUPPORTED;
@@ -260,7 +260,9 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     p.sk_lse = p.sk_o + (int64_t)a.num_splits * a.B * a.Hq * a.M * a.D;
     p.num_splits = a.num_splits;
     p.kv_lens = a.split_kv_lens;
+    if (a.split_causal) p.q_fold = a.q_fold;  // (... and the word of the third mask stride)
   }
+  c.splitkv_causal = a.split_kv && a.split_causal;
   c.D = a.D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;

@@ -1,12 +1,14 @@
 // The body of the attention kernels: included INTO attn_i8_kernel and attn_i8_blocksparse_kernel (sage_attn.hip),
 // attn_i8_blocksparse_pvskip_kernel (sage_attn_pvskip.hip), attn_i8_kvlen_kernel (sage_attn_kvlen.hip),
 // attn_i8_blocksparse_kvlen_kernel (sage_attn_sparse_kvlen.hip) and attn_i8_blocksparse_pvskip_kvlen_kernel
-// (sage_attn_sparse_kvlen_pvskip.hip) and attn_i8_splitkv_kernel (sage_attn_splitkv.hip), not a header in the usual sense.
+// (sage_attn_sparse_kvlen_pvskip.hip), attn_i8_splitkv_kernel (sage_attn_splitkv.hip) and attn_i8_splitkv_causal_kernel
+// (sage_attn_splitkv_causal.hip), not a header in the usual sense.
 // Expects in scope: the kernel parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8,
 // HAS_MASK, SPARSE, PVSKIP, KVLEN, SPLITKV
 // (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip; SPARSE && KVLEN: the tile lists
 // clipped at the batch's length, sage_attn_sparse_kvlen.hip; SPLITKV: one workgroup per (b, h, q-block, split) walks the
-// split's range of key tiles and stores an fp32 partial result, sage_attn_splitkv.hip).
+// split's range of key tiles and stores an fp32 partial result, sage_attn_splitkv.hip; CAUSAL && SPLITKV: the diagonal is
+// aligned to the END of the batch's keys and counts tokens of p.q_fold query rows, sage_attn_splitkv_causal.hip).
 #ifndef SAGE_ATTN_BODY_OF_KERNEL
 #error "sage_attn_body.h is the body of the attention kernels (sage_attn*.hip): included nowhere else"
 #endif
@@ -15,8 +17,8 @@
   static_assert(!SPARSE || (NWAVES == 4 && !CAUSAL && !HAS_MASK), "block-sparse: 4 waves = one block row of the map, non-causal");
   static_assert(!PVSKIP || SPARSE, "the P.V skip exists in the block-sparse form only");
   static_assert(!KVLEN || !HAS_MASK, "per-batch key lengths: the dense or the block-sparse kernel, without attn_mask");
-  static_assert(!SPLITKV || (!CAUSAL && !HAS_MASK && !SPARSE && !KVLEN && NWAVES == 4),
-                "split-KV: 4 waves, non-causal, no attn_mask, no block map (its optional lengths are its own: p.kv_lens may be null)");
+  static_assert(!SPLITKV || (!HAS_MASK && !SPARSE && !KVLEN && NWAVES == 4),
+                "split-KV: 4 waves, no attn_mask, no block map (its optional lengths are its own: p.kv_lens may be null)");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -105,6 +107,12 @@
   // on the moved operands.  Wave-uniform, before any barrier; a workgroup whose range is empty stores nothing.
   int sk_t0 = 0;
   (void)sk_t0;
+  // causal split-KV (the rule: include/sageattn_hip.h, sage_attn_fusedq_pv_*_splitkv_causal): row r is token t = r / g,
+  // g = p.q_fold, and attends the keys j <= t + off_b, off_b = len_b - M / g: the M / g tokens are the LAST positions of the
+  // batch's len_b keys.  sk_off is off_b in the coordinates of the moved operands, off_b - 64 * sk_t0 = (keys from the split's
+  // first one to len_b) - M / g: the first term is positive for a split that runs, so the difference cannot overflow.
+  int sk_off = 0;
+  (void)sk_off;
   if constexpr (SPLITKV) {
     int len_b = p.N;
     if (p.kv_lens) len_b = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
@@ -113,6 +121,7 @@
     const int t1 = min(sk_t0 + tps_b, ntk_b);
     if (sk_t0 >= t1) return;
     N_ = min(len_b, t1 << 6) - (sk_t0 << 6);
+    if constexpr (CAUSAL) sk_off = (len_b - (sk_t0 << 6)) - M_ / p.q_fold;
   }
   // block-sparse: the list row of this (b, h, q-block) = its count, then the ascending tile indices, padded with the last
   // valid one for kBlockListPad entries so that every read-ahead below is blind.  The first entries are requested together
@@ -183,6 +192,18 @@
   // the lane's row / key-half as the masked tiles and the epilogue see them: re-derived from the lane id after the fast loop
   // (below), so that neither they nor the output addresses built from them occupy registers while it runs
   int row_l = row, hh_l = hh;
+  // causal split-KV: the last key (of the moved operands) the lane's row may attend, token + sk_off, what `row_l` is to the
+  // top-left diagonal of the dense kernel.  Every negative limit means "no key of this split" and is held at -1, so that the
+  // tile offsets mask_limit subtracts from it cannot wrap.  Rows >= M are never stored.  One divide per lane here, for tile 0,
+  // and one more behind the fast loop, where row_l is re-derived: kept in a register through the loop instead, the limit
+  // costs the head_dim-64 FP8 variant with per-thread scales its third wave per SIMD (168 registers and 84 bytes of scratch).
+  int lim_l = 0, sk_tok0 = 0, sk_tok1 = 0;  // ... and the tokens of the wave's first row and of its last row < M
+  (void)lim_l; (void)sk_tok0; (void)sk_tok1;
+  if constexpr (CAUSAL && SPLITKV) {
+    lim_l = max(row / p.q_fold + sk_off, -1);
+    sk_tok0 = q0 / p.q_fold;
+    sk_tok1 = min(q0 + 31, M_ - 1) / p.q_fold;
+  }
 
   // ---- Q^T fragments (B operand), resident for the whole kernel, and the per-row q scale
   // (a lambda: it runs AFTER the first K/V tile copies have been issued, below -- nothing in it depends on them, and with
@@ -312,9 +333,22 @@
   if constexpr (SPLITKV) ksp += (int64_t)sk_t0 * p.ks_t;
 
   // ---- tile range
-  const int kv_end = CAUSAL ? min(N_, (qb + 1) * QB) : N_;
+  // (causal split-KV: up to the key bound of the q-block's last row < M.  A workgroup none of whose rows has a key in this
+  //  split stores nothing -- the merge derives the same count of splits for the q-block and reads no slot beyond it.  Wave
+  //  uniform, before any barrier.)
+  int sk_end = 0;
+  (void)sk_end;
+  if constexpr (CAUSAL && SPLITKV) {
+    sk_end = min((qb + 1) * QB - 1, M_ - 1) / p.q_fold + sk_off + 1;
+    if (sk_end <= 0) return;
+  }
+  const int kv_end = CAUSAL ? min(N_, SPLITKV ? sk_end : (qb + 1) * QB) : N_;
   const int ntiles = SPARSE ? bs_count : (kv_end + 63) >> 6;  // block-sparse: list positions
-  const int wave_tiles = CAUSAL ? min(ntiles, ((q0 + 31) >> 6) + 1) : ntiles;
+  // (causal split-KV: the tiles up to the bound of the wave's last row, at least one -- a wave whose rows all end before this
+  //  split's range computes tile 0, masks all of it and then stages like any causal wave that is done)
+  const int wave_tiles = CAUSAL ? min(ntiles, SPLITKV ? max(1, (min(N_, max(sk_tok1 + sk_off, -1) + 1) + 63) >> 6)
+                                                      : ((q0 + 31) >> 6) + 1)
+                                : ntiles;
 
   // ---- staging (global -> LDS by LDS-DMA).  Buffer addressing: the descriptor holds the (b, h_kv) slice, the
   //      per-thread byte offset is constant for the whole kernel and the tile advance is a scalar offset, so a
@@ -528,7 +562,11 @@
   // sequence end and causal diagonal (the kernels without attn_mask): register e of block mt holds key
   // 64*j + 32*mt + (e&3) + 8*(e>>2) + 4*hh, allowed iff <= min(N-1, row): one compare against a per-lane limit
   auto mask_limit = [&](const int j, v16i (&s)[2]) __attribute__((always_inline)) {
-    const int lim = min(N_ - 1, CAUSAL ? row_l : 0x7fffffff) - (j << 6) - 4 * hh_l;
+    // (causal split-KV under `if constexpr`: named in the expression of the others, lim_l is captured by this lambda in every
+    //  kernel, and the FP8 head_dim-64 block-sparse kernels came out with two scalar moves in another order)
+    int lim;
+    if constexpr (CAUSAL && SPLITKV) lim = min(N_ - 1, lim_l) - (j << 6) - 4 * hh_l;
+    else lim = min(N_ - 1, CAUSAL ? row_l : 0x7fffffff) - (j << 6) - 4 * hh_l;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -730,7 +768,9 @@
   } else {
     if (N_ & 63) n_plain = min(n_plain, N_ >> 6);
   }
-  if constexpr (CAUSAL) n_plain = min(n_plain, max(0, (q0 + 1) >> 6));  // tile j needs no mask iff 64*j+63 <= q0
+  // tile j needs no mask iff 64*j+63 <= q0 (causal split-KV: <= the limit of the wave's first row)
+  if constexpr (CAUSAL && SPLITKV) n_plain = min(n_plain, (max(sk_tok0 + sk_off, -1) + 1) >> 6);
+  else if constexpr (CAUSAL) n_plain = min(n_plain, max(0, (q0 + 1) >> 6));
   const int n_fast = (CAN_MASK && p.mask) ? 0 : max(0, min(n_plain - 1, wave_tiles - 1));  // attn_mask: all tiles generic
 
   // tile copies a wave issues per iteration (full tiles): the unit of the counted waits of the four-slot ring
@@ -1197,6 +1237,7 @@
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     row_l = q0 + (ln & 31);
     hh_l = ln >> 5;
+    if constexpr (CAUSAL && SPLITKV) lim_l = max(row_l / p.q_fold + sk_off, -1);
   }
   // staging with run-time slots: the compiler-scheduled tail body below and, for causal waves that are done early, staging-only iterations;
   // every copy drained (vmcnt(0)) -- the four-slot ring keeps its copy COUNT per iteration constant here as well

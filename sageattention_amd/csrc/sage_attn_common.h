@@ -46,7 +46,10 @@ struct AttnParams {
   //  mask strides: pv_thresh fp32 [Hq], pv_skipped int32 [B,Hq,nqb,4] or null)
   union { int64_t msb; const float* pv_thresh; float* sk_lse; };
   union { int64_t msh; int32_t* pv_skipped; };
-  int64_t msm, msn;
+  // (causal split-KV -- attn_i8_splitkv_causal_kernel, sage_attn_splitkv_causal.hip -- keeps its fold g >= 1 in the third mask
+  //  stride: query row r is token r / g, and the diagonal counts tokens)
+  union { int64_t msm; int q_fold; };
+  int64_t msn;
   union { int mask_kind; int bs_row; int num_splits; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
   // (b, h_kv) in k8 and in v (always set by attn_check; the dense defaults are 64 rows), and the strides of k_scale

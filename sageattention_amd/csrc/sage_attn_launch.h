@@ -27,4 +27,13 @@ static int launch_blocksparse_kernel(const AttnCall& c, hipStream_t st, KernelOf
   });
 }
 
+// slot count of the split-KV merge kernels as a compile-time constant: the first of 2, 4, 8, 16 that holds S
+template <class F>
+static void by_slots(int count, F&& f) {
+  if (count <= 2) f(std::integral_constant<int, 2>{});
+  else if (count <= 4) f(std::integral_constant<int, 4>{});
+  else if (count <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+
 }  // namespace sage

@@ -90,17 +90,9 @@ __global__ __launch_bounds__(256) void splitkv_merge_kernel(const AttnParams p, 
   }
 }
 
-// merge kernel's slot count as a compile-time constant: the first of 2, 4, 8, 16 that holds S
-template <class F>
-static void by_slots(int count, F&& f) {
-  if (count <= 2) f(std::integral_constant<int, 2>{});
-  else if (count <= 4) f(std::integral_constant<int, 4>{});
-  else if (count <= 8) f(std::integral_constant<int, 8>{});
-  else f(std::integral_constant<int, 16>{});
-}
-
 // the attention launch over (b, h, q-block, split), then the merge
 int launch_splitkv(const AttnCall& c, hipStream_t st) {
+  if (c.splitkv_causal) return launch_splitkv_causal(c, st);  // kernels of their own (sage_attn_splitkv_causal.hip)
   const AttnParams& p = c.p;
   const int s = by_dim(c.D, [&](auto d) {
     return by_flag(c.pv_fp8, [&](auto fp8) {
@@ -129,10 +121,10 @@ int launch_splitkv(const AttnCall& c, hipStream_t st) {
 }
 
 // the fused-Q argument block of a split-KV entry point (there is no INT8-Q form): 128-row q-blocks, the kernel applies sm_scale
-static AttnArgs splitkv_args(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
-                             const sage_tensor* o, int o_dtype, const float* k_scale, const void* km, const float* v_scale,
-                             const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int warpq,
-                             float sm_scale, const int32_t* kv_lens, int num_splits, void* workspace, size_t workspace_bytes) {
+AttnArgs splitkv_args(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
+                      const sage_tensor* o, int o_dtype, const float* k_scale, const void* km, const float* v_scale,
+                      const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int warpq,
+                      float sm_scale, const int32_t* kv_lens, int num_splits, void* workspace, size_t workspace_bytes) {
   AttnArgs a;
   a.q = q; a.q_dtype = q_dtype; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale;
   a.km = km; a.v_scale = v_scale; a.pv_fp8 = v_scale != nullptr; a.v_mean = v_mean; a.lse = lse;
@@ -143,7 +135,7 @@ static AttnArgs splitkv_args(const sage_tensor* q, int q_dtype, const sage_tenso
   return a;
 }
 
-static int run_splitkv(const AttnArgs& a, int q_dtype, sage_stream_t stream) {
+int run_splitkv(const AttnArgs& a, int q_dtype, sage_stream_t stream) {
   if (q_dtype != SAGE_F16 && q_dtype != SAGE_BF16) return SAGE_ERR_INVALID_ARGUMENT;
   AttnCall c;
   if (const int s = attn_check(c, a)) return s;

@@ -26,6 +26,9 @@ instead of breaking the graph.  The reference marks every entry
     torch.ops.sageattention_amd.attn_sparge_pv_kvlen / attn_sparge_pv_lse_kvlen(..., pvthreshd, kv_lens, ...) -> (o, [lse,] skipped)
     torch.ops.sageattention_amd.attn_splitkv(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran) -> o
     torch.ops.sageattention_amd.attn_splitkv_lse(...) -> (o, lse)   (split-KV: kv_lens an optional tensor, num_splits 0 = automatic)
+    torch.ops.sageattention_amd.attn_splitkv_causal(q, k, v, kv_lens, num_splits, q_fold, tensor_layout, sm_scale, pv,
+                                                    qk_quant_gran) -> o     (causal, the chunk at the end of the keys; q_fold
+    torch.ops.sageattention_amd.attn_splitkv_causal_lse(...) -> (o, lse)     a SymInt: query rows per token)
 
 The bodies call the same host code as ``sageattn_qk_int8_pv_{fp16,fp8}_cuda`` (core.py) and therefore the same HIP
 kernels; the fake (meta) implementations only describe shapes, dtypes and strides.  ``sageattn_compilable`` is the
@@ -37,7 +40,7 @@ import torch
 from . import core
 
 __all__ = ["sageattn_compilable", "sageattn_block_sparse_compilable", "sageattn_sparge_compilable",
-           "sageattn_kvlen_compilable", "sageattn_splitkv_compilable"]
+           "sageattn_kvlen_compilable", "sageattn_splitkv_compilable", "sageattn_splitkv_causal_compilable"]
 
 
 def _entry(pv: str):
@@ -537,6 +540,52 @@ def sageattn_splitkv_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
         sm_scale = q.size(-1) ** -0.5
     op = torch.ops.sageattention_amd.attn_splitkv_lse if return_lse else torch.ops.sageattention_amd.attn_splitkv
     return op(q, k, v, kv_lens, int(num_splits or 0), tensor_layout, float(sm_scale), pv, qk_quant_gran)
+
+
+@torch.library.custom_op("sageattention_amd::attn_splitkv_causal", mutates_args=())
+def attn_splitkv_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor], num_splits: int,
+                        q_fold: int, tensor_layout: str, sm_scale: float, pv: str, qk_quant_gran: str) -> torch.Tensor:
+    return core.sageattn_splitkv_causal(q, k, v, kv_lens=kv_lens, num_splits=num_splits or None, q_fold=q_fold,
+                                        tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
+                                        qk_quant_gran=qk_quant_gran).contiguous()
+
+
+@attn_splitkv_causal.register_fake
+def _(q, k, v, kv_lens, num_splits, q_fold, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape)
+
+
+@torch.library.custom_op("sageattention_amd::attn_splitkv_causal_lse", mutates_args=())
+def attn_splitkv_causal_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor],
+                            num_splits: int, q_fold: int, tensor_layout: str, sm_scale: float, pv: str,
+                            qk_quant_gran: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    o, lse = core.sageattn_splitkv_causal(q, k, v, kv_lens=kv_lens, num_splits=num_splits or None, q_fold=q_fold,
+                                          tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv, qk_quant_gran=qk_quant_gran,
+                                          return_lse=True)
+    return o.contiguous(), lse
+
+
+@attn_splitkv_causal_lse.register_fake
+def _(q, k, v, kv_lens, num_splits, q_fold, tensor_layout, sm_scale, pv, qk_quant_gran):
+    return q.new_empty(q.shape), _lse_like(q, tensor_layout)
+
+
+def sageattn_splitkv_causal_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                                       kv_lens: Optional[torch.Tensor] = None, num_splits: Optional[int] = None,
+                                       q_fold: int = 1, tensor_layout: str = "HND", sm_scale: Optional[float] = None,
+                                       pv: str = "fp16", qk_quant_gran: str = "per_thread", return_lse: bool = False):
+    """``sageattn_splitkv_causal`` (core.py) as a traceable custom op: ``kv_lens`` is an optional int32 [B] tensor argument of
+    the op, ``num_splits`` an int with 0 for the automatic choice (``core.splitkv_num_splits``), ``q_fold`` the query rows per
+    token."""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if num_splits is not None and not 1 <= int(num_splits) <= core.SPLITKV_MAX:
+        raise ValueError(f"num_splits must be in [1, {core.SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    if sm_scale is None:
+        sm_scale = q.size(-1) ** -0.5
+    ns = torch.ops.sageattention_amd
+    op = ns.attn_splitkv_causal_lse if return_lse else ns.attn_splitkv_causal
+    return op(q, k, v, kv_lens, int(num_splits or 0), q_fold, tensor_layout, float(sm_scale), pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",

@@ -13,7 +13,16 @@ S in {1, 2, 4, 8, 16} (S = 1 is the dense operator through the new entry) and wi
   (4, 32, 8192, 8192, 128)     the control: the grid fills the chip, the automatic choice must be 1 (S = 2 only beside it)
 The attention and the merge kernel of every S are listed separately, from a torch.profiler trace of a few calls.
 
-usage: splitkv_bench.py [--repeats 5] [--window-ms 100] [--pv fp16,fp8] [--commit HASH] [--out profiles/splitkv.md]"""
+``--causal``: ``sageattn_splitkv_causal`` (the chunk aligned to the end of the keys) instead, written to
+profiles/splitkv_causal.md.  The yardstick is the NON-CAUSAL ``sageattn_splitkv`` of the same shape and S, timed twice per
+rotation; only the last T keys differ between the two, so a ratio near 1.0 is what one would suppose:
+  (1, 40, 512, 32760, 128)     a chunk of a chunked prefill
+  (8, 8, 16, 8192, 128)        a speculative step of 4 tokens, the 4 query heads of a KV head folded into rows (q_fold = 4)
+  (1, 8, 64, 4096, 128)        small enough that ``sageattn_qk_int8_pv_fp16_triton`` with the equivalent bool attn_mask -- the
+                               only way to this result before -- is timed beside it (FP16 PV only: it has no FP8 form)
+There is no pass / fail time: the ratios are reported with the yardstick's spread.
+
+usage: splitkv_bench.py [--causal] [--repeats 5] [--window-ms 100] [--pv fp16,fp8] [--commit HASH] [--out profiles/splitkv.md]"""
 import argparse
 import os
 import statistics
@@ -30,6 +39,7 @@ ap.add_argument("--window-ms", type=float, default=100.0)
 ap.add_argument("--pv", default="fp16,fp8")
 ap.add_argument("--commit", default="")
 ap.add_argument("--out", default="")
+ap.add_argument("--causal", action="store_true")
 a = ap.parse_args()
 lines = []
 
@@ -77,7 +87,7 @@ def fmt_ratio(r):
     return f"{med(r):.3f} ({min(r):.3f} .. {max(r):.3f})"
 
 
-def kernel_times(fn, calls=5):
+def kernel_times(fn, calls=5, attn_name="attn_i8_splitkv_kernel", merge_name="splitkv_merge_kernel"):
     """mean device time (us) of the split-KV attention and merge kernels over `calls` calls -> (attn, merge) or None"""
     try:
         from torch.profiler import ProfilerActivity, profile
@@ -97,9 +107,9 @@ def kernel_times(fn, calls=5):
                     break
             if not tot:
                 continue
-            if "attn_i8_splitkv_kernel" in it.key:
+            if attn_name in it.key:
                 attn += tot; n_attn += it.count
-            elif "splitkv_merge_kernel" in it.key:
+            elif merge_name in it.key:
                 merge += tot; n_merge += it.count
         if not n_attn or not n_merge:
             return None
@@ -123,6 +133,88 @@ def dense_of(pv):
 
 if not torch.cuda.is_available():
     sys.exit("splitkv_bench.py measures on the GPU: none is visible")
+
+
+
+def causal_section():
+    # (label, (B, Hq, Hk, M, N, D) as the operator sees it, q_fold, beside the masked operator?)
+    shapes = [("(1, 40, 512, 32760, 128), a chunk of 512 tokens", (1, 40, 40, 512, 32760, 128), 1, False),
+              ("(8, 8, 16, 8192, 128), 4 speculative tokens folded by the GQA group 4", (8, 8, 8, 16, 8192, 128), 4, False),
+              ("(1, 8, 64, 4096, 128), beside the masked operator", (1, 8, 8, 64, 4096, 128), 1, True)]
+    emit("# sageattn_splitkv_causal: a chunk aligned to the end of the keys, times on MI355X")
+    emit()
+    emit(f"commit {a.commit or 'unknown'}; tools/splitkv_bench.py --causal, one process, the variants of a comparison timed round robin")
+    emit(f"in {a.repeats} rounds, a window = 3 warm-up calls and HIP events around about {a.window_ms:.0f} ms of calls.  fp16 inputs,")
+    emit("per-thread scales, no kv_lens (every batch has N keys), whole calls (pre-pass + attention + merge) on the same tensors.")
+    emit("Times: median over the rounds.  Ratios: median of the per-round ratios (least .. greatest) to \"non-causal\", the")
+    emit("sageattn_splitkv call of the same shape and S.  \"non-causal again\" is that call timed a second time in the same")
+    emit("rotation: its ratio is the spread a ratio has to leave before it says anything.  \"attention us\" / \"merge us\": the two")
+    emit("kernels of the call alone, mean device time from a torch.profiler trace of 5 calls.  No pass / fail time.")
+    notes, slower = [], []
+    for label, (B, Hq, Hk, M, N, D), fold, masked in shapes:
+        S = core.splitkv_num_splits(B, Hq, M, N)
+        emit()
+        emit(f"## {label}")
+        emit()
+        emit(f"q_fold = {fold}: {M // fold} tokens; S = {S} (the automatic choice), grid {B * Hq * ((M + 127) // 128) * S} workgroups")
+        emit()
+        emit("| PV | variant | ms | / non-causal | attention us | merge us |")
+        emit("|---|---|---|---|---|---|")
+        q, k, v = make(B, Hq, Hk, M, N, D, 1)
+        mask = None
+        if masked:  # the band of the rule as the [M, N] bool mask of the masked operator (True = attend)
+            tok = torch.arange(M, device="cuda") // fold
+            mask = torch.arange(N, device="cuda").view(1, -1) <= (tok + (N - M // fold)).view(-1, 1)
+        for pv in a.pv.split(","):
+            variants = {"non-causal": lambda: sa.sageattn_splitkv(q, k, v, num_splits=S, pv=pv),
+                        "non-causal again": lambda: sa.sageattn_splitkv(q, k, v, num_splits=S, pv=pv),
+                        "causal": lambda: sa.sageattn_splitkv_causal(q, k, v, num_splits=S, q_fold=fold, pv=pv)}
+            if masked and pv == "fp16":
+                variants["sageattn_qk_int8_pv_fp16_triton, bool attn_mask"] = \
+                    lambda: sa.sageattn_qk_int8_pv_fp16_triton(q, k, v, attn_mask=mask)
+            t = rounds(variants)
+            again = ratios(t["non-causal again"], t["non-causal"])
+            kts = {}
+            for name in variants:
+                kt = None
+                if name == "causal":
+                    kt = kernel_times(variants[name], 5, "attn_i8_splitkv_causal_kernel", "splitkv_causal_merge_kernel")
+                elif name == "non-causal" and S > 1:
+                    kt = kernel_times(variants[name])
+                kts[name] = kt
+                r = "" if name == "non-causal" else fmt_ratio(ratios(t[name], t["non-causal"]))
+                emit(f"| {pv} | {name} | {med(t[name]):.4f} | {r} | {'' if kt is None else f'{kt[0]:.1f}'} | "
+                     f"{'' if kt is None else f'{kt[1]:.1f}'} |")
+            rc = ratios(t["causal"], t["non-causal"])
+            where = "inside" if min(rc) <= max(again) and max(rc) >= min(again) else ("below" if max(rc) < min(again) else "ABOVE")
+            notes.append((label, pv, med(rc), min(rc), max(rc), min(again), max(again), where))
+            if where == "ABOVE" and kts.get("causal") and kts.get("non-causal"):  # where the time goes: the two kernels apart
+                (ca, cm), (na, nm) = kts["causal"], kts["non-causal"]
+                slower.append(f"{label}, {pv}: the call is {1e3 * (med(t['causal']) - med(t['non-causal'])):.1f} us slower; its "
+                              f"attention kernel takes {ca:.1f} us against {na:.1f} us, its merge {cm:.1f} us against {nm:.1f} us.")
+        del q, k, v
+        torch.cuda.empty_cache()
+    emit()
+    emit("## Causal against non-causal")
+    emit()
+    emit("| shape | PV | causal / non-causal (median, least .. greatest) | non-causal again (least .. greatest) | the causal ratio lies |")
+    emit("|---|---|---|---|---|")
+    for label, pv, m, lo, hi, alo, ahi, where in notes:
+        emit(f"| {label} | {pv} | {m:.3f}, {lo:.3f} .. {hi:.3f} | {alo:.3f} .. {ahi:.3f} | {where} the yardstick's spread |")
+    if slower:
+        emit()
+        emit("Slower than the non-causal call beyond its spread -- where the time goes, from the kernel traces above:")
+        emit()
+        for line in slower:
+            emit("- " + line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if a.causal:
+    causal_section()
+    sys.exit(0)
 
 # (label, (B, Hq, Hk, M, N, D) as the operator sees it, S values of the sweep)
 SHAPES = [("(1, 40, 512, 32760, 128)", (1, 40, 40, 512, 32760, 128), (1, 2, 4, 8, 16)),
