@@ -610,25 +610,60 @@ def _splitkv_attn(q, kv, tensor_layout, q_quant, sm_scale, return_lse, kv_lens, 
     lse = torch.empty((B, Hq, M), dtype=torch.float32, device=q.device) if return_lse else None
     nbytes = lib.sage_splitkv_workspace_bytes(B, Hq, M, D, num_splits)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if workspace is None else workspace
-    nbytes = ws.numel()
-    shape = (B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale))
-    tail = (L.ptr(kv_lens), num_splits, ws.data_ptr(), nbytes, L.stream_ptr(q.device))
-    if q_fold is not None:
-        tail = tail[:2] + (int(q_fold),) + tail[2:]
-    if v_scale is not None:
-        name = "sage_attn_fusedq_pv_f8_splitkv"
-        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc_vt(v, tensor_layout),
-                L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), v_scale.data_ptr(), None,
-                L.ptr(lse))
-    else:
-        name = "sage_attn_fusedq_pv_f16_splitkv"
-        args = (L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), L.desc(v, tensor_layout),
-                L.dtype_code(v.dtype), L.desc(o, tensor_layout), L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), None,
-                L.ptr(lse))
-    if q_fold is not None:
-        name += "_causal"
-    L.check(getattr(lib, name)(*args, *shape, *tail), name)
+    pv_fp8, causal = v_scale is not None, q_fold is not None
+    name = f"sage_attn_fusedq_pv_{'f8' if pv_fp8 else 'f16'}_splitkv{'_causal' if causal else ''}"
+    # in the order of the C signatures: the f8 forms have no v_dtype and take v_scale, the causal forms q_fold
+    v_args = (L.desc_vt(v, tensor_layout),) if pv_fp8 else (L.desc(v, tensor_layout), L.dtype_code(v.dtype))
+    v_scale_args = (v_scale.data_ptr(),) if pv_fp8 else ()
+    causal_args = (int(q_fold),) if causal else ()
+    L.check(getattr(lib, name)(
+        L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), *v_args, L.desc(o, tensor_layout),
+        L.dtype_code(o.dtype), ks.data_ptr(), km.data_ptr(), *v_scale_args, None, L.ptr(lse),
+        B, Hq, Hk, M, N, D, _GRAN_CODE[qk_quant_gran], warpq, float(sm_scale),
+        L.ptr(kv_lens), num_splits, *causal_args, ws.data_ptr(), ws.numel(), L.stream_ptr(q.device)), name)
     return o, lse
+
+
+def _splitkv_front(op, causal, q, k, v, kv_lens, num_splits, tensor_layout, pv, qk_quant_gran, refused):
+    """The argument handling that ``sageattn_splitkv`` and ``sageattn_splitkv_causal`` (``op``: the name in the messages)
+    share: the keywords refused by name -- ``is_causal`` asks for nothing where it is ``causal`` --, the strings, ``kv_lens``,
+    ``num_splits`` and the shape.  -> (kv_lens, num_splits resolved, M)"""
+    neutral = {"is_causal": causal, "attn_mask": None, "block_map": None, "plan": None, "cu_seqlens_q": None, "cu_seqlens_k": None,
+               "smooth_k": True, "smooth_v": False}  # what is not built, and the one value of each that asks for nothing
+    for name, value in refused.items():
+        if name not in neutral:
+            raise TypeError(f"{op}() got an unexpected keyword argument '{name}'")
+        if value is not neutral[name]:
+            raise ValueError(f"{op} does not take {name}={value!r}: it is {'causal' if causal else 'non-causal'}, without a "
+                             "mask, a block map or packed sequences, K smoothing always on and V not smoothed")
+    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
+    if kv_lens is not None:
+        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
+        if pv == "fp8" and k.shape != v.shape:
+            raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if num_splits is not None:
+        if isinstance(num_splits, bool) or not isinstance(num_splits, int):
+            raise TypeError(f"num_splits must be an int in [1, {SPLITKV_MAX}] or None, got {type(num_splits).__name__}")
+        if not 1 <= num_splits <= SPLITKV_MAX:
+            raise ValueError(f"num_splits must be in [1, {SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    B, Hq, M, _ = L.dims(q, tensor_layout)
+    N = L.dims(k, tensor_layout)[2]
+    if num_splits is None:
+        num_splits = splitkv_num_splits(B, Hq, M, N)
+    return kv_lens, num_splits, M
+
+
+def _splitkv_run(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran, return_lse, q_fold=None):
+    """The tail the two split-KV operators share: head-dim padding, the length-aware pre-pass, ``_splitkv_attn``, packing"""
+    _common_checks(q, k, v)
+    with torch.cuda.device(q.device):
+        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
+        if sm_scale is None:
+            sm_scale = head_dim_og ** -0.5
+        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
+        o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits,
+                               q_fold=q_fold)
+        return _pack(o[..., :head_dim_og], lse, None, None)
 
 
 @torch.compiler.disable
@@ -672,28 +707,8 @@ def sageattn_splitkv(
     ``g = Hq // Hk`` query heads of a KV head may be folded into query rows first -- ``q.view(B, Hk, g, D)`` for a
     ``[B, Hq, 1, D]`` query (HND) against the unchanged ``[B, Hk, N, D]`` cache, and ``o.view(B, Hq, 1, D)`` afterwards: K and V
     are then read once per KV head instead of once per query head."""
-    neutral = {"is_causal": False, "attn_mask": None, "block_map": None, "plan": None, "cu_seqlens_q": None, "cu_seqlens_k": None,
-               "smooth_k": True, "smooth_v": False}  # what is not built, and the one value of each that asks for nothing
-    for name, value in refused.items():
-        if name not in neutral:
-            raise TypeError(f"sageattn_splitkv() got an unexpected keyword argument '{name}'")
-        if value is not neutral[name]:
-            raise ValueError(f"sageattn_splitkv does not take {name}={value!r}: it is non-causal, without a mask, a block "
-                             "map or packed sequences, K smoothing always on and V not smoothed")
-    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
-    if kv_lens is not None:
-        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
-        if pv == "fp8" and k.shape != v.shape:
-            raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
-    if num_splits is not None:
-        if isinstance(num_splits, bool) or not isinstance(num_splits, int):
-            raise TypeError(f"num_splits must be an int in [1, {SPLITKV_MAX}] or None, got {type(num_splits).__name__}")
-        if not 1 <= num_splits <= SPLITKV_MAX:
-            raise ValueError(f"num_splits must be in [1, {SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
-    B, Hq, M, _ = L.dims(q, tensor_layout)
-    N = L.dims(k, tensor_layout)[2]
-    if num_splits is None:
-        num_splits = splitkv_num_splits(B, Hq, M, N)
+    kv_lens, num_splits, _ = _splitkv_front("sageattn_splitkv", False, q, k, v, kv_lens, num_splits, tensor_layout, pv,
+                                            qk_quant_gran, refused)
     if num_splits == 1:  # the operator this call names: its launches, its bits
         if kv_lens is not None:
             return sageattn_kvlen(q, k, v, kv_lens, tensor_layout=tensor_layout, sm_scale=sm_scale, pv=pv,
@@ -701,14 +716,7 @@ def sageattn_splitkv(
         dense = sageattn_qk_int8_pv_fp8_cuda if pv == "fp8" else sageattn_qk_int8_pv_fp16_cuda
         return dense(q, k, v, tensor_layout=tensor_layout, is_causal=False, qk_quant_gran=qk_quant_gran, sm_scale=sm_scale,
                      return_lse=return_lse)
-    _common_checks(q, k, v)
-    with torch.cuda.device(q.device):
-        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
-        if sm_scale is None:
-            sm_scale = head_dim_og ** -0.5
-        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
-        o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits)
-        return _pack(o[..., :head_dim_og], lse, None, None)
+    return _splitkv_run(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran, return_lse)
 
 
 @torch.compiler.disable
@@ -754,41 +762,13 @@ def sageattn_splitkv_causal(
     K smoothing always on, V not smoothed, ``per_warp`` or ``per_thread`` scales.  ``attn_mask``, ``block_map`` / ``plan``,
     ``cu_seqlens_q`` / ``cu_seqlens_k``, ``smooth_k=False`` and ``smooth_v`` are refused by name (ValueError), and so is
     ``is_causal=False``: the operator has no non-causal form to offer, that is ``sageattn_splitkv``."""
-    neutral = {"is_causal": True, "attn_mask": None, "block_map": None, "plan": None, "cu_seqlens_q": None, "cu_seqlens_k": None,
-               "smooth_k": True, "smooth_v": False}  # what is not built, and the one value of each that asks for nothing
-    for name, value in refused.items():
-        if name not in neutral:
-            raise TypeError(f"sageattn_splitkv_causal() got an unexpected keyword argument '{name}'")
-        if value is not neutral[name]:
-            raise ValueError(f"sageattn_splitkv_causal does not take {name}={value!r}: it is causal, without a mask, a block "
-                             "map or packed sequences, K smoothing always on and V not smoothed")
-    _check_sparse_args(pv, qk_quant_gran, tensor_layout)
-    if kv_lens is not None:
-        kv_lens = _check_kv_lens(kv_lens, q.size(0), q.device)
-        if pv == "fp8" and k.shape != v.shape:
-            raise ValueError(f"pv='fp8' with kv_lens needs k and v of one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
-    if num_splits is not None:
-        if isinstance(num_splits, bool) or not isinstance(num_splits, int):
-            raise TypeError(f"num_splits must be an int in [1, {SPLITKV_MAX}] or None, got {type(num_splits).__name__}")
-        if not 1 <= num_splits <= SPLITKV_MAX:
-            raise ValueError(f"num_splits must be in [1, {SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    kv_lens, num_splits, M = _splitkv_front("sageattn_splitkv_causal", True, q, k, v, kv_lens, num_splits, tensor_layout,
+                                            pv, qk_quant_gran, refused)
     if isinstance(q_fold, bool) or not isinstance(q_fold, int):
         raise TypeError(f"q_fold must be an int >= 1, got {type(q_fold).__name__}")
-    B, Hq, M, _ = L.dims(q, tensor_layout)
-    N = L.dims(k, tensor_layout)[2]
     if q_fold < 1 or M % q_fold != 0:
         raise ValueError(f"q_fold must be >= 1 and divide the {M} query rows, got {q_fold}")
-    if num_splits is None:
-        num_splits = splitkv_num_splits(B, Hq, M, N)
-    _common_checks(q, k, v)
-    with torch.cuda.device(q.device):
-        q, k, v, head_dim_og = _pad_head_dim(q, k, v)
-        if sm_scale is None:
-            sm_scale = head_dim_og ** -0.5
-        kv = _prepass(k, v, tensor_layout, qk_quant_gran, True, pv == "fp8", False, kv_lens)
-        o, lse = _splitkv_attn(q, kv, tensor_layout, (qk_quant_gran, 32), sm_scale, return_lse, kv_lens, num_splits,
-                               q_fold=q_fold)
-        return _pack(o[..., :head_dim_og], lse, None, None)
+    return _splitkv_run(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran, return_lse, q_fold=q_fold)
 
 
 # ---- block-sparse attention ------------------------------------------------------------------------------------------------

@@ -94,11 +94,12 @@ static int launch_kernel(const AttnParams& p, size_t smem, hipStream_t st) {
 // block-sparse form: the kernel, or its twin with the P.V skip (sage_attn_pvskip.hip), then the rows of the empty q-blocks
 static int launch_blocksparse(const AttnCall& c, hipStream_t st) {
   if (c.sparse_kvlen) return launch_blocksparse_kvlen(c, st);  // ... with key lengths: kernels and empty rows of their own
-  const int s = c.pvskip ? launch_blocksparse_pvskip(c, st) : launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
+  const int grid = c.p.nqb * c.p.Hq * c.p.B;
+  const int s = c.pvskip ? launch_blocksparse_pvskip(c, st) : launch_4wave_kernel(c, st, grid, [](auto d, auto k, auto v, auto fp8) {
     return attn_i8_blocksparse_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
   });
   if (s) return s;
-  hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(c.p.nqb * c.p.Hq * c.p.B), dim3(256), 0, st, c.p, c.D);
+  hipLaunchKernelGGL(attn_blocksparse_empty_kernel, dim3(grid), dim3(256), 0, st, c.p, c.D);
   return launch_status();
 }
 
@@ -271,7 +272,10 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
 int attn_launch(const AttnCall& c, hipStream_t st) {
   if (c.sparse) return launch_blocksparse(c, st);
   if (c.kvlen) return launch_kvlen(c, st);
-  if (c.splitkv) return launch_splitkv(c, st);
+  if (c.splitkv) {  // the attention kernel over (b, h, q-block, split), causal or not, then the merge
+    const int s = c.splitkv_causal ? launch_splitkv_causal_attn(c, st) : launch_splitkv_attn(c, st);
+    return s ? s : launch_splitkv_merge(c, st);
+  }
   return by_dim(c.D, [&](auto d) {
     return c.nwaves == 8 ? launch_attn<decltype(d)::value, 8>(c, st) : launch_attn<decltype(d)::value, 4>(c, st);
   });

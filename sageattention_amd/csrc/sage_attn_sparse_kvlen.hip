@@ -43,11 +43,12 @@ __global__ __launch_bounds__(256) void attn_blocksparse_kvlen_empty_kernel(const
 
 // the kernel, or its twin with the P.V skip, then the rows of the emptied q-blocks
 int launch_blocksparse_kvlen(const AttnCall& c, hipStream_t st) {
-  const int s = c.pvskip ? launch_blocksparse_pvskip_kvlen(c, st) : launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
+  const int grid = c.p.nqb * c.p.Hq * c.p.B;
+  const int s = c.pvskip ? launch_blocksparse_pvskip_kvlen(c, st) : launch_4wave_kernel(c, st, grid, [](auto d, auto k, auto v, auto fp8) {
     return attn_i8_blocksparse_kvlen_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
   });
   if (s) return s;
-  hipLaunchKernelGGL(attn_blocksparse_kvlen_empty_kernel, dim3(c.p.nqb * c.p.Hq * c.p.B), dim3(256), 0, st, c.p, c.D);
+  hipLaunchKernelGGL(attn_blocksparse_kvlen_empty_kernel, dim3(grid), dim3(256), 0, st, c.p, c.D);
   return launch_status();
 }
 

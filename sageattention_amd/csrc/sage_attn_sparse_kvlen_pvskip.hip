@@ -18,7 +18,7 @@ void attn_i8_blocksparse_pvskip_kvlen_kernel(const AttnParams p) {
 }
 
 int launch_blocksparse_pvskip_kvlen(const AttnCall& c, hipStream_t st) {
-  return launch_blocksparse_kernel(c, st, [](auto d, auto k, auto v, auto fp8) {
+  return launch_4wave_kernel(c, st, c.p.nqb * c.p.Hq * c.p.B, [](auto d, auto k, auto v, auto fp8) {
     return attn_i8_blocksparse_pvskip_kvlen_kernel<decltype(d)::value, decltype(k)::value, decltype(v)::value, decltype(fp8)::value>;
   });
 }

@@ -155,7 +155,7 @@ struct AttnCall {
   bool kvlen;   // attn_i8_kvlen_kernel: the dense kernel with per-batch key lengths
   bool sparse_kvlen;  // attn_i8_blocksparse_kvlen_kernel / ..._pvskip_kvlen_kernel: sparse (and pvskip) with key lengths
   bool splitkv;  // attn_i8_splitkv_kernel + splitkv_merge_kernel (always 4 waves)
-  bool splitkv_causal;  // ... their twins attn_i8_splitkv_causal_kernel + splitkv_causal_merge_kernel
+  bool splitkv_causal;  // ... attn_i8_splitkv_causal_kernel + splitkv_merge_kernel<.., CAUSAL = true>, with splitkv
 };
 int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
@@ -167,16 +167,12 @@ int launch_kvlen(const AttnCall& c, hipStream_t st);
 // kernel -- with c.pvskip the twin of sage_attn_sparse_kvlen_pvskip.hip, second function -- and the rows of the emptied q-blocks
 int launch_blocksparse_kvlen(const AttnCall& c, hipStream_t st);
 int launch_blocksparse_pvskip_kvlen(const AttnCall& c, hipStream_t st);
-// the launches of a split-KV call (c.splitkv; sage_attn_splitkv.hip): the attention kernel over the splits, then the merge
-int launch_splitkv(const AttnCall& c, hipStream_t st);
-// ... of a causal one (c.splitkv_causal; sage_attn_splitkv_causal.hip): launch_splitkv goes through it
-int launch_splitkv_causal(const AttnCall& c, hipStream_t st);
-// the argument block of a split-KV entry point and its check + launch (sage_attn_splitkv.hip), shared with the causal entries
-AttnArgs splitkv_args(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
-                      const sage_tensor* o, int o_dtype, const float* k_scale, const void* km, const float* v_scale,
-                      const float* v_mean, float* lse, int B, int Hq, int Hk, int M, int N, int D, int qk_gran, int warpq,
-                      float sm_scale, const int32_t* kv_lens, int num_splits, void* workspace, size_t workspace_bytes);
-int run_splitkv(const AttnArgs& a, int q_dtype, sage_stream_t stream);
+// the launches of a split-KV call (c.splitkv), which attn_launch makes in this order: the attention kernel over the splits --
+// sage_attn_splitkv.hip, or with c.splitkv_causal its twin of sage_attn_splitkv_causal.hip -- then the merge of either form
+// (sage_attn_splitkv.hip)
+int launch_splitkv_attn(const AttnCall& c, hipStream_t st);
+int launch_splitkv_causal_attn(const AttnCall& c, hipStream_t st);
+int launch_splitkv_merge(const AttnCall& c, hipStream_t st);
 // bytes of the workspace of a split-KV call: the partial outputs fp32 [S,B,Hq,M,D], then their base-2 LSEs fp32 [S,B,Hq,M]
 inline int64_t splitkv_bytes(int B, int Hq, int M, int D, int S) {
   return (int64_t)S * B * Hq * M * ((int64_t)D + 1) * 4;

@@ -526,20 +526,24 @@ def _(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran):
     return q.new_empty(q.shape), _lse_like(q, tensor_layout)
 
 
+def _splitkv_compilable_args(q, tensor_layout, num_splits, sm_scale):
+    """what the two split-KV wrappers below check, and the op's forms of num_splits (0: automatic) and sm_scale"""
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if num_splits is not None and not 1 <= int(num_splits) <= core.SPLITKV_MAX:
+        raise ValueError(f"num_splits must be in [1, {core.SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
+    return int(num_splits or 0), float(q.size(-1) ** -0.5 if sm_scale is None else sm_scale)
+
+
 def sageattn_splitkv_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_lens: Optional[torch.Tensor] = None,
                                 num_splits: Optional[int] = None, tensor_layout: str = "HND",
                                 sm_scale: Optional[float] = None, pv: str = "fp16", qk_quant_gran: str = "per_thread",
                                 return_lse: bool = False):
     """``sageattn_splitkv`` (core.py) as a traceable custom op: ``kv_lens`` is an optional int32 [B] tensor argument of the op,
     ``num_splits`` an int with 0 for the automatic choice (``core.splitkv_num_splits``)."""
-    if tensor_layout not in ("HND", "NHD"):
-        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
-    if num_splits is not None and not 1 <= int(num_splits) <= core.SPLITKV_MAX:
-        raise ValueError(f"num_splits must be in [1, {core.SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
-    if sm_scale is None:
-        sm_scale = q.size(-1) ** -0.5
+    num_splits, sm_scale = _splitkv_compilable_args(q, tensor_layout, num_splits, sm_scale)
     op = torch.ops.sageattention_amd.attn_splitkv_lse if return_lse else torch.ops.sageattention_amd.attn_splitkv
-    return op(q, k, v, kv_lens, int(num_splits or 0), tensor_layout, float(sm_scale), pv, qk_quant_gran)
+    return op(q, k, v, kv_lens, num_splits, tensor_layout, sm_scale, pv, qk_quant_gran)
 
 
 @torch.library.custom_op("sageattention_amd::attn_splitkv_causal", mutates_args=())
@@ -577,15 +581,10 @@ def sageattn_splitkv_causal_compilable(q: torch.Tensor, k: torch.Tensor, v: torc
     """``sageattn_splitkv_causal`` (core.py) as a traceable custom op: ``kv_lens`` is an optional int32 [B] tensor argument of
     the op, ``num_splits`` an int with 0 for the automatic choice (``core.splitkv_num_splits``), ``q_fold`` the query rows per
     token."""
-    if tensor_layout not in ("HND", "NHD"):
-        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
-    if num_splits is not None and not 1 <= int(num_splits) <= core.SPLITKV_MAX:
-        raise ValueError(f"num_splits must be in [1, {core.SPLITKV_MAX}] (or None: from the shape), got {num_splits}")
-    if sm_scale is None:
-        sm_scale = q.size(-1) ** -0.5
+    num_splits, sm_scale = _splitkv_compilable_args(q, tensor_layout, num_splits, sm_scale)
     ns = torch.ops.sageattention_amd
     op = ns.attn_splitkv_causal_lse if return_lse else ns.attn_splitkv_causal
-    return op(q, k, v, kv_lens, int(num_splits or 0), q_fold, tensor_layout, float(sm_scale), pv, qk_quant_gran)
+    return op(q, k, v, kv_lens, num_splits, q_fold, tensor_layout, sm_scale, pv, qk_quant_gran)
 
 
 def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tensor_layout: str = "HND",

@@ -7,7 +7,7 @@ their instruction streams?
 OLD and NEW are object files (sage_attn.o ...) or directories of them (csrc/ of two builds; objects are matched by name).
 Every device function is disassembled (llvm-objdump -d, no raw bytes), addresses and branch-target labels are dropped, and the
 remaining text -- mnemonics, registers, immediates, in order; not the padding behind a function's end -- is compared.  Prints one line per object with the number of
-identical functions and names every function that differs or exists on one side only; exit status 1 if any differs.
+identical functions and names every function that differs or exists on one side only; exit status 1 if there is any such.
 
 Functions are matched by mangled name.  Where a change renames kernels, --rename REGEX=REPL (repeatable, applied in order with
 re.sub to OLD's names before matching) maps the old names to the new ones.  The predictor kernels of sage_sparge.hip lost their
@@ -22,7 +22,16 @@ the lengths of the kernel's and the parameter struct's names).  The calibration 
 against a build from before that:
 
     --rename '(16tile_mass_kernelILi\d+ELb[01]E)EEvNS_10MassParamsE$=\1Lb0EEEvNS_10MassParamsE'
-    --rename '18plan_recall_kernelENS_12RecallParamsE$=18plan_recall_kernelILb0EEEvNS_12RecallParamsE'"""
+    --rename '18plan_recall_kernelENS_12RecallParamsE$=18plan_recall_kernelILb0EEEvNS_12RecallParamsE'
+
+The split-KV merge kernels were folded the same way (splitkv_causal_merge_kernel<BF16, MAXC> became
+splitkv_merge_kernel<BF16, MAXC, true>, the other one <BF16, MAXC, false>); against a build from before that:
+
+    --rename '(20splitkv_merge_kernelILb[01]ELi\d+E)EEvNS_10AttnParamsEi$=\1Lb0EEEvNS_10AttnParamsEi'
+    --rename '27splitkv_causal_merge_kernel(ILb[01]ELi\d+E)EEvNS_10AttnParamsEi$=20splitkv_merge_kernel\1Lb1EEEvNS_10AttnParamsEi'
+
+The causal instantiations moved from sage_attn_splitkv_causal.o to sage_attn_splitkv.o with that.  Between two directories a
+function that one object lost and another gained is compared across the two and reported as "moved"."""
 import argparse
 import glob
 import os
@@ -67,8 +76,10 @@ def functions(obj):
         ins = re.sub(r"<[^>]+>", "<label>", ins)           # branch targets by name
         if ins:
             cur.append(ins)
-    for ins in out.values():  # what follows a function's last instruction up to the next symbol: alignment, objdump's "..."
-        while ins and ins[-1] in ("s_nop 0", "s_code_end", "..."):
+    # what follows a function's last instruction up to the next symbol: alignment, objdump's "...", and zero dwords, which
+    # decode as this v_cndmask (no function ends with one: its last instruction is s_endpgm or a branch)
+    for ins in out.values():
+        while ins and ins[-1] in ("s_nop 0", "s_code_end", "...", "v_cndmask_b32_e32 v0, s0, v0, vcc"):
             ins.pop()
     return out
 
@@ -87,22 +98,33 @@ def main():
     else:
         pairs = [(a.old, a.new)]
     bad = 0
+    both = []
     for old, new in pairs:
         fo, fn = functions(old), functions(new)
         for r in a.rename:
             rx, repl = r.split("=", 1)
             fo = {re.sub(rx, repl, n): ins for n, ins in fo.items()}
-        keep = [n for n in sorted(set(fo) | set(fn)) if re.search(a.filter, n)]
+        both.append((os.path.basename(old), fo, fn))
+    # a function that one object lost and another gained: {name: (object, instructions)} on either side
+    lost = {n: (obj, fo[n]) for obj, fo, fn in both for n in fo if n not in fn}
+    gained = {n: (obj, fn[n]) for obj, fo, fn in both for n in fn if n not in fo}
+    moved = sorted(n for n in set(lost) & set(gained) if re.search(a.filter, n))
+    for obj, fo, fn in both:
+        keep = [n for n in sorted(set(fo) | set(fn)) if re.search(a.filter, n) and n not in moved]
         same = [n for n in keep if n in fo and n in fn and fo[n] == fn[n]]
-        print(f"{os.path.basename(old)}: {len(same)} of {len(keep)} functions identical "
-              f"({sum(len(fo[n]) for n in same)} instructions)")
+        print(f"{obj}: {len(same)} of {len(keep)} functions identical ({sum(len(fo[n]) for n in same)} instructions)")
         for n in keep:
             if n in same:
                 continue
-            bad += n in fo and n in fn
+            bad += 1
             what = "only in OLD" if n not in fn else "only in NEW" if n not in fo else \
                 f"DIFFERS ({len(fo[n])} -> {len(fn[n])} instructions)"
             print(f"  {n}: {what}")
+    for n in moved:
+        (src, io), (dst, ino) = lost[n], gained[n]
+        bad += io != ino
+        print(f"moved {src} -> {dst}: {n}: " +
+              (f"identical ({len(io)} instructions)" if io == ino else f"DIFFERS ({len(io)} -> {len(ino)} instructions)"))
     return 1 if bad else 0
 
 

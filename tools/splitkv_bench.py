@@ -178,7 +178,7 @@ def causal_section():
             for name in variants:
                 kt = None
                 if name == "causal":
-                    kt = kernel_times(variants[name], 5, "attn_i8_splitkv_causal_kernel", "splitkv_causal_merge_kernel")
+                    kt = kernel_times(variants[name], 5, "attn_i8_splitkv_causal_kernel")
                 elif name == "non-causal" and S > 1:
                     kt = kernel_times(variants[name])
                 kts[name] = kt
