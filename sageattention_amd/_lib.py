@@ -37,173 +37,101 @@ class OpOpts(ctypes.Structure):
 _P = ctypes.POINTER(SageTensor)
 _PO = ctypes.POINTER(OpOpts)
 _PL = ctypes.POINTER(KvLayout)
+_P64 = ctypes.POINTER(c_int64)  # a host array of strides
+_I, _V = c_int, c_void_p        # _V: a device pointer, or the stream
 _lib = None
 
-# name -> (restype, argtypes); must list every symbol include/sageattn_hip.h declares
+# name -> (restype, argtypes); must list every symbol include/sageattn_hip.h declares, with its types
+# (tests/test_bindings.py compares both with the header's prototypes)
 SIGNATURES = {
-    "sage_abi_version": (c_int, []),
-    "sage_status_string": (c_char_p, [c_int]),
+    "sage_abi_version": (_I, []),
+    "sage_status_string": (c_char_p, [_I]),
     "sage_target_arch": (c_char_p, []),
-    "sage_k_mean_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "sage_k_mean": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sage_quant_qk_int8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_void_p, _P, c_void_p, c_int, c_int, c_int,
-                                   c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "sage_sub_mean_f16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_void_p, _P, c_void_p]),
-    "sage_quant_v_fp8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "sage_quant_v_fp8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f16": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                         c_float, c_int, c_void_p]),
-    "sage_attn_qk_int8_pv_f8": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_float, c_int, c_void_p]),
-    "sage_quant_qk_int8_varlen": (c_int, [_P, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, _P, c_void_p, c_int,
-                                          c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "sage_attn_qk_int8_pv_f16_varlen": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                c_float, c_int, c_void_p]),
-    "sage_attn_fusedq_pv_f16": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "sage_attn_fusedq_pv_f8": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "sage_attn_qk_int8_pv_f16_masked": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                                ctypes.POINTER(c_int64), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "sage_merge_attn_states": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
-    "sage_merge_attn_states_multi": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    "sage_finish_lse": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
-    "sage_set_tuning": (c_int, [c_int, c_int]),
-    "sage_get_tuning": (c_int, [c_int]),
-    "sage_sageattn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _PO]),
-    "sage_sageattn_pv_f16": (c_int, [_P, _P, _P, c_int, _P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                     c_float, _PO, c_void_p, c_size_t, c_void_p]),
-    "sage_sageattn_pv_f8": (c_int, [_P, _P, _P, c_int, _P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_float, c_float, _PO, c_void_p, c_size_t, c_void_p]),
-    "sage_k_smooth_quant": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                    c_void_p]),
-    "sage_kv_prepare_fp8_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "sage_kv_prepare_fp8": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, _P,
-                                    c_void_p, c_float, c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f16_kvtiles": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, _PL, c_void_p,
-                                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                 c_float, c_void_p]),
-    "sage_attn_qk_int8_pv_f8_kvtiles": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, _PL, c_void_p,
-                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                c_float, c_void_p]),
-    "sage_seq_stats_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "sage_seq_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sage_kv_stats_reduce": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int64, c_int, c_float, c_void_p,
-                                     c_void_p, c_void_p, c_void_p]),
-    "sage_quant_k_int8_kvtiles": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_void_p, _P, c_int64, c_void_p,
-                                          ctypes.POINTER(c_int64), c_int, c_int, c_void_p]),
-    "sage_quant_v_fp8_apply": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p, c_void_p]),
-    "sage_merge_attn_states_multi_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int,
-                                                c_float, c_void_p, c_float, c_void_p]),
-    "sage_block_sparse_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "sage_block_map_compact": (c_int, [c_void_p, ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_void_p, c_int64,
-                                       c_void_p]),
-    # the dense twins' arguments, then (block_lists, block_lists_bytes) in front of the stream
-    "sage_attn_qk_int8_pv_f16_blocksparse": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                     c_float, c_int, c_void_p, c_int64, c_void_p]),
-    "sage_attn_qk_int8_pv_f8_blocksparse": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                    c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                    c_float, c_int, c_void_p, c_int64, c_void_p]),
-    "sage_attn_fusedq_pv_f16_blocksparse": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                    c_float, c_void_p, c_int64, c_void_p]),
-    "sage_attn_fusedq_pv_f8_blocksparse": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                   c_float, c_void_p, c_int64, c_void_p]),
-    # the _blocksparse twins' arguments, then (pv_thresh, skipped) in front of the stream
-    "sage_attn_qk_int8_pv_f16_blocksparse_pvskip": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                            c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
-                                                            c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f8_blocksparse_pvskip": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                           c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
-                                                           c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f16_blocksparse_pvskip": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p,
-                                                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                           c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
-                                                           c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f8_blocksparse_pvskip": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                          c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
-                                                          c_void_p, c_void_p]),
-    # per-batch key lengths: the twins' arguments, then kv_lens in front of the stream
-    "sage_k_smooth_quant_kvlen": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                          c_void_p, c_void_p]),
-    "sage_kv_prepare_fp8_kvlen": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_void_p, c_void_p, c_int, c_int, _P,
-                                          c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f16_kvlen": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                               c_float, c_int, c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f8_kvlen": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                              c_float, c_int, c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f16_kvlen": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                              c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f8_kvlen": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
-                                             c_void_p, c_void_p]),
-    # block-sparse attention with per-batch key lengths: the _blocksparse_pvskip twins' arguments, then kv_lens
-    "sage_attn_qk_int8_pv_f16_blocksparse_kvlen": (c_int, [_P, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                           c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
-                                                           c_void_p, c_void_p, c_void_p]),
-    "sage_attn_qk_int8_pv_f8_blocksparse_kvlen": (c_int, [_P, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                          c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p,
-                                                          c_void_p, c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f16_blocksparse_kvlen": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p,
-                                                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                          c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
-                                                          c_void_p, c_void_p, c_void_p]),
-    "sage_attn_fusedq_pv_f8_blocksparse_kvlen": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                         c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                         c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
-                                                         c_void_p, c_void_p, c_void_p]),
-    # the predictor with per-batch key lengths: the twins' arguments, then kv_lens
-    "sage_block_pool_sim_kvlen": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p]),
-    "sage_block_select_kvlen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p,
-                                        c_void_p, c_void_p]),
-    "sage_block_pool_sim": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sage_block_select_cdf": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                      c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sage_set_tuning": (_I, [_I, _I]),
+    "sage_get_tuning": (_I, [_I]),
+    "sage_k_mean": (_I, [_P, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "sage_quant_qk_int8": (_I, [_P, _I, _I, _I, _I, _I, _V, _P, _V, _I, _I, _I, _I, c_float, _I, _V, _I, _V, _V]),
+    "sage_sub_mean_f16": (_I, [_P, _I, _I, _I, _I, _I, _V, _P, _V]),
+    "sage_quant_v_fp8": (_I, [_P, _I, _I, _I, _I, _I, _P, _V, _V, c_float, _V, _V]),
+    "sage_quant_qk_int8_varlen": (_I, [_P, _I, _V, _I, _I, _I, _I, _V, _P, _V, _I, _I, _I, _I, c_float, _I, _V]),
+    "sage_merge_attn_states": (_I, [_V, _V, _V, _I, _V, c_int64, _I, _V]),
+    "sage_merge_attn_states_multi": (_I, [_V, _V, _I, _I, _V, _V, c_int64, _I, _V]),
+    "sage_merge_attn_states_multi_ex": (_I, [_V, _V, _I, _I, _V, _V, c_int64, _I, c_float, _V, c_float, _V]),
+    "sage_finish_lse": (_I, [_V, _V, c_float, _V, c_int64, _V]),
+    "sage_sageattn_workspace_bytes": (c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I, _PO]),
+    "sage_sageattn_pv_f16": (_I, [_P, _P, _P, _I, _P, _V, _I, _I, _I, _I, _I, _I, _I, c_float, _PO, _V, c_size_t, _V]),
+    "sage_sageattn_pv_f8": (_I, [_P, _P, _P, _I, _P, _V, _I, _I, _I, _I, _I, _I, _I, c_float, c_float, _PO, _V, c_size_t,
+                                 _V]),
+    "sage_k_smooth_quant": (_I, [_P, _I, _I, _I, _I, _I, _P, _V, _V, _I, _I, _V, _V]),
+    "sage_kv_prepare_fp8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _V, _V, _I, _I, _P, _V, c_float, _V, _V]),
+    "sage_seq_stats": (_I, [_P, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "sage_kv_stats_reduce": (_I, [_V, _V, _I, c_int64, _I, _I, c_int64, _I, c_float, _V, _V, _V, _V]),
+    "sage_quant_k_int8_kvtiles": (_I, [_P, _I, _I, _I, _I, _I, _V, _P, c_int64, _V, _P64, _I, _I, _V]),
+    "sage_quant_v_fp8_apply": (_I, [_P, _I, _I, _I, _I, _I, _P, c_int64, _V, _V]),
+    "sage_block_map_compact": (_I, [_V, _P64, _I, _I, _I, _I, _V, c_int64, _V]),
+    "sage_splitkv_workspace_bytes": (c_size_t, [_I, _I, _I, _I, _I]),
+    "sage_block_pool_sim": (_I, [_P, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
+    "sage_block_select_cdf": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, c_float, _V, _V, _V, c_int64, _V, _V]),
     # ... with (rule, rule_param, keep_first, keep_last) in the place of cdfthreshd
-    "sage_block_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                  c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sage_block_select": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, c_float, _V, _I, _V, _I, _I, _V, c_int64, _V, _V]),
     # the Q / K arguments of sage_attn_qk_int8_pv_f16, then mass
-    "sage_attn_tile_mass": (c_int, [_P, _P, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_int, c_float, c_int, c_void_p, c_void_p]),
-    "sage_block_plan_recall": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p]),
-    # calibration with per-batch key lengths: the twins' arguments, then kv_lens
-    "sage_attn_tile_mass_kvlen": (c_int, [_P, _P, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
-    "sage_block_plan_recall_kvlen": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                             c_void_p, c_void_p]),
-    # split-KV attention: the fused-Q twins' arguments without is_causal, then kv_lens (or NULL), num_splits, workspace, its bytes
-    "sage_splitkv_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "sage_attn_fusedq_pv_f16_splitkv": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                                c_int, c_void_p, c_size_t, c_void_p]),
-    "sage_attn_fusedq_pv_f8_splitkv": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                               c_int, c_void_p, c_size_t, c_void_p]),
-    # ... causal, the chunk aligned to the end of the keys: the same arguments with q_fold behind num_splits
-    "sage_attn_fusedq_pv_f16_splitkv_causal": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_void_p, c_void_p, c_void_p,
-                                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                       c_float, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "sage_attn_fusedq_pv_f8_splitkv_causal": (c_int, [_P, c_int, _P, _P, _P, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                      c_float, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "sage_attn_tile_mass": (_I, [_P, _P, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _I, c_float, _I, _V, _V]),
+    "sage_block_plan_recall": (_I, [_V, c_int64, _V, _I, _I, _I, _I, _V, _V, _V]),
 }
+for _name in ("sage_k_mean", "sage_quant_v_fp8", "sage_kv_prepare_fp8", "sage_seq_stats", "sage_block_sparse"):
+    SIGNATURES[_name + "_workspace_bytes"] = (c_size_t, [_I, _I, _I, _I])
+# per-batch key lengths on the pre-pass, predictor and calibration entries: the twin's arguments, then kv_lens in front of
+# the stream
+for _name in ("sage_k_smooth_quant", "sage_kv_prepare_fp8", "sage_block_pool_sim", "sage_block_select", "sage_attn_tile_mass",
+              "sage_block_plan_recall"):
+    SIGNATURES[_name + "_kvlen"] = (_I, SIGNATURES[_name][1][:-1] + [_V, _V])
+
+# The attention entry points.  Four families: the operands up to lse, then B, Hq, Hk, M, N, D, [is_causal,] the quantization
+# arguments, whatever the form appends, and the stream.
+_OPERANDS = {
+    "qk_int8_pv_f16": [_P, _P, _P, _I, _P, _I] + [_V] * 4,       # q8 k8 v v_dtype o o_dtype | q_scale k_scale v_mean lse
+    "qk_int8_pv_f8": [_P, _P, _P, _P, _I] + [_V] * 5,            # q8 k8 v_fp8 o o_dtype | q_scale k_scale v_scale v_mean lse
+    "fusedq_pv_f16": [_P, _I, _P, _P, _I, _P, _I] + [_V] * 4,    # q q_dtype k8 v v_dtype o o_dtype | k_scale km v_mean lse
+    "fusedq_pv_f8": [_P, _I, _P, _P, _P, _I] + [_V] * 5,         # q q_dtype k8 v_fp8 o o_dtype | k_scale km v_scale v_mean lse
+}
+_QUANT = {"qk_int8": [_I, _I, _I, c_float, _I],   # qk_gran blkq warpq sm_scale logit_mult_is_one
+          "fusedq": [_I, _I, c_float]}            # qk_gran warpq sm_scale
+
+
+def _attn(family, appended=(), operands=None, is_causal=True, quant=None):
+    operands = _OPERANDS[family] if operands is None else operands
+    quant = _QUANT[family.split("_pv_")[0]] if quant is None else quant
+    return (_I, operands + [_I] * 6 + [_I] * is_causal + quant + list(appended) + [_V])
+
+
+_LISTS = [_V, c_int64]                     # block_lists, block_lists_bytes
+_PVSKIP = _LISTS + [_V, _V]                # ... pv_thresh, skipped
+_SPLITKV = [_V, _I, _V, c_size_t]          # kv_lens (or NULL), num_splits, workspace, workspace_bytes
+_FORMS = {"": [], "_blocksparse": _LISTS, "_blocksparse_pvskip": _PVSKIP, "_kvlen": [_V], "_blocksparse_kvlen": _PVSKIP + [_V]}
+for _family in _OPERANDS:
+    for _form, _appended in _FORMS.items():
+        SIGNATURES[f"sage_attn_{_family}{_form}"] = _attn(_family, _appended)
+    if _family.startswith("fusedq"):   # split-KV: no is_causal; the causal form has q_fold behind num_splits
+        SIGNATURES[f"sage_attn_{_family}_splitkv"] = _attn(_family, _SPLITKV, is_causal=False)
+        SIGNATURES[f"sage_attn_{_family}_splitkv_causal"] = _attn(_family, _SPLITKV[:2] + [_I] + _SPLITKV[2:], is_causal=False)
+    else:                              # an explicit tile layout: kv_layout in the place of v_mean, no logit_mult_is_one
+        SIGNATURES[f"sage_attn_{_family}_kvtiles"] = _attn(_family, operands=_OPERANDS[_family][:-2] + [_PL, _V],
+                                                           quant=_QUANT["qk_int8"][:-1])
+# packed sequences: cu_seqlens_q, cu_seqlens_k in the place of v_mean, lse; num_seqs and the two max_seqlen among the sizes
+SIGNATURES["sage_attn_qk_int8_pv_f16_varlen"] = _attn("qk_int8_pv_f16")
+# attn_mask, mask_kind, mask_strides in the place of v_mean; no is_causal
+SIGNATURES["sage_attn_qk_int8_pv_f16_masked"] = _attn(
+    "qk_int8_pv_f16", operands=_OPERANDS["qk_int8_pv_f16"][:-2] + [_V, _I, _P64, _V], is_causal=False)
+
+
+def bind(cdll, missing_ok=True):
+    """Set restype / argtypes on every SIGNATURES symbol ``cdll`` has and return it.  An older library loaded for an A/B run
+    may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises AttributeError."""
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    return cdll
 
 
 def lib():
@@ -215,11 +143,7 @@ def lib():
                 f"{LIB_PATH} not found: the gfx950 HIP library has not been built. Run "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `python sageattention_amd/_build.py`). "
                 "There is no CPU fallback for the SageAttention hot path.")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = l
+        _lib = l = bind(ctypes.CDLL(LIB_PATH), missing_ok=False)
         if os.environ.get("SAGE_NWAVES"):  # tuning knob (speed only): waves per attention workgroup, 4 or 8
             l.sage_set_tuning(0, int(os.environ["SAGE_NWAVES"]))
     return _lib

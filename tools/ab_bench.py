@@ -46,10 +46,7 @@ ref = None
 variants = []
 for spec in a.libs:
     path, nw = (spec.split("@") + [""])[:2]   # lib.so[@nwaves]
-    l = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(l, name):
-            fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = L.bind(ctypes.CDLL(os.path.abspath(path)))
     variants.append((spec, l, int(nw) if nw else 0))
 st = torch.cuda.current_stream().cuda_stream
 def run(l, nw):

@@ -17,10 +17,7 @@ a = ap.parse_args()
 DT = torch.float16 if a.dtype == "fp16" else torch.bfloat16
 libs = []
 for path in a.libs:
-    l = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(l, name):
-            fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = L.bind(ctypes.CDLL(os.path.abspath(path)))
     libs.append((os.path.basename(path), l))
 st = torch.cuda.current_stream().cuda_stream
 shapes = [(4, 32, 1024, 64, False), (4, 32, 2048, 64, False), (4, 32, 1024, 128, False), (4, 32, 1024, 128, True),

@@ -35,10 +35,7 @@ def call(l, o):
                                       qs.data_ptr(), ks.data_ptr(), None, None, B, H, H, N, N, D, int(causal), 3, 128, 32,
                                       D ** -0.5, 0, st)
 for path in a.libs:
-    l = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(l, name):
-            fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = L.bind(ctypes.CDLL(os.path.abspath(path)))
     o = torch.empty_like(q)
     r = call(l, o)
     torch.cuda.synchronize()

@@ -4,10 +4,7 @@ from sageattention_amd import _lib as L
 from sageattention_amd.core import _GRAN_CODE
 libs=[]
 for path in sys.argv[1:]:
-    l = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(l, name):
-            fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = L.bind(ctypes.CDLL(os.path.abspath(path)))
     libs.append(l)
 st = torch.cuda.current_stream().cuda_stream
 B,H,N,D=2,4,256,64

@@ -18,10 +18,7 @@ gran, rounding = {"thread": (L.GRAN_PER_THREAD, L.ROUND_TRITON), "block": (L.GRA
                   "warp": (L.GRAN_PER_BLOCK, L.ROUND_CUDA)}[a.gran]  # (per_warp quantizes K per block, CUDA numerics)
 libs = []
 for path in a.libs:
-    l = ctypes.CDLL(os.path.abspath(path))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(l, name):
-            fn = getattr(l, name); fn.restype, fn.argtypes = res, args
+    l = L.bind(ctypes.CDLL(os.path.abspath(path)))
     libs.append((path, l))
 st = torch.cuda.current_stream().cuda_stream
 shapes = [(4, 32, 1024, 64), (4, 32, 2048, 64), (4, 32, 1024, 128), (4, 32, 2048, 128), (4, 32, 4096, 128), (4, 32, 8192, 128),

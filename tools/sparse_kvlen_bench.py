@@ -55,11 +55,7 @@ if not torch.cuda.is_available():
 THIS = L.lib()
 PARENT = THIS
 if a.parent_lib:
-    PARENT = ctypes.CDLL(os.path.abspath(a.parent_lib))
-    for name, (res, args) in L.SIGNATURES.items():
-        if hasattr(PARENT, name):  # the parent has no *_blocksparse_kvlen / predictor *_kvlen symbols
-            fn = getattr(PARENT, name)
-            fn.restype, fn.argtypes = res, args
+    PARENT = L.bind(ctypes.CDLL(os.path.abspath(a.parent_lib)))
 
 
 def on_parent(fn):
