@@ -6,7 +6,10 @@ leaves it); tests/test_constructed_logits_gpu.py holds the kernels that see ever
 tests/test_constructed_subsets_gpu.py those that see a subset (block maps, key lengths, split-KV: ``subcase``, the anchored
 forms for the fused-Q entry points, ``merged_bound``, ``restate_split64`` further down), and
 tests/test_constructed_masks_gpu.py the attn_mask kernel under structured masks (a case may carry ``c["mask"]``: ``with_mask``,
-``mask_pattern``, ``restate_mask64`` and ``public_form`` at the end).
+``mask_pattern``, ``restate_mask64`` and ``public_form``), and tests/test_constructed_layouts_gpu.py the batch, head, sequence and
+tile ADDRESSING: several different cases in one call, each slice held to its own case (``stack`` / ``stack_slots``, ``pack`` /
+``pack_cases``, ``tile_major``, causal ``cut_case`` with M != N, their ``read_*`` / ``restate_*`` restatements and ``LAYOUT_MISTAKES``
+at the end).
 
 Every case is a dict (``case(family, variant, D, N, causal, gran)``):
   q8 [1,2,M,D] / k8 [1,1,N,D] int8; q_scale [1,2,Gq] / k_scale [1,1,Gk] fp32 in the compact layout of the granularity
@@ -1063,16 +1066,29 @@ def with_mask(c, mask, name=None):
     return d
 
 
-def cut_case(c, M, N):
-    """the case cut to its first M rows and N keys, compact scales included (both layouts are prefix-compatible)"""
-    assert not c["causal"] and M <= c["M"] and N <= c["N"]
-    d = subcase(c, length=N)
+def cut_case(c, M, N, causal=None):
+    """the case cut to its first M rows and N keys, compact scales included (both layouts are prefix-compatible).
+    ``causal`` (default: as the parent): the copy is marked causal or not whatever the parent was -- the operands of a family do
+    not depend on the flag, and ``allowed`` is the TOP-LEFT mask n <= m for any (M, N), under which every row keeps key 0.  A
+    causal cut with more than 150 rows is taken from a causal parent (M = N).  N = 0: the keyless sequence of ``pack``, a case
+    with queries only; it has no reference."""
+    causal = c["causal"] if causal is None else bool(causal)
+    assert 0 < M <= c["M"] and 0 <= N <= c["N"] and c.get("mask") is None
+    if N > 0:
+        d = subcase(c, length=N)
+    else:
+        d = {k: v for k, v in c.items() if k not in ("k_scale", "_cache")}
+        d["_cache"] = {}
+        for key in ("k8", "v_f16", "v_bf16"):
+            d[key] = c[key][:, :, :0].contiguous()
+        d["k_scale_cols"], d["v_f8t"], d["N"] = c["k_scale_cols"][..., :0].contiguous(), c["v_f8t"][..., :0].contiguous(), 0
     _, gq = _gid_q(M, c["gran"])
-    _, gk = _gid_k(N, c["gran"])
+    gk = _gid_k(N, c["gran"])[1] if N else 0
     d.update(q8=c["q8"][:, :, :M].contiguous(), q_scale=c["q_scale"][..., :gq].contiguous(),
-             q_scale_rows=c["q_scale_rows"][..., :M].contiguous(), k_scale=c["k_scale"][..., :gk].contiguous(), M=M)
+             q_scale_rows=c["q_scale_rows"][..., :M].contiguous(), k_scale=c["k_scale"][..., :gk].contiguous(), M=M,
+             causal=causal)
     assert torch.equal(O.expand_q_scale(d["q_scale"], M, c["gran"]), d["q_scale_rows"])
-    assert torch.equal(O.expand_k_scale(d["k_scale"], N, c["gran"]), d["k_scale_cols"])
+    assert N == 0 or torch.equal(O.expand_k_scale(d["k_scale"], N, c["gran"]), d["k_scale_cols"])
     return d
 
 
@@ -1296,3 +1312,343 @@ def public_cases(D, backend):
     yield "ladder", public_form(scale_ladder(D, SUBSET_N, False, gran), backend)
     yield "hot200", public_form(one_hot(D, SUBSET_N, False, gran, 200), backend)
     yield "zero", public_form(extreme_s(D, SUBSET_N, False, gran, "zero"), backend)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# layouts: several cases in ONE call -- stacked over batches and KV heads, packed sequences, tile-major K / V (the CPU
+# soundness test and tests/test_constructed_layouts_gpu.py).  Reference and bound stay those of each case: a slice of the
+# call's result is held to the case that was put there.
+# ---------------------------------------------------------------------------------------------------------------------
+
+STACK_SHIFTS = ((0, 1), (2, 3))  # slot (b, hk): the power of two moved from its K scales into its Q scales
+
+
+def rebalance(c, e):
+    """The case with 2^e (e >= 0) moved from k_scale into q_scale: every product, hence every logit, reference and bound, is what
+    it was (the copy shares the cache), while the scale TENSORS differ from the original's by a power of two -- so the slots of
+    a stack carry K- and Q-scale ladders no two of which are equal, uniform families included."""
+    assert e >= 0
+    d, f = dict(c), 2.0 ** e
+    for key, g in (("q_scale", f), ("q_scale_rows", f), ("k_scale", 1 / f), ("k_scale_cols", 1 / f)):
+        d[key] = c[key] * g
+    assert torch.equal(scale_matrix(d), scale_matrix(c))
+    return d
+
+
+def distinct_heads(c):
+    """A rank-one family (ramp, one_hot) builds both query heads from one q8; the copy negates head 1 (the anchor channel of an
+    anchored case apart), so that every row trend / the hot key's lead changes sign there and the two heads of the slot have
+    different results: reading the other head's rows, scales or workspace slots then shows in every slot of a stack.  Another
+    set of operands, hence a fresh cache; reference and bound come from the operands as always."""
+    assert c["family"] in ("ramp", "one_hot") and int(c["q8"].abs().max()) <= 127 and torch.equal(c["q8"][:, 0], c["q8"][:, 1])
+    d = dict(c)
+    d["_cache"] = {}
+    q8, Dd = c["q8"].clone(), c["D"] - (1 if c.get("anchored") else 0)
+    q8[:, 1, :, :Dd] = -q8[:, 1, :, :Dd]
+    d["q8"] = q8
+    return d
+
+
+def stack(cases):
+    """One call's operands from a Bs x Hks grid of cases with equal (M, N, D, gran, causal): q8 [Bs, 2 Hks, M, D] (slot (b, hk)
+    holds the query heads 2 hk, 2 hk + 1: GQA group 2), k8 [Bs, Hks, N, D], the compact scales [Bs, 2 Hks, Gq] / [Bs, Hks, Gk]
+    and their expansions, the three V forms and v_scale [Bs, Hks, D].  ``grid`` keeps the cases: slice (b, hk) of a result is
+    held to reference and bound of grid[b][hk], whose caches stay shared."""
+    Bs, Hks = len(cases), len(cases[0])
+    first = cases[0][0]
+    same = ("M", "N", "D", "gran", "causal", "logit_mult", "sm_scale")
+    assert all(len(row) == Hks and all(c[k] == first[k] for k in same) and c.get("mask") is None for row in cases for c in row)
+    st = {k: first[k] for k in same}
+    for key in ("q8", "k8", "q_scale", "k_scale", "q_scale_rows", "k_scale_cols", "v_f16", "v_bf16", "v_f8t", "v_scale"):
+        st[key] = torch.cat([torch.cat([c[key] for c in row], dim=1) for row in cases], dim=0).contiguous()
+    st.update(grid=[list(row) for row in cases], Bs=Bs, Hks=Hks, Hq=HQ * Hks, Hk=HK * Hks,
+              anchored=all(c.get("anchored", False) for row in cases for c in row))
+    return st
+
+
+def stack_slots(D, N, causal, gran, anchored=False):
+    """The standard 2 x 2 grid: (0, 0) scale_ladder, (0, 1) ramp ascending (step 40), (1, 0) one_hot with the LAST key hot,
+    (1, 1) ramp descending (step 40), slot (b, hk) rebalanced by 2^STACK_SHIFTS[b][hk] -- the K scales of any two slots differ
+    in at least three groups of four (asserted), by a power of two, and the two query heads of every slot differ
+    (``distinct_heads``).  ``anchored``: the
+    anchored forms, for the entry points that quantize Q themselves."""
+    if anchored:
+        raw = [[anchor(scale_ladder(D, N, causal, gran)), ramp(D, N, causal, gran, "40", "ascending", anchor=True)],
+               [anchor(one_hot(D, N, causal, gran, "last")), ramp(D, N, causal, gran, "40", "descending", anchor=True)]]
+    else:
+        raw = [[scale_ladder(D, N, causal, gran), ramp(D, N, causal, gran, "40", "ascending")],
+               [one_hot(D, N, causal, gran, "last"), ramp(D, N, causal, gran, "40", "descending")]]
+    raw = [[c if c["family"] == "scale_ladder" else distinct_heads(c) for c in row] for row in raw]
+    st = stack([[rebalance(c, STACK_SHIFTS[b][hk]) for hk, c in enumerate(row)] for b, row in enumerate(raw)])
+    ks = st["k_scale"].reshape(4, -1)
+    assert all(float((ks[i] != ks[j]).float().mean()) >= 0.75 for i in range(4) for j in range(i))  # (a ladder meets a uniform
+    return st                                                                                         #  scale in 1 group of 7)
+
+
+def stack_of(c):
+    """a single case as a 1 x 1 stack"""
+    return stack([[c]])
+
+
+def slot_heads(hk):
+    return slice(HQ * hk, HQ * hk + HQ)
+
+
+def read_stack(st, b, hk, mistake=None):
+    """Slot (b, hk) of a stacked call AS A KERNEL READS IT, again a case: query heads 2 hk, 2 hk + 1 of batch b, K / V / v_scale
+    of (b, hk), the K scales of (b, hk).  Without a mistake these are the operands of grid[b][hk] bit for bit.
+      head_scales_of_kv_head_0    the K scales of (b, 0)
+      batch_operands_of_batch_0   K, V and v_scale of (0, hk); the scales (and any length) stay those of b"""
+    own = st["grid"][b][hk]
+    kb = 0 if mistake == "batch_operands_of_batch_0" else b
+    sh = 0 if mistake == "head_scales_of_kv_head_0" else hk
+    d = dict(own)
+    d["_cache"] = {}
+    for key in ("q8", "q_scale", "q_scale_rows"):
+        d[key] = st[key][b:b + 1, slot_heads(hk)]
+    for key in ("k8", "v_f16", "v_bf16", "v_f8t", "v_scale"):
+        d[key] = st[key][kb:kb + 1, hk:hk + 1]
+    for key in ("k_scale", "k_scale_cols"):
+        d[key] = st[key][b:b + 1, sh:sh + 1]
+    return d
+
+
+def stack_ratios(st, pv, o, lse2, sub=None):
+    """largest ``ratios`` over the slots of a stacked result o [Bs,Hq,M,D] / lse2 [Bs,Hq,M]; ``sub(case, b, hk)`` names the case
+    a slot is held to (default: the slot's own)"""
+    worst = (0.0, 0.0)
+    for b in range(st["Bs"]):
+        for hk in range(st["Hks"]):
+            c = st["grid"][b][hk] if sub is None else sub(st["grid"][b][hk], b, hk)
+            r = ratios(c, pv, o[b:b + 1, slot_heads(hk)], lse2[b:b + 1, slot_heads(hk)])
+            worst = (max(worst[0], r[0]), max(worst[1], r[1]))
+    return worst
+
+
+def interleaved_batch(st, b, h, mistake=None):
+    """The batch whose key length the workgroup of (b, h) reads.  The kvlen / split-KV kernels number their workgroups with the
+    batches alternating inside a head, id = h * B + b, and decode b = id % B.  ``interleave_b_h_swapped``: the length is taken
+    with the id decoded batch-major, b' = id // Hq, while every operand address keeps (b, h)."""
+    return (h * st["Bs"] + b) // st["Hq"] if mistake == "interleave_b_h_swapped" else b
+
+
+def restate_stack64(st, pv, b, hk, mistake=None, lens=None):
+    """restate64 (float64, no rounding) of slot (b, hk) of a stacked call, dense (``lens`` None) or with per-batch key lengths
+    -> (o [1,2,M,D], lse2 [1,2,M]).  ``mistake``: one of read_stack's, or interleave_b_h_swapped."""
+    d = read_stack(st, b, hk, mistake)
+    if lens is None:
+        return restate64(d, pv)
+    parts = []
+    for hl in range(HQ):
+        n = lens[interleaved_batch(st, b, HQ * hk + hl, mistake)]
+        o, l = restate64(subcase(d, length=n), pv)
+        parts.append((o[:, hl:hl + 1], l[:, hl:hl + 1]))
+    return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
+
+
+def stack_km(st):
+    """km [Bs,Hks,D] for the split-KV calls on a stack: split_km rolled by the slot number, so no two slots share it"""
+    km = split_km(st["D"], True)
+    return torch.cat([torch.cat([km.roll(2 * b + hk + 1, -1) for hk in range(st["Hks"])], dim=1) for b in range(st["Bs"])], dim=0)
+
+
+def restate_stack_split64(st, pv, S, b, hk, length, qkm, mistake=None):
+    """restate_split64 of slot (b, hk) of a stacked split-KV call -> (o, lse2, finished lse).  ``workspace_slot_of_head_0``: the
+    merge of every head reads the partials in the workspace slots of head 0 of its batch (the finish keeps the row's own
+    correction ``qkm``)."""
+    if mistake != "workspace_slot_of_head_0":
+        return restate_split64(read_stack(st, b, hk, mistake), pv, S, length, None, qkm)
+    o, l2 = restate_split64(read_stack(st, b, 0), pv, S, length)
+    o, l2 = o[:, :1].expand(-1, HQ, -1, -1), l2[:, :1].expand(-1, HQ, -1)
+    return o, l2, l2 / math.log2(math.e) + qkm
+
+
+# ---- packed sequences ----------------------------------------------------------------------------------------------------
+
+PACK_CUTS = ((150, 456), (64, 65), (1, 1), (129, 320), (33, 0))  # (M_s, N_s); the last sequence has no key
+PACK_CUTS_CAUSAL = ((150, 456), (65, 65), (200, 130))           # M_s < N_s, =, >
+
+
+def pack(rows):
+    """Packed-sequence operands (include/sageattn_hip.h, packed variable-length sequences).  ``rows[s]`` is the list of the Hks
+    cut cases (one per KV head, or a single case) of sequence s, all of equal (M_s, N_s); every case of the pack has the same
+    (D, gran, causal).  -> q8 [sum M_s, 2 Hks, D], k8 / v_f16 / v_bf16 [sum N_s, Hks, D], cu_q / cu_k int32 [S + 1], and the
+    scales in the private layout q_scale [S, 2 Hks, Gq(max M_s)] / k_scale [S, Hks, Gk(max N_s)]: sequence s fills the first
+    Gq(M_s) / Gk(N_s) slots of its rows, every other slot is NaN.  ``cases`` keeps the rows: heads 2 hk, 2 hk + 1 of sequence s
+    are held to cases[s][hk]."""
+    rows = [list(r) if isinstance(r, (list, tuple)) else [r] for r in rows]
+    first, Hks = rows[0][0], len(rows[0])
+    same = ("D", "gran", "causal", "logit_mult", "sm_scale")
+    assert all(len(r) == Hks and all(c[k] == first[k] for k in same) and (c["M"], c["N"]) == (r[0]["M"], r[0]["N"])
+               for r in rows for c in r)
+    Ms, Ns = [r[0]["M"] for r in rows], [r[0]["N"] for r in rows]
+    gran = first["gran"]
+    gq, gk = _gid_q(max(Ms), gran)[1], _gid_k(max(Ns), gran)[1]
+    pk = {k: first[k] for k in same}
+    pk["q_scale"] = torch.full((len(rows), HQ * Hks, gq), float("nan"))
+    pk["k_scale"] = torch.full((len(rows), HK * Hks, gk), float("nan"))
+    for s, r in enumerate(rows):
+        for hk, c in enumerate(r):
+            pk["q_scale"][s, slot_heads(hk), :c["q_scale"].shape[-1]] = c["q_scale"][0]
+            pk["k_scale"][s, hk, :c["k_scale"].shape[-1]] = c["k_scale"][0, 0]
+    for key in ("q8", "k8", "v_f16", "v_bf16"):
+        pk[key] = torch.cat([torch.cat([c[key][0] for c in r], dim=0).transpose(0, 1) for r in rows], dim=0).contiguous()
+    cu = lambda lens: torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32)
+    pk.update(cases=rows, S=len(rows), Hks=Hks, Hq=HQ * Hks, Hk=HK * Hks, Ms=Ms, Ns=Ns, cu_q=cu(Ms), cu_k=cu(Ns), max_q=max(Ms),
+              max_k=max(Ns), gq=gq, gk=gk)
+    return pk
+
+
+def pack_cases(D, gran, causal):
+    """The sequences of the packed call, two KV heads (four query heads); KV head 1 holds the families of KV head 0 rotated by
+    one sequence.  Non-causal, PACK_CUTS, KV head 0: scale_ladder (150, 456), ramp ascending (64, 65), one_hot with its hot
+    key first (1, 1), ramp descending (129, 320), scale_ladder (33, 0).  Causal, PACK_CUTS_CAUSAL, cut from causal parents
+    (M = N = 456): scale_ladder (150, 456), one_hot hot key 40 (65, 65), ramp sawtooth (200, 130).  The rank-one families with
+    ``distinct_heads``; the case at (s, hk) rebalanced by 2^(s + 5 hk): no two alike."""
+    if causal:
+        par = [scale_ladder(D, 456, True, gran), one_hot(D, 456, True, gran, 40), ramp(D, 456, True, gran, "40", "sawtooth")]
+        cuts = PACK_CUTS_CAUSAL
+    else:
+        par = [scale_ladder(D, 456, False, gran), ramp(D, 456, False, gran, "40", "ascending"),
+               one_hot(D, 456, False, gran, "first"), ramp(D, 456, False, gran, "40", "descending"),
+               scale_ladder(D, 456, False, gran)]
+        cuts = PACK_CUTS
+    par = [c if c["family"] == "scale_ladder" else distinct_heads(c) for c in par]
+    n = len(par)
+    return pack([[cut_case(rebalance(par[(s + hk) % n], s + 5 * hk), m, k, causal) for hk in range(2)]
+                 for s, (m, k) in enumerate(cuts)])
+
+
+def read_pack(pk, s, hk=0, mistake=None):
+    """Heads 2 hk, 2 hk + 1 of sequence s of a packed call AS A KERNEL READS THEM, again a case: rows [cu_q[s], cu_q[s + 1]) of
+    q8, rows [cu_k[s], cu_k[s + 1]) of k8 / v, the scale rows (s, h) of [S, H, G(max)] of which the first G(M_s) / G(N_s) slots
+    count.
+      cu_off_by_one_row             the K and V rows start at cu_k[s] + 1
+      scales_of_previous_sequence   the K scale rows of sequence s - 1 (sequence 0: its own; the Q scales stay the sequence's:
+                                    moved TOGETHER, the scales of two uniform families keep their product)
+      scale_row_by_max_seqlen_of_q  the K scale row of (s, hk) at (s * Hk + hk) * Gq(max M_s) of the flat tensor"""
+    own = pk["cases"][s][hk]
+    M, N, gran = own["M"], own["N"], own["gran"]
+    assert N > 0, "a sequence without keys has no softmax"
+    q_lo, k_lo = int(pk["cu_q"][s]), int(pk["cu_k"][s]) + (1 if mistake == "cu_off_by_one_row" else 0)
+    assert M == int(pk["cu_q"][s + 1]) - q_lo and N == int(pk["cu_k"][s + 1]) - int(pk["cu_k"][s])
+    rows = (k_lo + torch.arange(N)).clamp(max=pk["k8"].shape[0] - 1)
+    ss = max(s - 1, 0) if mistake == "scales_of_previous_sequence" else s
+    gq_s, gk_s = _gid_q(M, gran)[1], _gid_k(N, gran)[1]
+    d = dict(own)
+    d["_cache"] = {}
+    d["q8"] = pk["q8"][q_lo:q_lo + M, slot_heads(hk)].transpose(0, 1).unsqueeze(0)
+    for key in ("k8", "v_f16", "v_bf16"):
+        d[key] = pk[key][rows, hk:hk + 1].transpose(0, 1).unsqueeze(0)
+    d["q_scale"] = pk["q_scale"][s:s + 1, slot_heads(hk), :gq_s]
+    flat = pk["k_scale"].reshape(-1)
+    row = pk["gq"] if mistake == "scale_row_by_max_seqlen_of_q" else pk["gk"]
+    d["k_scale"] = flat[((ss * pk["Hk"] + hk) * row + torch.arange(gk_s)) % flat.numel()].view(1, 1, gk_s)
+    d["q_scale_rows"], d["k_scale_cols"] = O.expand_q_scale(d["q_scale"], M, gran), O.expand_k_scale(d["k_scale"], N, gran)
+    return d
+
+
+def restate_pack64(pk, pv, s, hk=0, mistake=None):
+    """restate64 of heads 2 hk, 2 hk + 1 of sequence s of a packed call; ``causal_bottom_right``: row m keeps the keys n <= m + (N_s - M_s) where the
+    entry point's mask is top-left, n <= m (a row left without a key is NaN)"""
+    d = read_pack(pk, s, hk, None if mistake == "causal_bottom_right" else mistake)
+    return restate_causal64(d, pv, mistake) if mistake == "causal_bottom_right" else restate64(d, pv)
+
+
+def restate_causal64(c, pv, mistake=None):
+    """restate64 of a causal case of any (M, N); ``causal_bottom_right`` aligns the diagonal to the LAST key"""
+    assert c["causal"]
+    M, N = c["M"], c["N"]
+    off = N - M if mistake == "causal_bottom_right" else 0
+    ok = torch.arange(N).view(1, 1, 1, N) <= torch.arange(M).view(1, 1, M, 1) + off
+    t = (scores(c) * scale_matrix(c)).masked_fill(~ok, float("-inf"))
+    return _lazy_loop64(t, v64(c, pv), pv)
+
+
+CAUSAL_CUTS = ((150, 456), (456, 150), (130, 129))  # top-left causal with M != N through the dense and kvlen kernels
+
+
+def causal_cut_cases(D, gran):
+    """(label, case) of CAUSAL_CUTS: scale_ladder at every shape, the sawtooth ramp (step 40) at (456, 150), all cut from
+    causal parents"""
+    lad, saw = scale_ladder(D, 456, True, gran), ramp(D, 456, True, gran, "40", "sawtooth")
+    for m, n in CAUSAL_CUTS:
+        yield f"ladder-{m}x{n}", cut_case(lad, m, n, True)
+    yield "sawtooth-456x150", cut_case(saw, 456, 150, True)
+
+
+# ---- tile-major K / V ----------------------------------------------------------------------------------------------------
+
+TILE_GAP_ROWS = 8     # poisoned rows behind the 64 rows of every K / V tile
+TILE_GAP_COLS = 16    # poisoned bytes behind the 64 tokens of every channel row of an e4m3 V^T tile
+TILE_SCALE_SLOT = 8   # floats per (tile, b, hk) in the K-scale buffer: 4 | 1 scales, the rest NaN
+
+
+def tile_major(c_or_stack):
+    """K, V and the K scales of a case or a stack in the TILE-MAJOR layout of the sequence-parallel exchange buffers
+    (include/sageattn_hip.h): k8 [T][B][Hk][64 + 8][D] int8, v_f16 / v_bf16 the same shape, v_f8t [T][B][Hk][D][64 + 16] e4m3
+    (tokens in natural order), k_scale [T][B][Hk][8] -- the first 64 rows / 64 bytes / 4 | 1 floats of every block are the
+    tile, the rest is poison (int8 127, NaN, 0x7F, NaN), and so are the K and fp16 / bf16 V rows behind key N - 1 in the ragged
+    last tile.  (The e4m3 V^T keeps its ZEROS in [N, 64 T): the contract of the dense operand, whose last block the kernel
+    reads whole.)  Tile strides are therefore larger than B * Hk tiles, and the K-scale strides are all non-zero.
+    ``kt`` / ``vt`` / ``v8t`` / ``kst``: (stride_b, stride_h, stride_n | None, tile stride) in elements; ``layout(pv)``: the
+    five sage_kv_layout values."""
+    st = c_or_stack if "grid" in c_or_stack else stack_of(c_or_stack)
+    Bs, Hk, N, D = st["Bs"], st["Hk"], st["N"], st["D"]
+    T, R, W, SL = O.cdiv(N, 64), 64 + TILE_GAP_ROWS, 64 + TILE_GAP_COLS, TILE_SCALE_SLOT
+    pt = 4 if st["gran"] == "per_thread" else 1
+    tm = dict(st=st, T=T, per_tile=pt)
+    tm["k8"] = torch.full((T, Bs, Hk, R, D), 127, dtype=torch.int8)
+    tm["v_f16"] = torch.full((T, Bs, Hk, R, D), float("nan"), dtype=torch.float16)
+    tm["v_bf16"] = torch.full((T, Bs, Hk, R, D), float("nan"), dtype=torch.bfloat16)
+    v8 = torch.full((T, Bs, Hk, D, W), 0x7F, dtype=torch.uint8)
+    tm["k_scale"] = torch.full((T, Bs, Hk, SL), float("nan"))
+    for j in range(T):
+        n = min(64, N - 64 * j)
+        for key in ("k8", "v_f16", "v_bf16"):
+            tm[key][j, :, :, :n] = st[key][:, :, 64 * j:64 * j + n]
+        v8[j, :, :, :, :64] = st["v_f8t"].view(torch.uint8)[..., 64 * j:64 * j + 64]
+        tm["k_scale"][j, :, :, :pt] = st["k_scale"][:, :, pt * j:pt * j + pt]
+    tm["v_f8t"] = v8.view(torch.float8_e4m3fn)
+    tm["kt"] = tm["vt"] = (Hk * R * D, R * D, D, Bs * Hk * R * D)
+    tm["v8t"] = (Hk * D * W, D * W, W, Bs * Hk * D * W)
+    tm["kst"] = (Hk * SL, SL, None, Bs * Hk * SL)
+    tm["layout"] = lambda pv: (tm["kt"][3], tm["v8t"][3] if pv == "fp8" else tm["vt"][3], tm["kst"][0], tm["kst"][1], tm["kst"][3])
+    return tm
+
+
+def read_tiles(tm, b, hk, mistake=None):
+    """Slot (b, hk) of a tile-major call AS A KERNEL READS IT, again a case: key r of (b, hk) is row r % 64 of tile r // 64, its
+    scales the first 4 | 1 floats of that tile's slot.  K and the K scales are gathered from the FLAT buffers by their
+    strides, V from its blocks.
+      tile_stride_dense        tile j of K at 64 * stride_n * j behind tile 0 of (b, hk): the gap rows, then foreign tiles
+      tile_scales_dense_layout the K scales at (b * Hk + hk) * T * (4 | 1) + (4 | 1) * j, the dense [B,Hk,Gk] strides"""
+    st, T, pt = tm["st"], tm["T"], tm["per_tile"]
+    own = st["grid"][b][hk]
+    N, D, gran = st["N"], st["D"], st["gran"]
+    r = torch.arange(N)
+    sb, sh, sn, stile = tm["kt"]
+    tile_of = 64 * sn if mistake == "tile_stride_dense" else stile
+    flat_k = tm["k8"].reshape(-1, D)
+    krow = ((b * sb + hk * sh + (r // 64) * tile_of + (r % 64) * sn) // D) % flat_k.shape[0]
+    ksb, ksh, _, kst = tm["kst"]
+    g = torch.arange(T * pt)
+    if mistake == "tile_scales_dense_layout":
+        kidx = (b * st["Hk"] + hk) * T * pt + g
+    else:
+        kidx = b * ksb + hk * ksh + (g // pt) * kst + g % pt
+    d = dict(own)
+    d["_cache"] = {}
+    d["k8"] = flat_k[krow].view(1, 1, N, D)
+    d["k_scale"] = tm["k_scale"].reshape(-1)[kidx % tm["k_scale"].numel()].view(1, 1, -1)
+    d["k_scale_cols"] = O.expand_k_scale(d["k_scale"], N, gran)
+    for key in ("v_f16", "v_bf16"):
+        d[key] = tm[key][:, b, hk, :64].reshape(1, 1, T * 64, D)[:, :, :N]
+    d["v_f8t"] = tm["v_f8t"].view(torch.uint8)[:, b, hk, :, :64].permute(1, 0, 2).reshape(1, 1, D, T * 64).view(torch.float8_e4m3fn)
+    return d
+
+
+LAYOUT_MISTAKES = ("head_scales_of_kv_head_0", "batch_operands_of_batch_0", "interleave_b_h_swapped", "workspace_slot_of_head_0",
+                   "cu_off_by_one_row", "scales_of_previous_sequence", "scale_row_by_max_seqlen_of_q", "causal_bottom_right",
+                   "tile_scales_dense_layout", "tile_stride_dense")
+STACK_KV_LENS = ((257, 456), (456, 64))

@@ -580,3 +580,148 @@ def test_public_forms_come_back_from_the_quantizers(backend, D):
                 m = C.with_mask(d, mask)
                 ro, rl = C.mask_ratios(m, pv, *C.oracle(m, pv))
                 assert ro <= 1.0 and rl <= 1.0, (label, name, pv, ro, rl)
+
+
+# ---- layouts: stacked, packed and tile-major calls (tests/test_constructed_layouts_gpu.py) ----------------------------------
+
+LAYOUT_SHAPES = ((64, "per_thread"), (128, "per_warp"), (64, "per_block"))  # (head_dim, granularity) of the CPU proofs
+_SAME = ("q8", "k8", "q_scale", "k_scale", "q_scale_rows", "k_scale_cols", "v_f16", "v_bf16")
+
+
+def _bytes(t):
+    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
+
+
+@pytest.mark.parametrize("gran", C.GRANS)
+def test_layout_builders_hold_each_case_where_a_kernel_reads_it(gran):
+    """read_stack / read_pack / read_tiles without a mistake return the operands of the slot's own case bit for bit, so a slice
+    of a call's result IS that case's result; the poison of the tile-major buffers and the NaN scale slots of a pack are where
+    the docstrings say"""
+    for causal in (False, True):
+        st = C.stack_slots(64, 456, causal, gran)
+        assert tuple(st["q8"].shape) == (2, 4, st["M"], 64) and tuple(st["k8"].shape) == (2, 2, 456, 64)
+        assert tuple(st["v_scale"].shape) == (2, 2, 64) and st["q_scale"].shape[:2] == (2, 4) and st["k_scale"].shape[:2] == (2, 2)
+        tm = C.tile_major(st)
+        for b in range(2):
+            for hk in range(2):
+                own = st["grid"][b][hk]
+                for d in (C.read_stack(st, b, hk), C.read_tiles(tm, b, hk)):
+                    assert all(torch.equal(_bytes(d[k]), _bytes(own[k])) for k in _SAME + ("v_f8t", "v_scale")), (b, hk)
+        kt, T = tm["layout"]("fp16")[0], tm["T"]
+        assert kt > 2 * 2 * 64 * 64 and all(x > 0 for x in tm["layout"]("fp8")) and all(x % 4 == 0 for x in tm["layout"]("fp8")[2:])
+        assert bool((tm["k8"][:, :, :, 64:] == 127).all()) and bool((tm["k8"][T - 1, :, :, 8:] == 127).all())  # 456 = 7 * 64 + 8
+        assert bool(torch.isnan(tm["v_f16"][:, :, :, 64:]).all()) and bool(torch.isnan(tm["v_bf16"][T - 1, :, :, 8:]).all())
+        assert bool((tm["v_f8t"].view(torch.uint8)[..., 64:] == 0x7F).all()) and bool(torch.isnan(tm["k_scale"][..., tm["per_tile"]:]).all())
+        pk = C.pack_cases(64, gran, causal)
+        assert pk["Ms"] == [m for m, _ in (C.PACK_CUTS_CAUSAL if causal else C.PACK_CUTS)]
+        assert pk["Ns"] == [n for _, n in (C.PACK_CUTS_CAUSAL if causal else C.PACK_CUTS)]
+        assert tuple(pk["q8"].shape) == (sum(pk["Ms"]), 4, 64) and tuple(pk["k8"].shape) == (sum(pk["Ns"]), 2, 64)
+        assert tuple(pk["q_scale"].shape) == (pk["S"], 4, pk["gq"]) and tuple(pk["k_scale"].shape) == (pk["S"], 2, pk["gk"])
+        used = 0
+        for s, row in enumerate(pk["cases"]):
+            for hk, own in enumerate(row):
+                used += own["q_scale"].numel() + own["k_scale"].numel()
+                if own["N"]:
+                    d = C.read_pack(pk, s, hk)
+                    assert all(torch.equal(d[k], own[k]) for k in _SAME), (s, hk)
+        finite = int(torch.isfinite(pk["q_scale"]).sum() + torch.isfinite(pk["k_scale"]).sum())
+        assert finite == used and pk["q_scale"].numel() + pk["k_scale"].numel() > used
+
+
+@pytest.mark.parametrize("D,gran", LAYOUT_SHAPES)
+def test_layout_slices_are_sound(D, gran):
+    """the oracle's restatement of the kernel on every slice of the stacked calls (dense and causal), on every sequence of the
+    packed calls and on the causal (M, N) cuts stays within ``bound`` of the slice's own case, every element"""
+    worst = {}
+    for causal in (False, True):
+        st = C.stack_slots(D, 456, causal, gran)
+        for pv in C.PVS:
+            for b in range(2):
+                for hk in range(2):
+                    r = C.ratios(st["grid"][b][hk], pv, *C.oracle(C.read_stack(st, b, hk), pv))
+                    worst["stack"] = max(worst.get("stack", 0.0), *r)
+                    assert max(r) <= 1.0, ("stack", causal, pv, b, hk, r)
+        pk = C.pack_cases(D, gran, causal)
+        for pv in ("fp16", "bf16"):
+            for s, row in enumerate(pk["cases"]):
+                for hk, own in enumerate(row):
+                    if own["N"]:
+                        r = C.ratios(own, pv, *C.oracle(C.read_pack(pk, s, hk), pv))
+                        worst["pack"] = max(worst.get("pack", 0.0), *r)
+                        assert max(r) <= 1.0, ("pack", causal, pv, s, hk, r)
+    for label, c in C.causal_cut_cases(D, gran):
+        for pv in C.PVS:
+            r = C.ratios(c, pv, *C.oracle(c, pv))
+            worst["cut"] = max(worst.get("cut", 0.0), *r)
+            assert max(r) <= 1.0, (label, pv, r)
+            assert max(C.ratios(c, pv, *C.restate_causal64(c, pv))) < 1e-3  # top-left IS the reference at M != N
+    print(f"layout soundness D={D} {gran}: largest oracle ratio " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(worst.items())))
+
+
+def _layout_mutants(mistake, D, gran, pv):
+    """yield (slice label, ratio without the mistake, ratio with it) over the slices the mistake should corrupt"""
+    both = lambda own, f: (max(C.ratios(own, pv, *f(None))), max(C.ratios(own, pv, *f(mistake))))
+    if mistake == "head_scales_of_kv_head_0":
+        st = C.stack_slots(D, 456, False, gran)
+        for b in range(2):
+            yield (f"dense b{b} hk1",) + both(st["grid"][b][1], lambda m: C.restate_stack64(st, pv, b, 1, m))
+    elif mistake in ("batch_operands_of_batch_0", "interleave_b_h_swapped"):
+        st = C.stack_slots(D, 456, False, gran)
+        for lens in C.STACK_KV_LENS:
+            for b, hk in ((1, 0), (1, 1)) if mistake == "batch_operands_of_batch_0" else ((0, 1), (1, 0)):
+                own = C.cached_subcase(st["grid"][b][hk], None, lens[b])
+                yield (f"kvlen {lens} b{b} hk{hk}",) + both(own, lambda m: C.restate_stack64(st, pv, b, hk, m, lens))
+    elif mistake == "workspace_slot_of_head_0":
+        st = C.stack_slots(D, 456, False, gran, anchored=True)
+        km = C.stack_km(st)
+        for b in range(2):
+            for hk in range(2):
+                own = st["grid"][b][hk]
+                qkm = C.split_qkm(own, km[b:b + 1, hk:hk + 1])
+                f = lambda m: C.restate_stack_split64(st, pv, 2, b, hk, None, qkm, m)
+                g = lambda m: max(C.merged_ratios(own, pv, 2, *[x for i, x in enumerate(f(m)) if i != 1], qkm))
+                yield f"splitkv S2 b{b} hk{hk}", g(None), g(mistake)
+    elif mistake in ("cu_off_by_one_row", "scales_of_previous_sequence", "scale_row_by_max_seqlen_of_q"):
+        for causal in (False, True):
+            pk = C.pack_cases(D, gran, causal)
+            for s, row in enumerate(pk["cases"]):
+                for hk, own in enumerate(row):
+                    if own["N"] and (s > 0 or mistake == "cu_off_by_one_row" or (hk > 0 and mistake == "scale_row_by_max_seqlen_of_q")):
+                        yield (f"pack{'-causal' if causal else ''} seq{s} hk{hk}",) + both(own, lambda m: C.restate_pack64(pk, pv, s, hk, m))
+    elif mistake == "causal_bottom_right":
+        pk = C.pack_cases(D, gran, True)
+        for s in (0, 2):
+            for hk in range(2):
+                yield (f"pack-causal seq{s} hk{hk}",) + both(pk["cases"][s][hk], lambda m: C.restate_pack64(pk, pv, s, hk, m))
+        for label, c in C.causal_cut_cases(D, gran):
+            yield (label,) + both(c, lambda m: C.restate_causal64(c, pv, m))
+    else:
+        tm = C.tile_major(C.stack_slots(D, 456, False, gran))
+        for b in range(2):
+            for hk in range(2):
+                own = tm["st"]["grid"][b][hk]
+                yield (f"tiles b{b} hk{hk}",) + both(own, lambda m: C.restate64(C.read_tiles(tm, b, hk, m), pv))
+
+
+@pytest.mark.parametrize("mistake", C.LAYOUT_MISTAKES)
+def test_layout_bound_has_teeth(mistake):
+    """every deliberate addressing mistake of LAYOUT_MISTAKES leaves the bound (ratio > 1 on some element) on EVERY slice it
+    should corrupt, at the shapes tests/test_constructed_layouts_gpu.py runs, while the same restatement without the mistake is
+    the reference.  scale_row_by_max_seqlen_of_q cannot show where Gq(max M_s) = Gk(max N_s): per_warp scales at these lengths
+    (8 groups each), stated here rather than hidden -- it shows under per_thread (64 against 32) and per_block (2 against 8)."""
+    packed = mistake in C.LAYOUT_MISTAKES[4:7]
+    for D, gran in LAYOUT_SHAPES:
+        if mistake == "workspace_slot_of_head_0" and gran == "per_block":
+            continue  # the fused-Q entry points have no per_block form
+        if mistake == "scale_row_by_max_seqlen_of_q" and gran == "per_warp":
+            pk = C.pack_cases(D, gran, False)
+            assert pk["gq"] == pk["gk"] == 8
+            continue
+        for pv in ("fp16", "bf16") if packed else C.PVS:
+            hit = 0
+            for label, clean, r in _layout_mutants(mistake, D, gran, pv):
+                print(f"layout teeth: {mistake:30s} {label:28s} {gran:10s} D={D:<3d} {pv:5s} ratio {r:12.4g}   (no mistake: {clean:.1e})")
+                assert clean < 1e-3, (label, pv, clean)
+                assert r > 1.0, (mistake, label, gran, D, pv, r)
+                hit += 1
+            assert hit > 0
