@@ -141,6 +141,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     that carries the built .so and its stamp but no objects (the GPU box: *.o stay behind, .gpurunignore) builds nothing."""
     hdrs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_kvcache.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}

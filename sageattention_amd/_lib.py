@@ -124,10 +124,19 @@ SIGNATURES["sage_attn_qk_int8_pv_f16_masked"] = _attn(
     "qk_int8_pv_f16", operands=_OPERANDS["qk_int8_pv_f16"][:-2] + [_V, _I, _P64, _V], is_causal=False)
 
 
+# The extension headers, one table each: SIGNATURES stays the list of include/sageattn_hip.h.
+# include/sageattn_hip_kvcache.h: k v dtype | B H N D | km k_int8 k_scale gran rounding | v_fp8 v_coef | start_lens kv_lens
+# max_new stream
+KVCACHE_SIGNATURES = {
+    "sage_kv_cache_append": (_I, [_P, _P, _I, _I, _I, _I, _I, _V, _P, _V, _I, _I, _P, _V, _V, _V, _I, _V]),
+}
+
+
 def bind(cdll, missing_ok=True):
-    """Set restype / argtypes on every SIGNATURES symbol ``cdll`` has and return it.  An older library loaded for an A/B run
-    may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises AttributeError."""
-    for name, (res, args) in SIGNATURES.items():
+    """Set restype / argtypes on every SIGNATURES and KVCACHE_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
+    AttributeError."""
+    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -41,8 +41,11 @@ __device__ __forceinline__ void v_quant_load(const uint16_t* __restrict__ vhead,
   for (int i = 0; i < 4; ++i) raw[i] = *reinterpret_cast<const uint4*>(vhead + (int64_t)min(row0 + i, N - 1) * sn + tc * 8);
 }
 
-// step 2: scale, round to e4m3, write the thread's 8 dwords of the [d][pos] image (tile: BLKS * IMG dwords)
-template <int D, bool BF16>
+// step 2: scale, round to e4m3, write the thread's 8 dwords of the [d][pos] image (tile: BLKS * IMG dwords).
+// The conversion does NOT saturate: beyond +-448 it returns the NaN byte.  A scale taken from the tensor's own maximum never
+// gets there; SAT (the KV cache's frozen scale, which later rows may exceed) clamps to +-448 first -- values within the range,
+// and so every byte the form without SAT gives that is no NaN, are unchanged.
+template <int D, bool BF16, bool SAT = false>
 __device__ __forceinline__ void v_quant_to_image(const uint4 (&raw)[4], int N, int bx, const float (&mean)[8], const float (&rcp)[8],
                                                  uint32_t* __restrict__ tile) {
   using G = VQuantGeom<D>;
@@ -60,6 +63,10 @@ __device__ __forceinline__ void v_quant_to_image(const uint4 (&raw)[4], int N, i
     unpack8<BF16>(raw[i], f);
 #pragma unroll
     for (int j = 0; j < 8; ++j) x[i][j] = row < N ? (f[j] - mean[j]) * rcp[j] : 0.f;  // pad columns are exact zeros
+    if constexpr (SAT) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[i][j] = fminf(fmaxf(x[i][j], -448.f), 448.f);
+    }
   }
   // token t = 32*mt + (reg&3) + 8*(reg>>2) + 4*hh  ->  pos = 32*hh + 16*mt + reg; tokens t0..t0+3 differ in reg&3 only
   const int mt = t0 >> 5, w0 = t0 & 31, hh = (w0 >> 2) & 1;
@@ -68,7 +75,7 @@ __device__ __forceinline__ void v_quant_to_image(const uint4 (&raw)[4], int N, i
   for (int j = 0; j < 8; ++j) {
     int pk;
     asm("" : "=v"(pk));  // (`old` of the first convert: both halves are written, a literal 0 would cost a v_mov_b32)
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[0][j], x[1][j], pk, false);  // OCP e4m3fn, RNE, saturating
+    pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[0][j], x[1][j], pk, false);  // OCP e4m3fn, RNE
     pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[2][j], x[3][j], pk, true);
     const int d = tc * 8 + j;
     tile[bi * IMG + d * 16 + 4 * (d >> 3) + pos_dw] = (uint32_t)pk;
@@ -90,14 +97,14 @@ __device__ __forceinline__ void v_quant_store_image(uint8_t* __restrict__ out, i
   }
 }
 
-template <int D, bool BF16>
+template <int D, bool BF16, bool SAT = false>
 __device__ __forceinline__ void v_quant_transpose_body(const uint16_t* __restrict__ v, int64_t sb, int64_t sh, int64_t sn,
                                                        int N, const float (&mean)[8], const float (&rcp)[8],
                                                        uint8_t* __restrict__ out, int64_t ob, int64_t oh, int64_t od,
                                                        int64_t o_tile, int bx, int h, int b, uint32_t* __restrict__ tile) {
   uint4 raw[4];
   v_quant_load<D>(v + b * sb + h * sh, sn, N, bx, raw);
-  v_quant_to_image<D, BF16>(raw, N, bx, mean, rcp, tile);
+  v_quant_to_image<D, BF16, SAT>(raw, N, bx, mean, rcp, tile);
   __syncthreads();
   v_quant_store_image<D>(out, ob, oh, od, o_tile, N, bx, h, b, tile);
 }

@@ -15,6 +15,8 @@
 // there -- co-limited by vector issue, not by HBM; written for what a dense K call fixes it holds 9 and takes 66 us
 // (profiles/k_quant_valu_diet.md: the instruction census and the in-step traces).
 // Compiled with -ffp-contract=off: the integer outputs must match the oracle bit for bit.
+#include <algorithm>
+#include "../../include/sageattn_hip_kvcache.h"
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
 
@@ -857,6 +859,77 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kvlen_ke
 }
 
 // ------------------------------------------------------------------------------------------------
+// Persistent KV cache (include/sageattn_hip_kvcache.h): extend prepared operands in place, one launch.
+//   workgroups [0, k_slots): K slot i is tile t0_b + i of the batch, quantized by k_quant_block against the FROZEN km (read
+//                            straight from p.k.mean: no chunk sums), ragged at len_b where the tile holds row len_b - 1
+//   the rest (WITH_V):       V slot i is unit t0_b / BLKS + i (BLKS 64-token blocks), v_quant_transpose_body with the frozen
+//                            coefficients, clamped to +-448 (later rows may exceed a frozen range)
+// t0_b = floor(min(start_b, len_b - 1) / 64).  A slot beyond the batch's last tile, and every slot of an empty batch, leaves
+// before any barrier.  Same arithmetic per tile as the quantizers above: bit-identical to a from-scratch quantization of the
+// first len_b rows against km / v_coef.
+// ------------------------------------------------------------------------------------------------
+struct KvAppendParams {
+  QuantParams k;        // x = k, mean = km, out = k8, scale; N = the capacity
+  VPrepParams v;        // v, out = the V^T image (o_tile 64); part, v_scale, scale_max unused
+  const float* v_coef;  // [B,H,2,D]: zeros, coefficients
+  const int32_t* start_lens;
+  const int32_t* kv_lens;
+  int k_slots;
+};
+
+template <int D, bool BF16, bool TRITON, bool PER_THREAD>
+__device__ __forceinline__ void kv_append_k_tile(const QuantParams& p, const int blk, const int h, const int b, const int H,
+                                                 unsigned int (*gmax)[64]) {
+  using G = QuantGeom<D, 64>;
+  if (threadIdx.x < 64) gmax[0][threadIdx.x] = 0u;
+  const int tc = (int)threadIdx.x % G::TPR;
+  const uint16_t* xbase = p.x + b * p.xsb + h * p.xsh + tc * 8;
+  const bool whole = blk < p.N / 64;
+  uint4 raw[G::NP];
+  if (whole) k_load_rows<D, false>(xbase, p.xsn, blk, p.N, raw);
+  else k_load_rows<D, true>(xbase, p.xsn, blk, p.N, raw);
+  const uint4 mbits = *reinterpret_cast<const uint4*>(p.mean + ((int64_t)b * H + h) * D + tc * 8);
+  __syncthreads();  // gmax zeroed
+  // (zero_next: the streaming walk's rotation has nothing to prepare here; a second buffer takes the store)
+  if (whole) k_quant_block<D, BF16, TRITON, PER_THREAD, false>(p, blk, h, b, raw, mbits, gmax[0], gmax[1], [] {});
+  else k_quant_block<D, BF16, TRITON, PER_THREAD, true>(p, blk, h, b, raw, mbits, gmax[0], gmax[1], [] {});
+}
+
+template <int D, bool BF16, bool TRITON, bool WITH_V>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_kernel(const KvAppendParams a) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[2][64];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[WITH_V ? G::BLKS * G::IMG : 4];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const int len = kv_len_of(a.kv_lens, b, a.k.N);
+  if (len == 0) return;
+  const int t0 = min(kv_len_of(a.start_lens, b, a.k.N), len - 1) >> 6;
+  const int ntile = (len + 63) >> 6;
+  if ((int)blockIdx.x < a.k_slots) {
+    const int blk = t0 + blockIdx.x;
+    if (blk >= ntile) return;
+    QuantParams p = a.k;
+    p.N = len;
+    if (p.gran == SAGE_GRAN_PER_THREAD) kv_append_k_tile<D, BF16, TRITON, true>(p, blk, h, b, H, gmax);
+    else kv_append_k_tile<D, BF16, TRITON, false>(p, blk, h, b, H, gmax);
+    return;
+  }
+  if constexpr (WITH_V) {
+    const int unit = t0 / G::BLKS + ((int)blockIdx.x - a.k_slots);
+    if (unit * G::BLKS >= ntile) return;
+    const int tc = threadIdx.x % G::TPR;
+    float mean[8], rcp[8];
+    {
+      const float* cf = a.v_coef + (((int64_t)b * H + h) * 2) * D + tc * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { mean[j] = cf[j]; rcp[j] = cf[D + j]; }
+    }
+    v_quant_transpose_body<D, BF16, true>(a.v.v, a.v.sb, a.v.sh, a.v.sn, len, mean, rcp, a.v.out, a.v.ob, a.v.oh, a.v.od, a.v.o_tile,
+                                    unit, h, b, tile);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: sub_mean_f16
 // ------------------------------------------------------------------------------------------------
 template <bool BF16>
@@ -1219,4 +1292,48 @@ extern "C" int sage_kv_prepare_fp8_kvlen(const sage_tensor* k, const sage_tensor
                                      scale_max, workspace, kv_lens))
     return s;
   return kv_prepare_launch(c, (hipStream_t)stream);
+}
+
+// ---- persistent KV cache (include/sageattn_hip_kvcache.h): every check, the slots of the grid, one launch
+extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                                    const void* km, const sage_tensor* k_int8, float* k_scale, int gran, int rounding,
+                                    const sage_tensor* v_fp8, const float* v_coef, const int32_t* start_lens,
+                                    const int32_t* kv_lens, int max_new, sage_stream_t stream) {
+  if (!km || !aligned16(km) || !kv_lens_ok(start_lens) || !kv_lens_ok(kv_lens) || max_new < 1) return SAGE_ERR_INVALID_ARGUMENT;
+  if (v_fp8 && (!v_coef || !aligned16(v_coef) || !tensor_ok(v, 8) || !tensor_ok(v_fp8, 16))) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
+  QuantCall c;
+  if (const int s = quant_check(c, k, dtype, B, H, N, D, km, k_int8, k_scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1,
+                                nullptr))
+    return s;
+  KvAppendParams a;
+  a.k = c.p;
+  a.v = VPrepParams();
+  a.v_coef = v_coef;
+  if (v_fp8) {
+    a.v.v = (const uint16_t*)v->data; a.v.sb = v->stride_b; a.v.sh = v->stride_h; a.v.sn = v->stride_n;
+    a.v.out = (uint8_t*)v_fp8->data; a.v.ob = v_fp8->stride_b; a.v.oh = v_fp8->stride_h; a.v.od = v_fp8->stride_n; a.v.o_tile = 64;
+  }
+  a.start_lens = start_lens;
+  a.kv_lens = kv_lens;
+  // K slots: the tile that holds row min(start_b, len_b - 1), then the tiles of at most max_new further rows
+  const int ntile = (N + 63) / 64;
+  const int k_slots = std::min((std::min(max_new, N) + 63) / 64 + 1, ntile);
+  a.k_slots = k_slots;
+  // V slots: k_slots consecutive tiles lie in at most k_slots / blks + 1 units of blks tiles (blks == 1: in k_slots)
+  const int blks = by_dim(D, [](auto d) { return VQuantGeom<decltype(d)::value>::BLKS; });
+  const int v_slots = !v_fp8 ? 0 : blks == 1 ? k_slots : std::min(k_slots / blks + 1, (ntile + blks - 1) / blks);
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    by_flag(c.bf16, [&](auto bf) {
+      by_flag(rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        by_flag(v_fp8 != nullptr, [&](auto wv) {
+          hipLaunchKernelGGL((kv_cache_append_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value,
+                                                     decltype(wv)::value>),
+                             dim3(k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a);
+        });
+      });
+    });
+  });
+  return launch_status();
 }
