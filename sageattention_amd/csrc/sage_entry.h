@@ -74,6 +74,7 @@ struct KSmoothCall {
   float* part;
   int per_wg;  // 64-row blocks per workgroup of the quantizer
   const int32_t* kv_lens = nullptr;  // sage_k_smooth_quant_kvlen: rows >= clamp(kv_lens[b], 0, N) of batch b are absent
+  int slots;   // chunk slots per head of `part`: the chunks of N rows, with kv_lens the most a batch of up to N rows can have
 };
 int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B, int H, int N, int D, const sage_tensor* out,
                          float* scale, void* km, int gran, int rounding, void* workspace, const int32_t* kv_lens = nullptr);
@@ -89,6 +90,7 @@ struct KVPrepCall {
   int per_k, per_v;     // ... per workgroup of the streaming kernel
   bool streaming;       // kv_quant_stream_kernel, else kv_quant_kernel (one block / unit per workgroup)
   const int32_t* kv_lens = nullptr;  // sage_kv_prepare_fp8_kvlen: rows >= clamp(kv_lens[b], 0, N) of batch b are absent
+  int slots;            // chunk slots per head of kpart and vpart (as KSmoothCall::slots)
 };
 int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
                      const sage_tensor* k_int8, float* k_scale, void* km, int gran, int rounding, const sage_tensor* v_fp8,

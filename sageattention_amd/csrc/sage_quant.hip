@@ -47,6 +47,19 @@ __host__ __device__ __forceinline__ int kmean_max_chunks(int N) {
   const int c256 = (N + KMEAN_ROWS - 1) / KMEAN_ROWS;
   return c256 < 16 ? c256 : 16;
 }
+// kv_lens as the last argument of a pre-pass kernel: the pointer in its KVLEN instantiation, in the other an empty struct.
+// (A pointer that is merely not read moves the hidden arguments behind it -- the grid size -- by 8 bytes; the one byte of
+// the empty struct goes into the padding behind the int that every one of these kernels has in front of it, and the
+// instantiations without lengths keep their instruction streams: profiles/prepass_one_text.md.)
+template <bool KVLEN>
+struct KvLens {
+  KvLens(const int32_t*) {}
+};
+template <>
+struct KvLens<true> {
+  const int32_t* p;
+  KvLens(const int32_t* kv_lens) : p(kv_lens) {}
+};
 __device__ __forceinline__ int kv_len_of(const int32_t* __restrict__ kv_lens, int b, int N) { return min(max(kv_lens[b], 0), N); }
 
 // chunk s (KMEAN_ROWS rows) of head (b, h) of H: column sums -> part[b][h][s][D]; `red`: 256/(D/8) x (D+1) floats of LDS
@@ -97,23 +110,19 @@ __device__ __forceinline__ void k_mean_partial_body(const uint16_t* __restrict__
   }
 }
 
-template <int D, bool BF16>
+// KVLEN (per-batch key lengths): the chunks of batch b are those of a call on its len_b rows,
+// in the S chunk slots of its heads; the grid is sized for S slots, and the workgroups of chunks a batch does not have
+// leave before any barrier
+template <int D, bool BF16, bool KVLEN>
 __global__ __launch_bounds__(256) void k_mean_partial_kernel(const uint16_t* __restrict__ k, int64_t sb, int64_t sh,
-                                                             int64_t sn, int N, float* __restrict__ part, int S) {
+                                                             int64_t sn, int N, float* __restrict__ part, int S,
+                                                             const KvLens<KVLEN> kv_lens) {
   __shared__ float red[256 / (D / 8)][D + 1];
+  if constexpr (KVLEN) {
+    N = kv_len_of(kv_lens.p, blockIdx.z, N);
+    if ((int)blockIdx.x >= kmean_chunks(N)) return;  // (an empty batch has none)
+  }
   k_mean_partial_body<D, BF16>(k, sb, sh, sn, N, part, S, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, red);
-}
-
-// ... with per-batch key lengths: the chunks of batch b are those of a call on its len_b rows, in the S chunk slots of its
-// heads; the grid is sized for S slots, and the workgroups of chunks a batch does not have leave before any barrier
-template <int D, bool BF16>
-__global__ __launch_bounds__(256) void k_mean_partial_kvlen_kernel(const uint16_t* __restrict__ k, int64_t sb, int64_t sh,
-                                                                   int64_t sn, int N, float* __restrict__ part, int S,
-                                                                   const int32_t* __restrict__ kv_lens) {
-  __shared__ float red[256 / (D / 8)][D + 1];
-  const int len = kv_len_of(kv_lens, blockIdx.z, N);
-  if ((int)blockIdx.x >= kmean_chunks(len)) return;  // (an empty batch has none)
-  k_mean_partial_body<D, BF16>(k, sb, sh, sn, len, part, S, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, red);
 }
 
 template <bool BF16>
@@ -571,19 +580,12 @@ __device__ __forceinline__ void k_quant_stream_body(const QuantParams& p, const 
   else k_quant_stream_walk<D, BF16, TRITON, false>(p, per_wg, wg, h, b, H, gmax, mpart);
 }
 
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kernel(const QuantParams p, const int per_wg) {
-  __shared__ unsigned int gmax[3][64];
-  __shared__ __attribute__((aligned(16))) float mpart[16][D];
-  k_quant_stream_body<D, BF16, TRITON>(p, per_wg, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, gmax, mpart);
-}
-
 // The quantizer's parameters for batch b of a call with per-batch key lengths: N and the chunk count become those of its
 // len_b rows, so that the mean, the blocks and their scales are exactly those of a call on the first len_b rows (rows beyond
 // are never loaded: the ragged block clamps to row len_b - 1).  The quantizers address the chunk sums of head (b, h) at
 // (b H + h) S: S is count and head stride in one, but here every head has kmean_max_chunks(N) slots and the batch fills the
 // first S of them -- so the base moves by `part_shift` floats, and the unchanged address arithmetic lands on the head's slots
-// (the kernels without lengths keep their code).  Returns false when the workgroup, whose first 64-row block is blk0, has no
+// (the KVLEN = false instantiations keep their code).  Returns false when the workgroup, whose first 64-row block is blk0, has no
 // block of the batch: it leaves before any barrier.  An empty batch has no mean to take: km = 0, not 0 / 0, stored by the
 // first workgroup of the K half (k_half).
 template <int D>
@@ -600,16 +602,17 @@ __device__ __forceinline__ bool kvlen_batch_params(QuantParams& p, int64_t& part
   return blk0 * 64 < len;
 }
 
-// k_quant_stream_kernel with per-batch key lengths (sage_k_smooth_quant_kvlen): the grid is sized for N rows
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kvlen_kernel(const QuantParams p, const int per_wg,
-                                                                                    const int32_t* __restrict__ kv_lens) {
+// KVLEN (sage_k_smooth_quant_kvlen): the grid is sized for N rows, and p becomes the batch's own (kvlen_batch_params)
+template <int D, bool BF16, bool TRITON, bool KVLEN>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void k_quant_stream_kernel(QuantParams p, const int per_wg,
+                                                                              const KvLens<KVLEN> kv_lens) {
   __shared__ unsigned int gmax[3][64];
   __shared__ __attribute__((aligned(16))) float mpart[16][D];
-  QuantParams pb = p;
-  int64_t part_shift;
-  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, blockIdx.x * per_wg, blockIdx.y, blockIdx.z, gridDim.y, true)) return;
-  k_quant_stream_body<D, BF16, TRITON>(pb, per_wg, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, gmax, mpart);
+  if constexpr (KVLEN) {
+    int64_t part_shift;
+    if (!kvlen_batch_params<D>(p, part_shift, kv_lens.p, blockIdx.x * per_wg, blockIdx.y, blockIdx.z, gridDim.y, true)) return;
+  }
+  k_quant_stream_body<D, BF16, TRITON>(p, per_wg, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, gmax, mpart);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -664,48 +667,38 @@ __device__ __forceinline__ void v_amax_partial_body(const uint16_t* __restrict__
   }
 }
 
-template <int D, bool BF16>
+// KVLEN (see k_mean_partial_kernel): the sums and max|v| over the rows < len_b only
+template <int D, bool BF16, bool KVLEN>
 __global__ __launch_bounds__(256) void kv_partial_kernel(const uint16_t* __restrict__ k, int64_t ksb, int64_t ksh, int64_t ksn,
                                                          const uint16_t* __restrict__ v, int64_t vsb, int64_t vsh, int64_t vsn,
-                                                         int N, float* __restrict__ kpart, float* __restrict__ vpart, int S) {
+                                                         int N, float* __restrict__ kpart, float* __restrict__ vpart, int S,
+                                                         const KvLens<KVLEN> kv_lens) {
   static_assert(KMEAN_ROWS == VQ_ROWS, "one chunk size for both tensors");
   __shared__ float red[256 / (D / 8)][D + 1];
-  const int x = blockIdx.x;
+  const int x = blockIdx.x;  // K chunk x, or V chunk x - S
+  if constexpr (KVLEN) {
+    N = kv_len_of(kv_lens.p, blockIdx.z, N);
+    if ((x < S ? x : x - S) >= kmean_chunks(N)) return;
+  }
   if (x < S) k_mean_partial_body<D, BF16>(k, ksb, ksh, ksn, N, kpart, S, x, blockIdx.y, blockIdx.z, gridDim.y, red);
   else v_amax_partial_body<D, BF16>(v, vsb, vsh, vsn, N, vpart, S, x - S, blockIdx.y, blockIdx.z, gridDim.y, red);
 }
 
-// ... with per-batch key lengths (see k_mean_partial_kvlen_kernel): max|v| over the rows < len_b only
-template <int D, bool BF16>
-__global__ __launch_bounds__(256) void kv_partial_kvlen_kernel(const uint16_t* __restrict__ k, int64_t ksb, int64_t ksh, int64_t ksn,
-                                                               const uint16_t* __restrict__ v, int64_t vsb, int64_t vsh, int64_t vsn,
-                                                               int N, float* __restrict__ kpart, float* __restrict__ vpart, int S,
-                                                               const int32_t* __restrict__ kv_lens) {
-  __shared__ float red[256 / (D / 8)][D + 1];
-  const int len = kv_len_of(kv_lens, blockIdx.z, N);
-  const int x = blockIdx.x, s = x < S ? x : x - S;
-  if (s >= kmean_chunks(len)) return;
-  if (x < S) k_mean_partial_body<D, BF16>(k, ksb, ksh, ksn, len, kpart, S, s, blockIdx.y, blockIdx.z, gridDim.y, red);
-  else v_amax_partial_body<D, BF16>(v, vsb, vsh, vsn, len, vpart, S, s, blockIdx.y, blockIdx.z, gridDim.y, red);
-}
-
-// V half of kv_quant_kernel: unit bx (BLKS x 64 tokens) of head (b, h) of H.  p: N and the chunk count S
-template <int D, bool BF16>
-__device__ __forceinline__ void v_quant_unit(const QuantParams& p, const VPrepParams& q, const int bx, const int h, const int b,
-                                             const int H, float (*exch)[D], uint32_t* tile) {
+// The per-channel V scale of head (b, h) of H from its p.S chunk maxima (q.part): one round trip fetches all chunks (S <= 16
+// <= token groups per workgroup), the FIRST token group finishes the scale and hands the coefficients over through LDS
+// (every thread doing it for itself: 8 S maxima and 16 IEEE divisions per thread for 32 elements of real work), and the
+// head's workgroup wg == 0 stores v_scale.  Two barriers; rcp: this thread's 8 coefficients scale_max / max|v|
+template <int D>
+__device__ __forceinline__ void v_scale_finish(const QuantParams& p, const VPrepParams& q, const int h, const int b, const int H,
+                                               const int wg, float (*exch)[D], float (&rcp)[8]) {
   using G = VQuantGeom<D>;
   const int tg = threadIdx.x / G::TPR, tc = threadIdx.x % G::TPR;
-  // the unit's rows first: the statistics below overlap with this trip to HBM
-  uint4 raw[4];
-  v_quant_load<D>(q.v + b * q.sb + h * q.sh, q.sn, p.N, bx, raw);
-  if (tg < p.S) {  // one round trip for all chunks (S <= 16 <= token groups per workgroup)
+  if (tg < p.S) {
     const float* pp = q.part + (((int64_t)b * H + h) * p.S + tg) * D + tc * 8;
     *reinterpret_cast<float4*>(&exch[tg][tc * 8]) = *reinterpret_cast<const float4*>(pp);
     *reinterpret_cast<float4*>(&exch[tg][tc * 8 + 4]) = *reinterpret_cast<const float4*>(pp + 4);
   }
   __syncthreads();
-  // the per-channel scale is finished by the FIRST token group and handed over through LDS (every thread doing it for itself:
-  // 8 S maxima and 16 IEEE divisions per thread for 32 elements of real work)
   if (tg == 0) {  // (this thread alone reads columns tc*8 .. tc*8+7 of exch, so it may overwrite them in row 0)
     float rc[8], vs[8];
 #pragma unroll
@@ -717,54 +710,55 @@ __device__ __forceinline__ void v_quant_unit(const QuantParams& p, const VPrepPa
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) exch[0][tc * 8 + j] = rc[j];
-    if (bx == 0) {
+    if (wg == 0) {
       float* o = q.v_scale + ((int64_t)b * H + h) * D + tc * 8;
       *reinterpret_cast<float4*>(o) = make_float4(vs[0], vs[1], vs[2], vs[3]);
       *reinterpret_cast<float4*>(o + 4) = make_float4(vs[4], vs[5], vs[6], vs[7]);
     }
   }
   __syncthreads();
-  float mean[8], rcp[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { mean[j] = 0.f; rcp[j] = exch[0][tc * 8 + j]; }
+  for (int j = 0; j < 8; ++j) rcp[j] = exch[0][tc * 8 + j];
+}
+
+// V half of kv_quant_kernel: unit bx (BLKS x 64 tokens) of head (b, h) of H.  p: N and the chunk count S
+template <int D, bool BF16>
+__device__ __forceinline__ void v_quant_unit(const QuantParams& p, const VPrepParams& q, const int bx, const int h, const int b,
+                                             const int H, float (*exch)[D], uint32_t* tile) {
+  // the unit's rows first: the statistics below overlap with this trip to HBM
+  uint4 raw[4];
+  v_quant_load<D>(q.v + b * q.sb + h * q.sh, q.sn, p.N, bx, raw);
+  const float mean[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float rcp[8];
+  v_scale_finish<D>(p, q, h, b, H, bx, exch, rcp);
   v_quant_to_image<D, BF16>(raw, p.N, bx, mean, rcp, tile);
   __syncthreads();
   v_quant_store_image<D>(q.out, q.ob, q.oh, q.od, q.o_tile, p.N, bx, h, b, tile);
 }
 
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(const QuantParams p, const VPrepParams q, const int nblk_k) {
+// One K block or V unit per workgroup.  KVLEN (sage_kv_prepare_fp8_kvlen): the grid is sized for N rows and p, q become
+// the batch's own; the V^T image of the batch's last 64-token block is written whole, its columns >= len_b as zero bytes
+// (v_quant_to_image)
+template <int D, bool BF16, bool TRITON, bool KVLEN>
+__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kernel(QuantParams p, VPrepParams q, const int nblk_k,
+                                                                        const KvLens<KVLEN> kv_lens) {
   using G = VQuantGeom<D>;
   __shared__ unsigned int gmax[64];
   __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
   __shared__ __attribute__((aligned(16))) uint32_t tile[G::BLKS * G::IMG];
   const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  if ((int)blockIdx.x < nblk_k) {
+  const bool k_half = (int)blockIdx.x < nblk_k;  // K block blockIdx.x, or V unit blockIdx.x - nblk_k (BLKS blocks)
+  if constexpr (KVLEN) {
+    int64_t part_shift;
+    const int blk0 = k_half ? blockIdx.x : (blockIdx.x - nblk_k) * G::BLKS;
+    if (!kvlen_batch_params<D>(p, part_shift, kv_lens.p, blk0, h, b, H, k_half)) return;
+    q.part += part_shift;  // (the V partials have the layout of the K sums)
+  }
+  if (k_half) {
     quant_qk_int8_body<D, 64, BF16, TRITON>(p, blockIdx.x, h, b, H, gmax, exch);
     return;
   }
   v_quant_unit<D, BF16>(p, q, blockIdx.x - nblk_k, h, b, H, exch, tile);
-}
-
-// ... with per-batch key lengths (sage_kv_prepare_fp8_kvlen): the grid is sized for N rows; the V^T image of the batch's last
-// 64-token block is written whole, its columns >= len_b as zero bytes (v_quant_to_image)
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 8 : 7) void kv_quant_kvlen_kernel(const QuantParams p, const VPrepParams q, const int nblk_k,
-                                                                              const int32_t* __restrict__ kv_lens) {
-  using G = VQuantGeom<D>;
-  __shared__ unsigned int gmax[64];
-  __shared__ __attribute__((aligned(16))) float exch[16][D];
-  __shared__ __attribute__((aligned(16))) uint32_t tile[G::BLKS * G::IMG];
-  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  const bool k_half = (int)blockIdx.x < nblk_k;
-  const int unit = k_half ? blockIdx.x : blockIdx.x - nblk_k;  // K block, or V unit of BLKS blocks
-  QuantParams pb = p;
-  VPrepParams qb = q;
-  int64_t part_shift;
-  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, k_half ? unit : unit * G::BLKS, h, b, H, k_half)) return;
-  qb.part += part_shift;  // (the V partials have the layout of the K sums)
-  if (k_half) quant_qk_int8_body<D, 64, BF16, TRITON>(pb, unit, h, b, H, gmax, exch);
-  else v_quant_unit<D, BF16>(pb, qb, unit, h, b, H, exch, tile);
 }
 
 // Launch B as a STREAMING kernel for long sequences (sage_kv_prepare_fp8 picks by the units a workgroup would walk): workgroups [0, nwg_k) walk per_k consecutive K blocks
@@ -783,34 +777,9 @@ __device__ __forceinline__ void v_quant_stream_walk(const QuantParams& p, const 
   const uint16_t* vhead = q.v + b * q.sb + h * q.sh;
   uint4 raw[4];
   v_quant_load<D>(vhead, q.sn, p.N, u0, raw);
-  const int tg = threadIdx.x / G::TPR, tc = threadIdx.x % G::TPR;
-  if (tg < p.S) {  // one round trip for all chunks (S <= 16 <= token groups per workgroup)
-    const float* pp = q.part + (((int64_t)b * H + h) * p.S + tg) * D + tc * 8;
-    *reinterpret_cast<float4*>(&exch[tg][tc * 8]) = *reinterpret_cast<const float4*>(pp);
-    *reinterpret_cast<float4*>(&exch[tg][tc * 8 + 4]) = *reinterpret_cast<const float4*>(pp + 4);
-  }
-  __syncthreads();
-  if (tg == 0) {  // (this thread alone reads columns tc*8 .. tc*8+7 of exch, so it may overwrite them in rows 0 and 1)
-    float rc[8], vs[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = exch[0][tc * 8 + j];
-      for (int s_ = 1; s_ < p.S; ++s_) a = fmaxf(a, exch[s_][tc * 8 + j]);
-      rc[j] = a > 0.f ? q.scale_max / a : 0.f;   // v_stats_final_kernel (an all-zero channel: coefficient 0, not inf)
-      vs[j] = a / q.scale_max;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { exch[0][tc * 8 + j] = rc[j]; exch[1][tc * 8 + j] = vs[j]; }
-    if (wg == 0) {
-      float* o = q.v_scale + ((int64_t)b * H + h) * D + tc * 8;
-      *reinterpret_cast<float4*>(o) = make_float4(vs[0], vs[1], vs[2], vs[3]);
-      *reinterpret_cast<float4*>(o + 4) = make_float4(vs[4], vs[5], vs[6], vs[7]);
-    }
-  }
-  __syncthreads();
-  float mean[8], rcp[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { mean[j] = 0.f; rcp[j] = exch[0][tc * 8 + j]; }
+  const float mean[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float rcp[8];
+  v_scale_finish<D>(p, q, h, b, H, wg, exch, rcp);
   for (int u = u0; u < u1; ++u) {
     uint32_t* img = tile[(u - u0) & 1];
     v_quant_to_image<D, BF16>(raw, p.N, u, mean, rcp, img);
@@ -822,40 +791,28 @@ __device__ __forceinline__ void v_quant_stream_walk(const QuantParams& p, const 
   }
 }
 
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(const QuantParams p, const VPrepParams q, const int per_k,
-                                                                               const int nwg_k, const int per_v) {
+// KVLEN: see kv_quant_kernel
+template <int D, bool BF16, bool TRITON, bool KVLEN>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kernel(QuantParams p, VPrepParams q, const int per_k,
+                                                                               const int nwg_k, const int per_v,
+                                                                               const KvLens<KVLEN> kv_lens) {
   using G = VQuantGeom<D>;
   __shared__ unsigned int gmax[3][64];
   __shared__ __attribute__((aligned(16))) float exch[16][D];  // chunk partials of this head: K sums or V max|v|
   __shared__ __attribute__((aligned(16))) uint32_t tile[2][G::BLKS * G::IMG];
   const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  if ((int)blockIdx.x < nwg_k) {
+  const bool k_half = (int)blockIdx.x < nwg_k;  // K workgroup blockIdx.x, or V workgroup blockIdx.x - nwg_k
+  if constexpr (KVLEN) {
+    int64_t part_shift;
+    const int blk0 = k_half ? (int)blockIdx.x * per_k : (int)(blockIdx.x - nwg_k) * per_v * G::BLKS;
+    if (!kvlen_batch_params<D>(p, part_shift, kv_lens.p, blk0, h, b, H, k_half)) return;
+    q.part += part_shift;  // (the V partials have the layout of the K sums)
+  }
+  if (k_half) {
     k_quant_stream_body<D, BF16, TRITON>(p, per_k, blockIdx.x, h, b, H, gmax, exch);
     return;
   }
   v_quant_stream_walk<D, BF16>(p, q, per_v, blockIdx.x - nwg_k, h, b, H, exch, tile);
-}
-
-// ... with per-batch key lengths (see kv_quant_kvlen_kernel)
-template <int D, bool BF16, bool TRITON>
-__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_quant_stream_kvlen_kernel(const QuantParams p, const VPrepParams q,
-                                                                                     const int per_k, const int nwg_k, const int per_v,
-                                                                                     const int32_t* __restrict__ kv_lens) {
-  using G = VQuantGeom<D>;
-  __shared__ unsigned int gmax[3][64];
-  __shared__ __attribute__((aligned(16))) float exch[16][D];
-  __shared__ __attribute__((aligned(16))) uint32_t tile[2][G::BLKS * G::IMG];
-  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
-  const bool k_half = (int)blockIdx.x < nwg_k;
-  const int wg = k_half ? blockIdx.x : blockIdx.x - nwg_k;
-  QuantParams pb = p;
-  VPrepParams qb = q;
-  int64_t part_shift;
-  if (!kvlen_batch_params<D>(pb, part_shift, kv_lens, k_half ? wg * per_k : wg * per_v * G::BLKS, h, b, H, k_half)) return;
-  qb.part += part_shift;  // (the V partials have the layout of the K sums)
-  if (k_half) k_quant_stream_body<D, BF16, TRITON>(pb, per_k, wg, h, b, H, gmax, exch);
-  else v_quant_stream_walk<D, BF16>(pb, qb, per_v, wg, h, b, H, exch, tile);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -966,12 +923,17 @@ static int units_per_wg(int64_t BH, int units, int64_t target, int64_t cap) {
   return (int)(per < 1 ? 1 : per > units ? units : per);
 }
 
-static void launch_k_mean_partial(const sage_tensor& k, int B, int H, int N, int D, bool bf16, float* part, int S,
-                                  hipStream_t st) {
+// `slots` chunk slots per head: the chunks of N rows or, with kv_lens, kmean_max_chunks(N) (every batch is chunked by its
+// own length)
+static void launch_k_mean_partial(const sage_tensor& k, int B, int H, int N, int D, bool bf16, float* part, int slots,
+                                  const int32_t* kv_lens, hipStream_t st) {
   by_dim(D, [&](auto d) {
     by_flag(bf16, [&](auto bf) {
-      hipLaunchKernelGGL((k_mean_partial_kernel<decltype(d)::value, decltype(bf)::value>), dim3(S, H, B), dim3(256), 0, st,
-                         (const uint16_t*)k.data, k.stride_b, k.stride_h, k.stride_n, N, part, S);
+      by_flag(kv_lens != nullptr, [&](auto kl) {
+        hipLaunchKernelGGL((k_mean_partial_kernel<decltype(d)::value, decltype(bf)::value, decltype(kl)::value>),
+                           dim3(slots, H, B), dim3(256), 0, st, (const uint16_t*)k.data, k.stride_b, k.stride_h, k.stride_n, N,
+                           part, slots, kv_lens);
+      });
     });
   });
 }
@@ -1043,6 +1005,7 @@ int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B,
     return s;
   c.k = *k;
   c.kv_lens = kv_lens;
+  c.slots = kv_lens ? kmean_max_chunks(N) : opt.S;
   // as many blocks per workgroup as leave about as many workgroups per CU as the quantizer's registers allow to be resident
   // (five at head_dim 64, four at 128), so that every workgroup is resident from the start and streams its share of a head
   const int nblk = (N + 63) / 64;
@@ -1053,18 +1016,7 @@ int k_smooth_quant_check(KSmoothCall& c, const sage_tensor* k, int dtype, int B,
 int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
   const QuantParams& p = c.q.p;
   launch_begin();
-  if (c.kv_lens) {
-    const int slots = kmean_max_chunks(p.N);  // chunk slots per head: every batch is chunked by its own length
-    by_dim(c.q.D, [&](auto d) {
-      by_flag(c.q.bf16, [&](auto bf) {
-        hipLaunchKernelGGL((k_mean_partial_kvlen_kernel<decltype(d)::value, decltype(bf)::value>), dim3(slots, c.q.H, c.q.B),
-                           dim3(256), 0, st, (const uint16_t*)c.k.data, c.k.stride_b, c.k.stride_h, c.k.stride_n, p.N, c.part,
-                           slots, c.kv_lens);
-      });
-    });
-  } else {
-    launch_k_mean_partial(c.k, c.q.B, c.q.H, p.N, c.q.D, c.q.bf16, c.part, p.S, st);
-  }
+  launch_k_mean_partial(c.k, c.q.B, c.q.H, p.N, c.q.D, c.q.bf16, c.part, c.slots, c.kv_lens, st);
   if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
   const int nblk = (p.N + 63) / 64;
   const dim3 grid((nblk + c.per_wg - 1) / c.per_wg, c.q.H, c.q.B);
@@ -1072,12 +1024,10 @@ int k_smooth_quant_launch(const KSmoothCall& c, hipStream_t st) {
   by_dim(c.q.D, [&](auto d) {
     by_flag(c.q.bf16, [&](auto bf) {
       by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
-        constexpr int DD = decltype(d)::value;
-        constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value;
-        if (c.kv_lens)
-          hipLaunchKernelGGL((k_quant_stream_kvlen_kernel<DD, BF, TR>), grid, dim3(256), 0, st, p, c.per_wg, c.kv_lens);
-        else
-          hipLaunchKernelGGL((k_quant_stream_kernel<DD, BF, TR>), grid, dim3(256), 0, st, p, c.per_wg);
+        by_flag(c.kv_lens != nullptr, [&](auto kl) {
+          hipLaunchKernelGGL((k_quant_stream_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value, decltype(kl)::value>),
+                             grid, dim3(256), 0, st, p, c.per_wg, c.kv_lens);
+        });
       });
     });
   });
@@ -1094,9 +1044,9 @@ int kv_prepare_check(KVPrepCall& c, const sage_tensor* k, const sage_tensor* v, 
   if (!tensor_ok(v_fp8, 16)) return SAGE_ERR_INVALID_ARGUMENT;
   if (const int s = dim_dtype_status(D, dtype)) return s;
   const int S = kmean_chunks(N);
-  const int slots = kv_lens ? kmean_max_chunks(N) : S;  // chunk slots per head (every batch is chunked by its own length)
+  c.slots = kv_lens ? kmean_max_chunks(N) : S;  // chunk slots per head (every batch is chunked by its own length)
   c.kpart = (float*)workspace;
-  c.vpart = c.kpart + (size_t)B * H * slots * D;
+  c.vpart = c.kpart + (size_t)B * H * c.slots * D;
   c.kv_lens = kv_lens;
   QuantOptions opt;
   opt.mean_part = c.kpart;
@@ -1131,14 +1081,11 @@ int kv_prepare_launch(const KVPrepCall& c, hipStream_t st) {
   launch_begin();
   by_dim(c.k.D, [&](auto d) {
     by_flag(c.k.bf16, [&](auto bf) {
-      constexpr int DD = decltype(d)::value;
-      constexpr bool BF = decltype(bf)::value;
-      if (c.kv_lens)
-        hipLaunchKernelGGL((kv_partial_kvlen_kernel<DD, BF>), dim3(2 * kmean_max_chunks(p.N), H, B), dim3(256), 0, st, p.x, p.xsb,
-                           p.xsh, p.xsn, q.v, q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, kmean_max_chunks(p.N), c.kv_lens);
-      else
-        hipLaunchKernelGGL((kv_partial_kernel<DD, BF>), dim3(2 * p.S, H, B), dim3(256), 0, st, p.x, p.xsb, p.xsh, p.xsn, q.v,
-                           q.sb, q.sh, q.sn, p.N, c.kpart, c.vpart, p.S);
+      by_flag(c.kv_lens != nullptr, [&](auto kl) {
+        hipLaunchKernelGGL((kv_partial_kernel<decltype(d)::value, decltype(bf)::value, decltype(kl)::value>),
+                           dim3(2 * c.slots, H, B), dim3(256), 0, st, p.x, p.xsb, p.xsh, p.xsn, q.v, q.sb, q.sh, q.sn, p.N, c.kpart,
+                           c.vpart, c.slots, c.kv_lens);
+      });
     });
   });
   if (launch_status() != SAGE_OK) return SAGE_ERR_LAUNCH;
@@ -1146,19 +1093,16 @@ int kv_prepare_launch(const KVPrepCall& c, hipStream_t st) {
   by_dim(c.k.D, [&](auto d) {
     by_flag(c.k.bf16, [&](auto bf) {
       by_flag(p.rounding == SAGE_ROUND_TRITON, [&](auto tr) {
-        constexpr int DD = decltype(d)::value;
-        constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value;
-        if (c.kv_lens && c.streaming)
-          hipLaunchKernelGGL((kv_quant_stream_kvlen_kernel<DD, BF, TR>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q,
-                             c.per_k, nwg_k, c.per_v, c.kv_lens);
-        else if (c.kv_lens)
-          hipLaunchKernelGGL((kv_quant_kvlen_kernel<DD, BF, TR>), dim3(c.nblk_k + c.nunit_v, H, B), dim3(256), 0, st, p, q,
-                             c.nblk_k, c.kv_lens);
-        else if (c.streaming)
-          hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, TR>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q, c.per_k,
-                             nwg_k, c.per_v);
-        else
-          hipLaunchKernelGGL((kv_quant_kernel<DD, BF, TR>), dim3(c.nblk_k + c.nunit_v, H, B), dim3(256), 0, st, p, q, c.nblk_k);
+        by_flag(c.kv_lens != nullptr, [&](auto kl) {
+          constexpr int DD = decltype(d)::value;
+          constexpr bool BF = decltype(bf)::value, TR = decltype(tr)::value, KL = decltype(kl)::value;
+          if (c.streaming)
+            hipLaunchKernelGGL((kv_quant_stream_kernel<DD, BF, TR, KL>), dim3(nwg_k + nwg_v, H, B), dim3(256), 0, st, p, q, c.per_k,
+                               nwg_k, c.per_v, c.kv_lens);
+          else
+            hipLaunchKernelGGL((kv_quant_kernel<DD, BF, TR, KL>), dim3(c.nblk_k + c.nunit_v, H, B), dim3(256), 0, st, p, q,
+                               c.nblk_k, c.kv_lens);
+        });
       });
     });
   });
@@ -1182,7 +1126,7 @@ extern "C" int sage_k_mean(const sage_tensor* k, int dtype, int B, int H, int N,
   float* const ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   launch_begin();
-  launch_k_mean_partial(*k, B, H, N, D, dtype == SAGE_BF16, ws, S, st);
+  launch_k_mean_partial(*k, B, H, N, D, dtype == SAGE_BF16, ws, S, nullptr, st);
   by_flag(dtype == SAGE_BF16, [&](auto bf) {
     hipLaunchKernelGGL((k_mean_final_kernel<decltype(bf)::value>), dim3(B * H), dim3(128), 0, st, ws, S, D, N, (uint16_t*)km);
   });

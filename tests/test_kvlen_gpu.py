@@ -142,15 +142,11 @@ def test_lengths_are_clamped(sa, pv):
 
 
 # ---- 6. the pre-pass alone ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,lens", [(320, [320, 257, 256, 65, 1, 0]), (4400, LONG)], ids=["n320", "n4400"])
-@pytest.mark.parametrize("gran", ["per_thread", "per_warp"])
-@pytest.mark.parametrize("D", [64, 128])
-def test_prepass(sa, D, gran, N, lens):
-    """km, the INT8 K rows < len_b and their scales, and for FP8 v_scale and the V^T columns < len_b, equal those of the
-    pre-pass called on the slice; the V^T columns up to the end of the last 64-token block are zero bytes; km of a batch
-    without keys is 0"""
+def _check_prepass(k, v, lens, gran):
+    """NaN into the K and V rows >= len_b, then ``k_smooth_quant_kvlen`` and ``kv_prepare_fp8_kvlen`` against the calls without
+    lengths on every batch's slice: km, the INT8 K rows < len_b and their scales, v_scale and the V^T bytes up to the padded
+    length equal, bit for bit; zero bytes in the pad columns of the last 64-token block; km = 0 for a batch without keys"""
     from sageattention_amd import core, quant
-    _, k, v = _make(len(lens), N, D, seed=2)
     _poison(k, v, lens)
     kv_lens = torch.tensor(lens, dtype=torch.int32, device="cuda")
     kg, rnd = core._k_pairing(gran)
@@ -176,6 +172,62 @@ def test_prepass(sa, D, gran, N, lens):
         beyond = order + 64 * (nb - 1) >= n  # positions of the last 64-token block that hold tokens >= len_b
         last = v8[b, :, :, npad - 64:npad].view(torch.uint8)
         assert not last[..., beyond].any(), f"V^T pad columns of batch {b} (len {n})"
+
+
+@pytest.mark.parametrize("N,lens", [(320, [320, 257, 256, 65, 1, 0]), (4400, LONG)], ids=["n320", "n4400"])
+@pytest.mark.parametrize("gran", ["per_thread", "per_warp"])
+@pytest.mark.parametrize("D", [64, 128])
+def test_prepass(sa, D, gran, N, lens):
+    """km, the INT8 K rows < len_b and their scales, and for FP8 v_scale and the V^T columns < len_b, equal those of the
+    pre-pass called on the slice; the V^T columns up to the end of the last 64-token block are zero bytes; km of a batch
+    without keys is 0"""
+    _, k, v = _make(len(lens), N, D, seed=2)
+    _check_prepass(k, v, lens, gran)
+
+
+def _kv(B, H, N, D, dtype, seed):
+    """seeded k and v of H heads, drawn on the GPU (the streaming shapes are up to 126 MB an operand); k with a per-channel
+    offset as in _make"""
+    g = torch.Generator(device="cuda").manual_seed(1000 * D + N + seed)
+    k = torch.randn(B, H, N, D, generator=g, device="cuda") + 2.0 * torch.randn(B, H, 1, D, generator=g, device="cuda")
+    v = torch.randn(B, H, N, D, generator=g, device="cuda")
+    return k.to(dtype), v.to(dtype)
+
+
+# The smallest shapes at which the dense K/V pre-pass streams (test_gpu_parity.py): by units_per_wg a V workgroup walks 4 units
+# at head_dim 64 and 16 at 128 (streaming from 4 and 12), a K workgroup of sage_k_smooth_quant 4 blocks at head_dim 64
+STREAMING = [((4, 32, 2050, 64), [2050, 2049, 1300, 0]), ((3, 40, 4100, 128), [4100, 4097, 65])]
+
+
+@pytest.mark.parametrize("gran", ["per_thread", "per_warp"])  # (per_thread, triton) and (per_block, cuda)
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("shape,lens", STREAMING, ids=["d64", "d128"])
+def test_prepass_streaming(sa, shape, lens, dtype, gran):
+    """test_prepass where the calls with lengths run the streaming kernels, K and V, several blocks per workgroup; the sliced
+    calls (one batch) do not stream, and the two dense forms are held equal in test_gpu_parity.py"""
+    k, v = _kv(*shape, dtype, seed=5)
+    _check_prepass(k, v, lens, gran)
+
+
+@pytest.mark.parametrize("dtype,gran", [(torch.float16, "per_thread"), (torch.bfloat16, "per_warp")], ids=["fp16-per_thread", "bf16-per_warp"])
+@pytest.mark.parametrize("shape", [(2, 2, 320, 64), (2, 2, 4400, 128), STREAMING[0][0]], ids=["n320", "n4400", "streaming"])
+def test_full_lengths_take_the_other_branch_of_one_text(sa, shape, dtype, gran):
+    """kv_lens = [N] * B: every output equals that of the call without lengths on the same operands -- km, k8, scales, v_scale
+    and all V^T bytes, pad columns included.  (2, 2, 4400, 128): 16 chunk slots per head for 9 chunks, so the workspace is
+    addressed through part_shift"""
+    from sageattention_amd import core, quant
+    B, _, N, _ = shape
+    k, v = _kv(*shape, dtype, seed=6)
+    kv_lens = torch.full((B,), N, dtype=torch.int32, device="cuda")
+    kg, rnd = core._k_pairing(gran)
+    got = quant.k_smooth_quant_kvlen(k, kv_lens, "HND", kg, rnd) + quant.kv_prepare_fp8_kvlen(k, v, kv_lens, "HND", kg, rnd)
+    ref = quant.k_smooth_quant(k, "HND", kg, rnd) + quant.kv_prepare_fp8(k, v, "HND", kg, rnd)
+    torch.cuda.synchronize()
+    names = ("k8", "k_scale", "km", "k8 (fp8)", "k_scale (fp8)", "km (fp8)", "v_fp8", "v_scale")
+    for name, a, r in zip(names, got, ref):
+        a, r = (t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t for t in (a, r))
+        assert torch.equal(a, r), name
+    assert all(torch.isfinite(t.float()).all() for t in ref if t.dtype != torch.float8_e4m3fn)
 
 
 # ---- 7. HIP-graph capture ------------------------------------------------------------------------------------------------------

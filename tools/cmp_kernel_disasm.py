@@ -31,7 +31,23 @@ splitkv_merge_kernel<BF16, MAXC, true>, the other one <BF16, MAXC, false>); agai
     --rename '27splitkv_causal_merge_kernel(ILb[01]ELi\d+E)EEvNS_10AttnParamsEi$=20splitkv_merge_kernel\1Lb1EEEvNS_10AttnParamsEi'
 
 The causal instantiations moved from sage_attn_splitkv_causal.o to sage_attn_splitkv.o with that.  Between two directories a
-function that one object lost and another gained is compared across the two and reported as "moved"."""
+function that one object lost and another gained is compared across the two and reported as "moved".
+
+The five K and K/V pre-pass kernels of sage_quant.hip (k_mean_partial, kv_partial, k_quant_stream, kv_quant, kv_quant_stream)
+lost their _kvlen twins to a trailing template flag KVLEN and a trailing argument KvLens<KVLEN>; against a build from before
+that:
+
+    --rename '((?:21k_mean_partial|17kv_partial)_kernelI.*E)EEv(.*)$=\1Lb0EEEv\2NS_6KvLensIXT1_EEE'
+    --rename '((?:21k_quant_stream|15kv_quant|22kv_quant_stream)_kernelI.*E)EEv(.*)$=\1Lb0EEEv\2NS_6KvLensIXT2_EEE'
+    --rename '27k_mean_partial_kvlen_kernel(I.*E)EEv(.*)PKi$=21k_mean_partial_kernel\1Lb1EEEv\2NS_6KvLensIXT1_EEE'
+    --rename '23kv_partial_kvlen_kernel(I.*E)EEv(.*)PKi$=17kv_partial_kernel\1Lb1EEEv\2NS_6KvLensIXT1_EEE'
+    --rename '27k_quant_stream_kvlen_kernel(I.*E)EEv(.*)PKi$=21k_quant_stream_kernel\1Lb1EEEv\2NS_6KvLensIXT2_EEE'
+    --rename '21kv_quant_kvlen_kernel(I.*E)EEv(.*)PKi$=15kv_quant_kernel\1Lb1EEEv\2NS_6KvLensIXT2_EEE'
+    --rename '28kv_quant_stream_kvlen_kernel(I.*E)EEv(.*)PKi$=22kv_quant_stream_kernel\1Lb1EEEv\2NS_6KvLensIXT2_EEE'
+
+(the first two give the kernels without lengths the flag false and the argument, the others rename the twins, whose last
+argument was the pointer, PKi.  A mangled name spells the argument's type as "KvLens of the kernel's template parameter n":
+XT1_ is the third parameter of the two partial kernels, XT2_ the fourth of the three quantizers)."""
 import argparse
 import glob
 import os
