@@ -48,8 +48,9 @@
  * attention call, and a replay reads the lengths the tensors hold then.
  *
  * NOT BUILT: dropping the caller's fp16 K buffer (the ragged tile is quantized again from its fp16 rows; without them the
- * cache would need a 64-row fp16 tail per head and a sequential walk); paged / block-table caches; moving the frozen km or
- * V scale without preparing again; V smoothing and K without smoothing.
+ * cache would need a 64-row fp16 tail per head and a sequential walk); moving the frozen km or V scale without preparing
+ * again; V smoothing and K without smoothing.  Paged / block-table caches are sageattn_hip_paged.h: this rule in logical
+ * tiles, on pages of one pool.
  */
 #ifndef SAGEATTN_HIP_KVCACHE_H
 #define SAGEATTN_HIP_KVCACHE_H

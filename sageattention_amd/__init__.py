@@ -12,11 +12,13 @@ from . import quant, _qattn, _fused  # noqa: F401
 from .ring import ring_sageattn  # noqa: F401  (sequence parallel, RCCL send/recv)
 from .ulysses import ulysses_sageattn  # noqa: F401  (head parallel, RCCL all-to-all)
 from .kvcache import SageKVCache, sageattn_splitkv_cached  # a persistent quantized KV cache for the split-KV operators
+from .paged import SagePagedKVCache, sageattn_splitkv_paged  # ... kept in pages of one pool, addressed through a block table
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen", "ring_sageattn",
            "ulysses_sageattn", "sageattn_block_sparse", "block_sparse_plan", "BlockSparsePlan", "sageattn_sparge",
            "sparge_plan", "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen",
            "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits",
-           "sageattn_splitkv_causal", "SageKVCache", "sageattn_splitkv_cached"]
+           "sageattn_splitkv_causal", "SageKVCache", "sageattn_splitkv_cached",
+           "SagePagedKVCache", "sageattn_splitkv_paged"]
 __version__ = "0.2.0"

@@ -29,6 +29,9 @@ SOURCES = [
     ("sage_attn_splitkv.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     # ... and their causal twins (the diagonal aligned to the end of the batch's keys)
     ("sage_attn_splitkv_causal.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # ... and the paged twins of the two (K / V tiles out of the pages a block table names)
+    ("sage_attn_splitkv_paged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    ("sage_attn_splitkv_causal_paged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -72,6 +75,8 @@ def _check_occupancy(src, compiler_output):
                             re.search(r"attn_i8_kvlen_kernelILi64ELi4E(Lb[01]E){4}EE", name) or     # ... with key lengths
                             re.search(r"attn_i8_splitkv_kernelILi64E(Lb[01]E){3}EE", name) or       # ... over splits of the keys
                             re.search(r"attn_i8_splitkv_causal_kernelILi64E(Lb[01]E){3}EE", name) or  # ... with the diagonal
+                            re.search(r"attn_i8_splitkv_paged_kernelILi64E(Lb[01]E){3}EE", name) or       # ... out of pages
+                            re.search(r"attn_i8_splitkv_causal_paged_kernelILi64E(Lb[01]E){3}EE", name) or
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
                             re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name) or
                             # the block-sparse kernels with key lengths, held to the lines of their twins above
@@ -142,6 +147,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_kvcache.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -182,6 +188,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_sparse_kvlen_pvskip.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_causal.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_paged.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_causal_paged.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

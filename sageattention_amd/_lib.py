@@ -131,12 +131,24 @@ KVCACHE_SIGNATURES = {
     "sage_kv_cache_append": (_I, [_P, _P, _I, _I, _I, _I, _I, _V, _P, _V, _I, _I, _P, _V, _V, _V, _I, _V]),
 }
 
+# include/sageattn_hip_paged.h.  The table's own arguments, in this order in all three: block_table table_stride max_pages
+# page_size num_pages.  The append: k_pool v_pool dtype | B H D | km k8_pool k_scale_pool gran rounding | v8_pool v_coef | table |
+# start_lens kv_lens max_new stream.  The attention entries: the fusedq operands without v_mean | B Hq Hk M D | qk_gran warpq
+# sm_scale | table | kv_lens num_splits causal q_fold workspace workspace_bytes stream
+_TABLE = [_V, c_int64, _I, _I, _I]
+_PAGED_TAIL = [_I] * 5 + _QUANT["fusedq"] + _TABLE + [_V, _I, _I, _I, _V, c_size_t, _V]
+PAGED_SIGNATURES = {
+    "sage_kv_cache_append_paged": (_I, [_P, _P, _I, _I, _I, _I, _V, _P, _V, _I, _I, _P, _V] + _TABLE + [_V, _V, _I, _V]),
+    "sage_attn_fusedq_pv_f16_splitkv_paged": (_I, [_P, _I, _P, _P, _I, _P, _I, _V, _V, _V] + _PAGED_TAIL),
+    "sage_attn_fusedq_pv_f8_splitkv_paged": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _PAGED_TAIL),
+}
+
 
 def bind(cdll, missing_ok=True):
-    """Set restype / argtypes on every SIGNATURES and KVCACHE_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES and PAGED_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
-    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

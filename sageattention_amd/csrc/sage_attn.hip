@@ -43,7 +43,7 @@ template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8
 //  without scratch, but left alone hipcc settles a few registers above the line)
 __global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kernel(const AttnParams p) {
-  constexpr bool SPARSE = false, PVSKIP = false, KVLEN = false, SPLITKV = false;
+  constexpr bool SPARSE = false, PVSKIP = false, KVLEN = false, SPLITKV = false, PAGED = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -55,7 +55,7 @@ template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(256, (D == 64 && PV_FP8) ? 3 : 2)
 void attn_i8_blocksparse_kernel(const AttnParams p) {
   constexpr int NWAVES = 4;
-  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false, KVLEN = false, SPLITKV = false;
+  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = false, KVLEN = false, SPLITKV = false, PAGED = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL
@@ -160,6 +160,7 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     if (sparse || a.key_lens || a.is_causal || a.mask || a.cu_q || a.cu_k || a.kvl || a.v_mean || a.q_dtype < 0 || !a.km)
       return SAGE_ERR_UNSUPPORTED;
   }
+  if (a.paged && !a.split_kv) return SAGE_ERR_UNSUPPORTED;  // block tables: the split-KV form only
   if (a.mask && (a.mask_kind < 1 || a.mask_kind > 3 || !a.mask_strides || a.is_causal || a.pv_fp8 || a.cu_q)) return SAGE_ERR_INVALID_ARGUMENT;
   const bool fusedq = a.q_dtype >= 0;  // a.q is then the fp16/bf16 query tensor
   if ((a.cu_q == nullptr) != (a.cu_k == nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
@@ -187,7 +188,8 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
   if ((warpq != 16 && warpq != 32 && warpq != 64 && warpq != 128) || a.blkq % warpq != 0) return SAGE_ERR_INVALID_ARGUMENT;
   if ((a.v_mean && !aligned16(a.v_mean)) || (a.v_scale && !aligned16(a.v_scale))) return SAGE_ERR_INVALID_ARGUMENT;
   // KV tile layout: dense by default (a tile = 64 consecutive rows of the sage_tensor), explicit for tile-major buffers
-  const int64_t ntile = ((int64_t)a.N + 63) >> 6;
+  // (paged: the tiles of one PAGE -- a (page, head) slice is what the strides of the scales and the window below describe)
+  const int64_t ntile = a.paged ? a.page_size / 64 : ((int64_t)a.N + 63) >> 6;
   int64_t k_tile = 64 * a.k8->stride_n, v_tile = a.pv_fp8 ? 64 : 128 * a.v->stride_n;  // bytes
   const int per_tile = a.qk_gran == SAGE_GRAN_PER_THREAD ? 4 : 1;
   int64_t ks_h = ntile * per_tile, ks_b = ks_h * a.Hk, ks_t = per_tile;
@@ -264,6 +266,12 @@ int attn_check(AttnCall& c, const AttnArgs& a) {
     if (a.split_causal) p.q_fold = a.q_fold;  // (... and the word of the third mask stride)
   }
   c.splitkv_causal = a.split_kv && a.split_causal;
+  c.paged = a.paged;
+  if (c.paged) {  // (the words of the second and fourth mask stride and of kv_tiled, which only the host reads)
+    p.block_table = a.block_table;
+    p.bt_stride = a.table_stride;
+    p.bt_shift = a.page_size == 64 ? 0 : a.page_size == 128 ? 1 : 2;
+  }
   c.D = a.D; c.nwaves = nw; c.sparse = sparse;
   c.pv_fp8 = a.pv_fp8; c.causal = a.is_causal != 0; c.kthread = a.qk_gran == SAGE_GRAN_PER_THREAD; c.v_bf16 = a.v_dtype == SAGE_BF16;
   return SAGE_OK;
@@ -273,7 +281,8 @@ int attn_launch(const AttnCall& c, hipStream_t st) {
   if (c.sparse) return launch_blocksparse(c, st);
   if (c.kvlen) return launch_kvlen(c, st);
   if (c.splitkv) {  // the attention kernel over (b, h, q-block, split), causal or not, then the merge
-    const int s = c.splitkv_causal ? launch_splitkv_causal_attn(c, st) : launch_splitkv_attn(c, st);
+    const int s = c.paged ? (c.splitkv_causal ? launch_splitkv_causal_paged_attn(c, st) : launch_splitkv_paged_attn(c, st))
+                          : (c.splitkv_causal ? launch_splitkv_causal_attn(c, st) : launch_splitkv_attn(c, st));
     return s ? s : launch_splitkv_merge(c, st);
   }
   return by_dim(c.D, [&](auto d) {

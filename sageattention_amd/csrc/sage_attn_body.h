@@ -4,7 +4,10 @@
 // (sage_attn_sparse_kvlen_pvskip.hip), attn_i8_splitkv_kernel (sage_attn_splitkv.hip) and attn_i8_splitkv_causal_kernel
 // (sage_attn_splitkv_causal.hip), not a header in the usual sense.
 // Expects in scope: the kernel parameter block `p` and the compile-time constants D, NWAVES, CAUSAL, KTHREAD, V_BF16, PV_FP8,
-// HAS_MASK, SPARSE, PVSKIP, KVLEN, SPLITKV
+// HAS_MASK, SPARSE, PVSKIP, KVLEN, SPLITKV, PAGED
+// (PAGED, with SPLITKV only: attn_i8_splitkv_paged_kernel / attn_i8_splitkv_causal_paged_kernel, sage_attn_splitkv_paged.hip /
+// sage_attn_splitkv_causal_paged.hip -- K, V and the K scales are pools of pages and tile j of the batch comes from the page
+// its block-table row names, through a descriptor of its own; every other kernel defines PAGED = false)
 // (see those files for what they select; KVLEN: attn_i8_kvlen_kernel, sage_attn_kvlen.hip; SPARSE && KVLEN: the tile lists
 // clipped at the batch's length, sage_attn_sparse_kvlen.hip; SPLITKV: one workgroup per (b, h, q-block, split) walks the
 // split's range of key tiles and stores an fp32 partial result, sage_attn_splitkv.hip; CAUSAL && SPLITKV: the diagonal is
@@ -19,6 +22,7 @@
   static_assert(!KVLEN || !HAS_MASK, "per-batch key lengths: the dense or the block-sparse kernel, without attn_mask");
   static_assert(!SPLITKV || (!HAS_MASK && !SPARSE && !KVLEN && NWAVES == 4),
                 "split-KV: 4 waves, no attn_mask, no block map (its optional lengths are its own: p.kv_lens may be null)");
+  static_assert(!PAGED || SPLITKV, "block tables: the split-KV kernels only");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -389,19 +393,68 @@
       v_voff[i] = (vr * (int)p.vsn + cc * 8) * 2;
     }
   }
-  // K(j) -> K buffer `buf`
-  auto dma_k = [&](const int j, const int buf) __attribute__((always_inline)) {
+  // PAGED (the rule: include/sageattn_hip_paged.h).  Tile j of the moved operands is logical tile sk_t0 + j of the batch: tile
+  // (sk_t0 + j) % tpp of the page that entry (sk_t0 + j) / tpp of the batch's table row names, tpp = page_size / 64 a power of
+  // two.  A page may lie anywhere in a pool of any size, so the tile gets a descriptor of its OWN: words 0-1 are the 64-bit
+  // address pool + page * page stride + hk * head stride + tile * tile bytes, formed on the scalar unit, word 2 the bytes of
+  // the tile -- of the batch's last tile those up to row len_b - 1, so that the rows behind it (NaN in a recycled page) reach
+  // the LDS as zeros exactly as they do through k_bytes / v_bytes above -- and the scalar offset is 0.  Only a tile's own
+  // bytes go through a 32-bit offset.  The copies use lds_dma16_fresh: the descriptor is computed in front of every copy, and
+  // its wait states stand inside that asm string (sage_attn_common.h).  The page ids come through the scalar cache, requested
+  // an iteration ahead like the block-sparse lists (bw1 .. bw4 below hold pages here), with the table index clamped to the
+  // one of the range's last tile: no entry at or beyond ceil(len_b / page_size) is read.
+  const int8_t* pg_k = nullptr;
+  const uint8_t* pg_v = nullptr;
+  const float* pg_ks = nullptr;
+  const int* pg_row = nullptr;
+  int pg_tmask = 0;
+  unsigned pg_kfull = 0, pg_klast = 0, pg_vfull = 0, pg_vlast = 0;
+  (void)pg_k; (void)pg_v; (void)pg_ks; (void)pg_row; (void)pg_tmask; (void)pg_kfull; (void)pg_klast; (void)pg_vfull; (void)pg_vlast;
+  if constexpr (PAGED) {
+    pg_k = p.k + hk * p.ksh;
+    pg_v = p.v + hk * p.vsh * (PV_FP8 ? 1 : 2);
+    pg_ks = p.k_scale + hk * p.ks_h;
+    pg_row = p.block_table + (int64_t)b * p.bt_stride;
+    pg_tmask = (1 << p.bt_shift) - 1;
+    pg_kfull = (unsigned)(63 * (int)p.ksn + D);
+    pg_klast = (unsigned)(last_r * (int)p.ksn + D);
+    pg_vfull = PV_FP8 ? (unsigned)((D - 1) * (int)p.vsn + 64) : (unsigned)((63 * (int)p.vsn + D) * 2);
+    pg_vlast = PV_FP8 ? pg_vfull : (unsigned)((last_r * (int)p.vsn + D) * 2);
+  }
+  // K(j) -> K buffer `buf` (PAGED: out of page `page`)
+  auto dma_k = [&](const int j, const int buf, const int page = 0) __attribute__((always_inline)) {
+    if constexpr (PAGED) {
+      const uint64_t base = reinterpret_cast<uint64_t>(pg_k) + (uint64_t)((int64_t)page * p.ksb) +
+                            (uint64_t)(((sk_t0 + j) & pg_tmask) * k_tile_stride);
+      const v4i rs = make_rsrc_uniform(base, j == last_t ? pg_klast : pg_kfull);
+#pragma unroll
+      for (int i = 0; i < KC; ++i)
+        if (KC * T == 64 * KCH || wave * 64 + i * T < 64 * KCH)
+          lds_dma16_fresh(rs, (unsigned)(buf * KBYTES + (wave * 64 + i * T) * 16), k_voff[i], 0);
+    } else {
 #pragma unroll
     for (int i = 0; i < KC; ++i)
       if (KC * T == 64 * KCH || wave * 64 + i * T < 64 * KCH)
         lds_dma16(k_rsrc, (unsigned)(buf * KBYTES + (wave * 64 + i * T) * 16), k_voff[i], j * k_tile_stride);
+    }
   };
-  // V(j) -> V buffer `buf`
-  auto load_v = [&](const int j, const int buf) __attribute__((always_inline)) {
+  // V(j) -> V buffer `buf` (PAGED: out of page `page`)
+  auto load_v = [&](const int j, const int buf, const int page = 0) __attribute__((always_inline)) {
+    if constexpr (PAGED) {
+      const uint64_t base = reinterpret_cast<uint64_t>(pg_v) + (uint64_t)((int64_t)page * p.vsb * (PV_FP8 ? 1 : 2)) +
+                            (uint64_t)(((sk_t0 + j) & pg_tmask) * v_tile_stride);
+      const v4i rs = make_rsrc_uniform(base, j == last_t ? pg_vlast : pg_vfull);
+#pragma unroll
+      for (int i = 0; i < VC; ++i) {
+        if (!(VC * T == VROWS * VCH || wave * 64 + i * T < VROWS * VCH)) continue;
+        lds_dma16_fresh(rs, (unsigned)(RING * KBYTES + buf * VBYTES + (wave * 64 + i * T) * 16), v_voff[i], 0);
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < VC; ++i) {
       if (!(VC * T == VROWS * VCH || wave * 64 + i * T < VROWS * VCH)) continue;
       lds_dma16(v_rsrc_dma, (unsigned)(RING * KBYTES + buf * VBYTES + (wave * 64 + i * T) * 16), v_voff[i], j * v_tile_stride);
+    }
     }
   };
   // ---- lane-constant LDS read offsets
@@ -503,9 +556,16 @@
   // vmcnt where they would queue behind the tile DMA.  The lane-half select is an fma with a zeroed partner
   // (x*q + z*0 is exactly x*q) instead of two v_mov + v_cndmask per scale: SGPR operands feed the VALU directly.
   float qsc_lo = 0.f, qsc_hi = 0.f;  // = hh ? (0, qsc) : (qsc, 0), set once the Q scale is known (prologue)
-  auto load_kscales = [&](const int j) __attribute__((always_inline)) -> float4 {
+  // (PAGED: out of the scale row of page `page`, [P, Hk, tpp * (4 | 1)]: the same load at the same depth)
+  auto load_kscales = [&](const int j, const int page = 0) __attribute__((always_inline)) -> float4 {
+    if constexpr (PAGED) {
+      const float* sp = pg_ks + (int64_t)page * p.ks_b + ((sk_t0 + j) & pg_tmask) * p.ks_t;
+      if constexpr (KTHREAD) return uniform_load4(sp);
+      else return make_float4(uniform_load1(sp), 0.f, 0.f, 0.f);
+    } else {
     if constexpr (KTHREAD) return uniform_load4(ksp + j * p.ks_t);
     else return make_float4(uniform_load1(ksp + j * p.ks_t), 0.f, 0.f, 0.f);
+    }
   };
   auto scales_from = [&](const float4 kk, float& sc0, float& sc1) __attribute__((always_inline)) {
     if constexpr (KTHREAD) {
@@ -515,8 +575,8 @@
       sc0 = sc1 = qsc * kk.x;
     }
   };
-  auto tile_scales = [&](const int j, float& sc0, float& sc1) __attribute__((always_inline)) {
-    scales_from(load_kscales(j), sc0, sc1);
+  auto tile_scales = [&](const int j, float& sc0, float& sc1, const int page = 0) __attribute__((always_inline)) {
+    scales_from(load_kscales(j, page), sc0, sc1);
   };
   // which of the lane's 32 keys of tile j may be attended: bit 16*mt+e.  Sequence end, causal diagonal and the
   // caller's bool attn_mask (False = masked; the reference adds -1e6, which is the same for every row that keeps
@@ -781,6 +841,14 @@
   auto ahead = [&](const int pos) __attribute__((always_inline)) -> int {
     if constexpr (SPARSE) return tile_at(pos); else return min(pos, last_tile);
   };
+  // PAGED: the page of the tile at position `pos` of the range, the position clamped like every read-ahead (dense: nothing)
+  auto page_at = [&](const int pos) __attribute__((always_inline)) -> int {
+    if constexpr (PAGED) return uniform_load_i32(pg_row + ((sk_t0 + min(pos, last_tile)) >> p.bt_shift)); else return 0;
+  };
+  if constexpr (PAGED) {  // the pages of the first five tiles, requested together: one scalar round trip in front of the first copies
+#pragma unroll
+    for (int i = 0; i < 5; ++i) bs_first[i] = page_at(i);
+  }
   if constexpr (SPARSE) {
     if constexpr (RING == 2) {
       dma_k(bs_first[0], 0);
@@ -800,22 +868,22 @@
       dma_wait_keep<2 * NDMA>();
     }
   } else if constexpr (RING == 2) {
-    dma_k(0, 0);
-    load_v(0, 0);
-    if (ntiles > 1) dma_k(1, 1);
+    dma_k(0, 0, bs_first[0]);
+    load_v(0, 0, bs_first[0]);
+    if (ntiles > 1) dma_k(1, 1, bs_first[1]);
     prepare_q();
     dma_wait_all();
   } else {
     // K(0..3) and V(0..2), clamped to the last tile so that every wave issues the same number of copies whatever the
     // sequence length (a clamped copy re-loads the last tile into a slot nobody reads any more); only K(0), V(0), K(1)
     // are needed now, the rest keeps flying
-    dma_k(0, 0);
-    load_v(0, 0);
-    dma_k(min(1, last_tile), 1);
-    load_v(min(1, last_tile), 1);
-    dma_k(min(2, last_tile), 2);
-    load_v(min(2, last_tile), 2);
-    dma_k(min(3, last_tile), 3);
+    dma_k(0, 0, bs_first[0]);
+    load_v(0, 0, bs_first[0]);
+    dma_k(min(1, last_tile), 1, bs_first[1]);
+    load_v(min(1, last_tile), 1, bs_first[1]);
+    dma_k(min(2, last_tile), 2, bs_first[2]);
+    load_v(min(2, last_tile), 2, bs_first[2]);
+    dma_k(min(3, last_tile), 3, bs_first[3]);
     prepare_q();
     dma_wait_keep<2 * NDMA>();
   }
@@ -859,17 +927,18 @@
   // S(0) from a mix of K(0) and K(2) rows -- one wrong 32-row wave, the same wrong value every time
   // (profiles/r02_race_evidence.md).
   __syncthreads();
-  tile_scales(SPARSE ? bs_first[0] : 0, sc0, sc1);
+  tile_scales(SPARSE ? bs_first[0] : 0, sc0, sc1, bs_first[0]);
   // a plain tile 0 needs no mask (64 compare + select instructions per wave); the causal head_dim-64 variants keep it
   // unconditional -- under the branch they need 170 registers, two over the three-waves-per-SIMD line
   if (CAUSAL || n_plain <= 0) mask_limit(SPARSE ? bs_first[0] : 0, s_cur);
   mx_cur = row_max(s_cur, sc0, sc1);
 
   // fast loop, unrolled by two so that S(j) / S(j+1) swap roles without register copies
-  float4 kk_nxt = load_kscales(SPARSE ? bs_first[1] : min(1, ntiles - 1));
+  float4 kk_nxt = load_kscales(SPARSE ? bs_first[1] : min(1, ntiles - 1), bs_first[1]);
   // block-sparse: the key tiles at list positions j+1 .. j+RING, in SGPRs.  Iteration j requests the entry of position
   // j+RING+1 next to the scale load and shifts it in at its end, so the tile of every copy and of the scale load of
   // position j+2 is known a whole iteration before it is used: no scalar round trip in front of a copy or a K-fragment wait.
+  // PAGED: the same window holds the PAGES of the tiles min(j+1 .. j+RING, last_tile), requested and shifted the same way.
   int bw1 = bs_first[1], bw2 = bs_first[2], bw3 = bs_first[3], bw4 = bs_first[4];
   (void)bw1; (void)bw2; (void)bw3; (void)bw4;
   int k_slot = 0, v_slot = 0;  // slots the LDS read pointers point at (moved by the run-time-slot tiles only)
@@ -912,18 +981,19 @@
     int bw_in = RING == 2 ? bw2 : bw4;  // block-sparse: the entry that enters the window (the wave's last tile: none)
     if constexpr (NEXT != 2) {
       scales_from(kk_nxt, b0, b1);
-      kk_nxt = load_kscales(SPARSE ? bw2 : min(j + 2, ntiles - 1));
+      kk_nxt = load_kscales(SPARSE ? bw2 : min(j + 2, ntiles - 1), bw2);
       if constexpr (SPARSE) bw_in = tile_at(j + RING + 1);
+      if constexpr (PAGED) bw_in = page_at(j + RING + 1);
       kf_early = *reinterpret_cast<const v4i*>(k_rd[0] + (DYN ? 0 : K_RD * KBYTES));
     }
     __builtin_amdgcn_sched_barrier(0);
     maybe_rescale(mx_cur);
     if constexpr (RING == 2) {
-      if (j + 2 < ntiles) dma_k(SPARSE ? bw2 : j + 2, K_WR);
-      if (!DYN || j + 1 < ntiles) load_v(SPARSE ? bw1 : j + 1, V_WR);
+      if (j + 2 < ntiles) dma_k(SPARSE ? bw2 : j + 2, K_WR, bw2);
+      if (!DYN || j + 1 < ntiles) load_v(SPARSE ? bw1 : j + 1, V_WR, bw1);
     } else {
-      dma_k(SPARSE ? bw4 : min(j + RING, last_tile), K_WR);
-      load_v(SPARSE ? bw3 : min(j + RING - 1, last_tile), V_WR);
+      dma_k(SPARSE ? bw4 : min(j + RING, last_tile), K_WR, bw4);
+      load_v(SPARSE ? bw3 : min(j + RING - 1, last_tile), V_WR, bw3);
     }
     bool skip = false;
     if constexpr (PVSKIP) skip = pv_skip(j, mx_cur);
@@ -1176,7 +1246,7 @@
     // tile's wait and barrier, where a wave idles anyway: hipcc sank it below the barrier in one of the two unrolled
     // bodies, i.e. in front of the next tile's first MFMA (C3 +1.1 %)
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SPARSE) {  // the window moves on by one list position
+    if constexpr (SPARSE || PAGED) {  // the window moves on by one list position
       if constexpr (RING == 2) { bw1 = bw2; bw2 = bw_in; }
       else { bw1 = bw2; bw2 = bw3; bw3 = bw4; bw4 = bw_in; }
     }
@@ -1239,15 +1309,16 @@
     hh_l = ln >> 5;
     if constexpr (CAUSAL && SPLITKV) lim_l = max(row_l / p.q_fold + sk_off, -1);
   }
+  // (PAGED: the tail body and the staging-only iterations look their pages up where they need them: a scalar round trip each)
   // staging with run-time slots: the compiler-scheduled tail body below and, for causal waves that are done early, staging-only iterations;
   // every copy drained (vmcnt(0)) -- the four-slot ring keeps its copy COUNT per iteration constant here as well
   auto stage_generic = [&](const int jj) __attribute__((always_inline)) {
     if constexpr (RING == 2) {
-      if (jj + 2 < ntiles) dma_k(tile_at(jj + 2), jj & 1);
-      if (jj + 1 < ntiles) load_v(tile_at(jj + 1), (jj + 1) & 1);
+      if (jj + 2 < ntiles) dma_k(tile_at(jj + 2), jj & 1, page_at(jj + 2));
+      if (jj + 1 < ntiles) load_v(tile_at(jj + 1), (jj + 1) & 1, page_at(jj + 1));
     } else {
-      dma_k(ahead(jj + RING), jj % RING);
-      load_v(ahead(jj + RING - 1), (jj + RING - 1) % RING);
+      dma_k(ahead(jj + RING), jj % RING, page_at(jj + RING));
+      load_v(ahead(jj + RING - 1), (jj + RING - 1) % RING, page_at(jj + RING - 1));
     }
   };
   // The wave's remaining tiles (a successor that may need masking, then its last one).
@@ -1273,7 +1344,7 @@
       const bool has_next = j + 1 < wave_tiles;
       if (has_next) {
         const int jt = tile_at(j + 1);
-        tile_scales(jt, nsc0, nsc1);
+        tile_scales(jt, nsc0, nsc1, page_at(j + 1));
         qk((j + 1) % RING, s_nxt);
         if (j + 1 >= n_plain) mask_limit(jt, s_nxt);  // a plain last tile (N % 64 == 0, no diagonal) needs none
       }

@@ -45,11 +45,15 @@ struct AttnParams {
   // (the P.V skip of the block-sparse form -- attn_i8_blocksparse_pvskip_kernel -- keeps its two pointers in the first two
   //  mask strides: pv_thresh fp32 [Hq], pv_skipped int32 [B,Hq,nqb,4] or null)
   union { int64_t msb; const float* pv_thresh; float* sk_lse; };
-  union { int64_t msh; int32_t* pv_skipped; };
+  // (paged split-KV -- attn_i8_splitkv_paged_kernel / attn_i8_splitkv_causal_paged_kernel, include/sageattn_hip_paged.h -- keeps
+  //  its block table here: int32 [B, bt_stride], row b names the pages of batch b.  k, v and k_scale are then POOLS of pages:
+  //  ksb / vsb / ks_b are the strides of a page, N = max_pages * page_size the logical capacity)
+  union { int64_t msh; int32_t* pv_skipped; const int32_t* block_table; };
   // (causal split-KV -- attn_i8_splitkv_causal_kernel, sage_attn_splitkv_causal.hip -- keeps its fold g >= 1 in the third mask
   //  stride: query row r is token r / g, and the diagonal counts tokens)
   union { int64_t msm; int q_fold; };
-  int64_t msn;
+  // (paged split-KV: the table's row stride in entries, in the word of the fourth mask stride)
+  union { int64_t msn; int bt_stride; };
   union { int mask_kind; int bs_row; int num_splits; };
   // KV tile layout (sage_kv_layout, include/sageattn_hip.h): byte distance between consecutive 64-key tiles of one
   // (b, h_kv) in k8 and in v (always set by attn_check; the dense defaults are 64 rows), and the strides of k_scale
@@ -58,7 +62,8 @@ struct AttnParams {
   int k_tile_bytes, v_tile_bytes;
   int64_t ks_b, ks_h;
   int ks_t;
-  int kv_tiled;  // non-default tile strides
+  // non-default tile strides (read by the host only; paged split-KV: log2 of the 64-key tiles per page, 0 .. 2)
+  union { int kv_tiled; int bt_shift; };
   int o_vec16;   // every output row starts on a 16-byte boundary (all strides multiples of 8 elements): 16-byte stores
 };
 
@@ -121,6 +126,22 @@ __device__ __forceinline__ void lds_dma16(v4i rsrc, unsigned lds_off, int voffse
       : "memory", "m0");
 #endif
 }
+// The same copy for a descriptor (or soffset) that was computed just in front of it -- the per-tile descriptors of the paged
+// split-KV kernels.  Nothing inside an asm string is padded by the compiler: a buffer instruction that reads an SGPR written by
+// a v_readfirstlane needs 5 wait states behind the write, and whether hipcc forms a descriptor word on the scalar ALU (no
+// hazard) or moves it over from a VGPR is its choice per instantiation.  `s_nop 4` behind the M0 move gives 5 states (the move
+// is a sixth), which covers that case and the one state M0 itself needs, whatever produced the operands.
+__device__ __forceinline__ void lds_dma16_fresh(v4i rsrc, unsigned lds_off, int voffset, int soffset) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile(
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 4\n\t"
+      "buffer_load_dwordx4 %0, %1, %3 offen lds"
+      :
+      : "v"(voffset), "s"(rsrc), "s"(lds_off), "s"(soffset)
+      : "memory", "m0");
+#endif
+}
 // counted form: wait until at most N of the wave's vector-memory operations are outstanding (they complete in order)
 template <int N>
 __device__ __forceinline__ void dma_wait_keep() {
@@ -168,6 +189,17 @@ __device__ __forceinline__ float uniform_load1(const float* ptr) {
 #else
   return 0.f;
 #endif
+}
+
+// raw buffer descriptor from values that ARE wave-uniform by construction (kernel arguments, workgroup ids, scalar loads):
+// no readfirstlane, the words stay on the scalar unit
+__device__ __forceinline__ v4i make_rsrc_uniform(const uint64_t a, const unsigned num_bytes) {
+  v4i r;
+  r[0] = (int)(a & 0xffffffffu);
+  r[1] = (int)((a >> 32) & 0xffffu);
+  r[2] = (int)num_bytes;
+  r[3] = 0x00020000;
+  return r;
 }
 
 template <int D>

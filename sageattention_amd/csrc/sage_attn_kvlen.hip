@@ -18,7 +18,7 @@ template <int D, int NWAVES, bool CAUSAL, bool KTHREAD, bool V_BF16, bool PV_FP8
 // (register budget as attn_i8_kernel: head_dim 64 FP8 PV with 4 waves is held to three waves per SIMD)
 __global__ __launch_bounds__(NWAVES * 64, (D == 64 && PV_FP8 && NWAVES == 4) ? 3 : 2)
 void attn_i8_kvlen_kernel(const AttnParams p) {
-  constexpr bool HAS_MASK = false, SPARSE = false, PVSKIP = false, KVLEN = true, SPLITKV = false;
+  constexpr bool HAS_MASK = false, SPARSE = false, PVSKIP = false, KVLEN = true, SPLITKV = false, PAGED = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL

@@ -1,6 +1,7 @@
 // The launch of a 4-wave attention kernel without attn_mask, written once for the block-sparse kernels (sage_attn.hip,
 // sage_attn_pvskip.hip, sage_attn_sparse_kvlen.hip, sage_attn_sparse_kvlen_pvskip.hip) and the split-KV kernels
-// (sage_attn_splitkv.hip, sage_attn_splitkv_causal.hip).  Each file instantiates its own kernel: it passes a generic callable
+// (sage_attn_splitkv.hip, sage_attn_splitkv_causal.hip and their paged twins sage_attn_splitkv_paged.hip,
+// sage_attn_splitkv_causal_paged.hip).  Each file instantiates its own kernel: it passes a generic callable
 // that returns the kernel for (D, KTHREAD, V_BF16, PV_FP8), given as std::integral_constant / std::bool_constant values.
 #pragma once
 #include "sage_entry.h"

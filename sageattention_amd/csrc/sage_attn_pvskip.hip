@@ -23,7 +23,7 @@ template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(256, (D == 64 && PV_FP8) ? 3 : 2)
 void attn_i8_blocksparse_pvskip_kernel(const AttnParams p) {
   constexpr int NWAVES = 4;
-  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = true, KVLEN = false, SPLITKV = false;
+  constexpr bool CAUSAL = false, HAS_MASK = false, SPARSE = true, PVSKIP = true, KVLEN = false, SPLITKV = false, PAGED = false;
 #define SAGE_ATTN_BODY_OF_KERNEL
 #include "sage_attn_body.h"
 #undef SAGE_ATTN_BODY_OF_KERNEL

@@ -145,6 +145,14 @@ struct AttnArgs {
   // positions of the batch's keys; q_fold < 1 or M % q_fold != 0: SAGE_ERR_INVALID_ARGUMENT
   bool split_causal = false;
   int q_fold = 1;
+  // ... paged (sage_attn_fusedq_pv_*_splitkv_paged, include/sageattn_hip_paged.h; with split_kv only, else
+  // SAGE_ERR_UNSUPPORTED): k8, v and k_scale are pools of pages -- stride_b of k8 and v is the stride of a page -- and row b of
+  // block_table (int32, table_stride entries per row) names the pages of batch b; page_size is 64, 128 or 256 keys and N the
+  // logical capacity max_pages * page_size.  The entry point checks the table's own arguments; here the 32-bit window is that
+  // of one (page, head) slice and the K scales are laid out per page
+  bool paged = false;
+  const int32_t* block_table = nullptr;
+  int table_stride = 0, page_size = 0;
 };
 
 // one launch of attn_i8_kernel: its parameters and the template arguments they select
@@ -158,6 +166,7 @@ struct AttnCall {
   bool sparse_kvlen;  // attn_i8_blocksparse_kvlen_kernel / ..._pvskip_kvlen_kernel: sparse (and pvskip) with key lengths
   bool splitkv;  // attn_i8_splitkv_kernel + splitkv_merge_kernel (always 4 waves)
   bool splitkv_causal;  // ... attn_i8_splitkv_causal_kernel + splitkv_merge_kernel<.., CAUSAL = true>, with splitkv
+  bool paged;  // ... attn_i8_splitkv_paged_kernel / attn_i8_splitkv_causal_paged_kernel in the place of the two, with splitkv
 };
 int attn_check(AttnCall& c, const AttnArgs& a);
 int attn_launch(const AttnCall& c, hipStream_t st);
@@ -175,6 +184,10 @@ int launch_blocksparse_pvskip_kvlen(const AttnCall& c, hipStream_t st);
 int launch_splitkv_attn(const AttnCall& c, hipStream_t st);
 int launch_splitkv_causal_attn(const AttnCall& c, hipStream_t st);
 int launch_splitkv_merge(const AttnCall& c, hipStream_t st);
+// ... of a paged split-KV call (c.paged; sage_attn_splitkv_paged.hip / sage_attn_splitkv_causal_paged.hip): the attention
+// kernel in the place of the two above, then the same merge
+int launch_splitkv_paged_attn(const AttnCall& c, hipStream_t st);
+int launch_splitkv_causal_paged_attn(const AttnCall& c, hipStream_t st);
 // bytes of the workspace of a split-KV call: the partial outputs fp32 [S,B,Hq,M,D], then their base-2 LSEs fp32 [S,B,Hq,M]
 inline int64_t splitkv_bytes(int B, int Hq, int M, int D, int S) {
   return (int64_t)S * B * Hq * M * ((int64_t)D + 1) * 4;

@@ -16,7 +16,9 @@
 // (profiles/k_quant_valu_diet.md: the instruction census and the in-step traces).
 // Compiled with -ffp-contract=off: the integer outputs must match the oracle bit for bit.
 #include <algorithm>
+#include <climits>
 #include "../../include/sageattn_hip_kvcache.h"
+#include "../../include/sageattn_hip_paged.h"
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
 
@@ -852,6 +854,51 @@ __device__ __forceinline__ void kv_append_k_tile(const QuantParams& p, const int
   else k_quant_block<D, BF16, TRITON, PER_THREAD, true>(p, blk, h, b, raw, mbits, gmax[0], gmax[1], [] {});
 }
 
+// The block table of the paged form (include/sageattn_hip_paged.h): row b, `stride` int32 entries, names the pages of batch b;
+// a page holds 1 << shift tiles.  The K, V, INT8 K, scale and V^T pointers of KvAppendParams are then POOLS whose batch strides
+// (xsb, osb, ss_b; sb, ob) are the strides of a page, and k.N the logical capacity max_pages * page_size.
+struct KvPageTable {
+  const int32_t* table;
+  int64_t stride;
+  int shift;
+};
+// the page of logical tile `blk` of batch b: only tiles below ceil(len_b / 64) are asked for, so no entry at or beyond
+// ceil(len_b / page_size) is read
+__device__ __forceinline__ int64_t kv_page_of(const KvPageTable& pt, const int b, const int blk) {
+  return pt.table[(int64_t)b * pt.stride + (blk >> pt.shift)];
+}
+
+// V unit of the paged form: v_quant_transpose_body with the rows and the image blocks looked up per 64-token block.  At
+// head_dim 64 a unit is two blocks, which with 64-key pages lie in two pages: the two halves of the workgroup look up their
+// own.  A row index clamped to len - 1 (the loads are unconditional, as in v_quant_load) lies in block min(blk, ntile - 1): a
+// block the batch has, whose page is named.
+template <int D, bool BF16>
+__device__ __forceinline__ void kv_append_v_unit_paged(const VPrepParams& q, const KvPageTable& pt, const int len,
+                                                       const float (&mean)[8], const float (&rcp)[8], const int unit,
+                                                       const int h, const int b, uint32_t* __restrict__ tile) {
+  using G = VQuantGeom<D>;
+  const int tmask = (1 << pt.shift) - 1, ntile = (len + 63) >> 6;
+  uint4 raw[4];
+  {
+    const int tg = threadIdx.x / G::TPR, tc = threadIdx.x % G::TPR;
+    const int blk = unit * G::BLKS + tg / 16, blk_c = min(blk, ntile - 1);
+    const uint16_t* vbase = q.v + kv_page_of(pt, b, blk_c) * q.sb + h * q.sh + (int64_t)((blk_c & tmask) * 64) * q.sn + tc * 8;
+    const int row0 = blk * 64 + 4 * (tg % 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) raw[i] = *reinterpret_cast<const uint4*>(vbase + (int64_t)(min(row0 + i, len - 1) & 63) * q.sn);
+  }
+  v_quant_to_image<D, BF16, true>(raw, len, unit, mean, rcp, tile);
+  __syncthreads();
+  for (int c = threadIdx.x; c < G::BLKS * D * 4; c += 256) {
+    const int bo = c / (D * 4), cc = c % (D * 4), d = cc >> 2, ch = cc & 3;
+    const int ob_blk = unit * G::BLKS + bo;
+    if (ob_blk * 64 >= len) continue;
+    const uint4 u = *reinterpret_cast<const uint4*>(&tile[bo * G::IMG + d * 16 + 4 * (d >> 3) + ch * 4]);
+    *reinterpret_cast<uint4*>(q.out + kv_page_of(pt, b, ob_blk) * q.ob + h * q.oh + (int64_t)d * q.od + (ob_blk & tmask) * q.o_tile +
+                              ch * 16) = u;
+  }
+}
+
 template <int D, bool BF16, bool TRITON, bool WITH_V>
 __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_kernel(const KvAppendParams a) {
   using G = VQuantGeom<D>;
@@ -883,6 +930,49 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_kernel(c
     }
     v_quant_transpose_body<D, BF16, true>(a.v.v, a.v.sb, a.v.sh, a.v.sn, len, mean, rcp, a.v.out, a.v.ob, a.v.oh, a.v.od, a.v.o_tile,
                                     unit, h, b, tile);
+  }
+}
+
+// The paged form (sage_kv_cache_append_paged): the same grid, the same slots in logical tiles, the same K block and V unit
+// bodies.  A K slot moves its pointers to the page of its tile -- after that, tile `blk` of batch b IS the tile of the page,
+// and kv_append_k_tile runs unchanged (km stays that of batch b); a V slot runs kv_append_v_unit_paged.
+// (A kernel text of its own: with the slot arithmetic shared through one function template and a PAGED flag, the 16
+//  instantiations of kv_cache_append_kernel came out with other instruction streams, 2 to 105 instructions shorter.)
+template <int D, bool BF16, bool TRITON, bool WITH_V>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_paged_kernel(const KvAppendParams a, const KvPageTable pt) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[2][64];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[WITH_V ? G::BLKS * G::IMG : 4];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const int len = kv_len_of(a.kv_lens, b, a.k.N);
+  if (len == 0) return;
+  const int t0 = min(kv_len_of(a.start_lens, b, a.k.N), len - 1) >> 6;
+  const int ntile = (len + 63) >> 6;
+  if ((int)blockIdx.x < a.k_slots) {
+    const int blk = t0 + blockIdx.x;
+    if (blk >= ntile) return;
+    QuantParams p = a.k;
+    p.N = len;
+    const int64_t page = kv_page_of(pt, b, blk);
+    const int64_t back = (blk & ((1 << pt.shift) - 1)) - blk;  // tile inside the page - logical tile (<= 0)
+    p.x += page * p.xsb + back * 64 * p.xsn - b * p.xsb;
+    p.out += page * p.osb + back * p.o_blk - b * p.osb;
+    p.scale += page * p.ss_b + back * p.ss_blk - b * p.ss_b;
+    if (p.gran == SAGE_GRAN_PER_THREAD) kv_append_k_tile<D, BF16, TRITON, true>(p, blk, h, b, H, gmax);
+    else kv_append_k_tile<D, BF16, TRITON, false>(p, blk, h, b, H, gmax);
+    return;
+  }
+  if constexpr (WITH_V) {
+    const int unit = t0 / G::BLKS + ((int)blockIdx.x - a.k_slots);
+    if (unit * G::BLKS >= ntile) return;
+    const int tc = threadIdx.x % G::TPR;
+    float mean[8], rcp[8];
+    {
+      const float* cf = a.v_coef + (((int64_t)b * H + h) * 2) * D + tc * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { mean[j] = cf[j]; rcp[j] = cf[D + j]; }
+    }
+    kv_append_v_unit_paged<D, BF16>(a.v, pt, len, mean, rcp, unit, h, b, tile);
   }
 }
 
@@ -1239,17 +1329,21 @@ extern "C" int sage_kv_prepare_fp8_kvlen(const sage_tensor* k, const sage_tensor
 }
 
 // ---- persistent KV cache (include/sageattn_hip_kvcache.h): every check, the slots of the grid, one launch
-extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
-                                    const void* km, const sage_tensor* k_int8, float* k_scale, int gran, int rounding,
-                                    const sage_tensor* v_fp8, const float* v_coef, const int32_t* start_lens,
-                                    const int32_t* kv_lens, int max_new, sage_stream_t stream) {
+// (both forms; pt: the block table of sage_kv_cache_append_paged, else null.  Paged: k, v, k_int8, k_scale and v_fp8 are the
+//  pools, P their page count, N the logical capacity; the quantizer's parameters are those of one page of page_size rows)
+static int kv_cache_append(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D, const void* km,
+                           const sage_tensor* k_int8, float* k_scale, int gran, int rounding, const sage_tensor* v_fp8,
+                           const float* v_coef, const int32_t* start_lens, const int32_t* kv_lens, int max_new,
+                           const KvPageTable* pt, int P, sage_stream_t stream) {
   if (!km || !aligned16(km) || !kv_lens_ok(start_lens) || !kv_lens_ok(kv_lens) || max_new < 1) return SAGE_ERR_INVALID_ARGUMENT;
   if (v_fp8 && (!v_coef || !aligned16(v_coef) || !tensor_ok(v, 8) || !tensor_ok(v_fp8, 16))) return SAGE_ERR_INVALID_ARGUMENT;
   if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
+  if (B <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
   QuantCall c;
-  if (const int s = quant_check(c, k, dtype, B, H, N, D, km, k_int8, k_scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1,
-                                nullptr))
+  if (const int s = quant_check(c, k, dtype, pt ? P : B, H, pt ? 64 << pt->shift : N, D, km, k_int8, k_scale, gran, 1, 64, 64,
+                                1.0f, rounding, nullptr, 1, nullptr))
     return s;
+  c.p.N = N;
   KvAppendParams a;
   a.k = c.p;
   a.v = VPrepParams();
@@ -1272,6 +1366,11 @@ extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, 
     by_flag(c.bf16, [&](auto bf) {
       by_flag(rounding == SAGE_ROUND_TRITON, [&](auto tr) {
         by_flag(v_fp8 != nullptr, [&](auto wv) {
+          if (pt)
+            hipLaunchKernelGGL((kv_cache_append_paged_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value,
+                                                             decltype(wv)::value>),
+                               dim3(k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a, *pt);
+          else
           hipLaunchKernelGGL((kv_cache_append_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value,
                                                      decltype(wv)::value>),
                              dim3(k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a);
@@ -1280,4 +1379,30 @@ extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, 
     });
   });
   return launch_status();
+}
+
+extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                                    const void* km, const sage_tensor* k_int8, float* k_scale, int gran, int rounding,
+                                    const sage_tensor* v_fp8, const float* v_coef, const int32_t* start_lens,
+                                    const int32_t* kv_lens, int max_new, sage_stream_t stream) {
+  return kv_cache_append(k, v, dtype, B, H, N, D, km, k_int8, k_scale, gran, rounding, v_fp8, v_coef, start_lens, kv_lens,
+                         max_new, nullptr, 0, stream);
+}
+
+// ---- paged KV cache (include/sageattn_hip_paged.h): the table's own arguments, then the checks and the launch above
+extern "C" int sage_kv_cache_append_paged(const sage_tensor* k_pool, const sage_tensor* v_pool, int dtype, int B, int H, int D,
+                                          const void* km, const sage_tensor* k8_pool, float* k_scale_pool, int gran,
+                                          int rounding, const sage_tensor* v8_pool, const float* v_coef,
+                                          const int32_t* block_table, int64_t table_stride, int max_pages, int page_size,
+                                          int num_pages, const int32_t* start_lens, const int32_t* kv_lens, int max_new,
+                                          sage_stream_t stream) {
+  if (page_size != 64 && page_size != 128 && page_size != 256) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!kv_lens_ok(block_table) || max_pages < 1 || num_pages < 1 || table_stride < max_pages) return SAGE_ERR_INVALID_ARGUMENT;
+  if ((int64_t)max_pages * page_size > INT_MAX) return SAGE_ERR_TOO_LARGE;
+  KvPageTable pt;
+  pt.table = block_table;
+  pt.stride = table_stride;
+  pt.shift = page_size == 64 ? 0 : page_size == 128 ? 1 : 2;
+  return kv_cache_append(k_pool, v_pool, dtype, B, H, max_pages * page_size, D, km, k8_pool, k_scale_pool, gran, rounding,
+                         v8_pool, v_coef, start_lens, kv_lens, max_new, &pt, num_pages, stream);
 }

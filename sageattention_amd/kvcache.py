@@ -10,8 +10,8 @@ and ``attn_splitkv_cached[_lse]`` / ``attn_splitkv_causal_cached[_lse]``; everyt
 ``torch.compile(fullgraph=True)`` and captures into a HIP graph (lengths are read on the device only).
 
 Not built: dropping the caller's fp16 K buffer (the ragged tile is quantized again from its fp16 rows; without them the cache
-needs a 64-row fp16 tail per head and a sequential walk), paged / block-table caches, moving the frozen mean or V scale
-without preparing again, V smoothing and ``smooth_k=False``."""
+needs a 64-row fp16 tail per head and a sequential walk), moving the frozen mean or V scale without preparing again, V
+smoothing and ``smooth_k=False``.  Paged / block-table caches: ``SagePagedKVCache`` (paged.py)."""
 from typing import Any, Optional
 
 import torch
