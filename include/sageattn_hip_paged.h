@@ -57,8 +57,10 @@
  *  - the valid pages of different batches are distinct: km and the V scale are per sequence;
  *  - the rows < start_b are unchanged since they were quantized; len_b - min(start_b, len_b) <= max_new.
  *
- * NOT BUILT: page sizes below 64 (a 16-key page cannot hold a scale group); dropping the fp16 K pool; paged forms of the
- * dense, kvlen and block-sparse operators; moving frozen statistics without preparing again; pages shared between sequences
+ * A cache that owns every pool and keeps no fp16 K pool: sageattn_hip_paged_rows.h.
+ *
+ * NOT BUILT: page sizes below 64 (a 16-key page cannot hold a scale group); paged forms of the dense, kvlen and block-sparse
+ * operators; moving frozen statistics without preparing again; pages shared between sequences
  * (prefix sharing needs frozen statistics shared by the sequences that use the page).
  */
 #ifndef SAGEATTN_HIP_PAGED_H

@@ -59,6 +59,17 @@ def _check_no_scratch(src, compiler_output):
             raise RuntimeError(f"{src}: kernel {name} uses {m.group(1)} bytes/lane of scratch (register spill)")
 
 
+def _check_rows_kernels(src, compiler_output):
+    """kv_cache_append_rows_paged_kernel (sage_quant.hip): all 16 instantiations -- head_dim x dtype x rounding x V mode -- must
+    have come through the compiler's resource report, so that _check_no_scratch has seen every one of them."""
+    import re
+    if src != "sage_quant.hip":
+        return
+    seen = set(re.findall(r"Function Name: (\S*kv_cache_append_rows_paged_kernel\S*)", compiler_output))
+    if len(seen) != 16:
+        raise RuntimeError(f"{src}: {len(seen)} instantiations of kv_cache_append_rows_paged_kernel in the resource report, not 16")
+
+
 def _check_occupancy(src, compiler_output):
     """The head_dim-64 kernels in their dispatched geometry (4 waves, no attn_mask) are tuned for THREE waves per SIMD
     (<= 168 VGPRs); hipcc's allocation sits within a few registers of that line and an innocent-looking source change can
@@ -148,6 +159,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_kvcache.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged_rows.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -171,6 +183,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
         try:
             _check_no_scratch(src, out)
+            _check_rows_kernels(src, out)
             _check_occupancy(src, out)
         except RuntimeError:
             os.remove(o)  # never link (or cache) a spilling object

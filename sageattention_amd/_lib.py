@@ -143,12 +143,18 @@ PAGED_SIGNATURES = {
     "sage_attn_fusedq_pv_f8_splitkv_paged": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _PAGED_TAIL),
 }
 
+# include/sageattn_hip_paged_rows.h: k_new v_new dtype | B H T D | km k_tail k8_pool k_scale_pool gran rounding | v_pool v8_pool
+# v_coef | table | start_lens kv_lens stream
+PAGED_ROWS_SIGNATURES = {
+    "sage_kv_cache_append_rows_paged": (_I, [_P, _P, _I, _I, _I, _I, _I, _V, _V, _P, _V, _I, _I, _P, _P, _V] + _TABLE + [_V, _V, _V]),
+}
+
 
 def bind(cdll, missing_ok=True):
-    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES and PAGED_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES and PAGED_ROWS_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
-    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

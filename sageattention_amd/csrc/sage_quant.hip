@@ -19,6 +19,7 @@
 #include <climits>
 #include "../../include/sageattn_hip_kvcache.h"
 #include "../../include/sageattn_hip_paged.h"
+#include "../../include/sageattn_hip_paged_rows.h"
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
 
@@ -977,6 +978,163 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_paged_ke
 }
 
 // ------------------------------------------------------------------------------------------------
+// The paged cache without fp16 pools (include/sageattn_hip_paged_rows.h, sage_kv_cache_append_rows_paged): the same grid and
+// the same slots in logical tiles as kv_cache_append_paged_kernel, but the rows come from the step's k_new / v_new [B,H,T,D]
+// (logical row s_b + i is row i) and, for the rows of tile t0_b below min(s_b, len_b), from the ring k_tail [B,H,2,64,D] (row
+// r in slot (r >> 6) & 1, row r & 63).  Rows of k_new / v_new at i >= n_b = min(len_b - s_b, T) are never loaded: every row
+// index is clamped into [0, n_b), and a unit without new rows loads none.
+//
+// THE RING HAS ONE READER AND ONE WRITER: K slot 0 of (b, h).  Only tile t0_b has rows below s_b (a later tile starts at
+// 64 * (t0_b + 1) > s_b, and with s_b >= len_b there is no later tile), so only slot 0 reads the ring; the same workgroup
+// writes the new rows of the tiles tl_b and tl_b - 1 into it AFTER it has quantized its tile.  With a chunk of more than 64
+// rows tl_b can have the parity of t0_b, and the rows written are then the rows read -- which is why no other workgroup
+// writes them: nothing orders workgroups.  Inside the workgroup the order holds because every thread's ring rows feed the
+// group maxima it publishes (atomicMax into LDS) in front of the barrier of k_quant_block -- a load has returned before its
+// value is used -- so behind that barrier (and the one in front of the ring's stores) every ring row of the workgroup sits
+// in registers.
+// V_MODE 1 (FP8 P.V): the V unit quantizes the new rows into the LDS image with v_quant_to_image<.., SAT = true>, zeros for
+// the columns >= len_b, and stores it 16 bytes at a time; a chunk with tokens below min(s_b, len_b) -- four consecutive tokens
+// share a dword, in the image's permuted order -- takes those BYTES from the chunk the pool holds, and a chunk of old tokens
+// alone is not stored.  V_MODE 0 (FP16 / BF16 P.V): the rows [s_b, len_b) of v_new are copied into the pages of v_pool.
+// ------------------------------------------------------------------------------------------------
+struct KvRowsParams {
+  const uint16_t* k_new;  // [B,H,T,D], strides in elements
+  int64_t ksb, ksh, ksn;
+  const uint16_t* v_new;
+  int64_t vsb, vsh, vsn;
+  uint16_t* k_tail;       // [B,H,2,64,D] contiguous
+  uint16_t* v_pool;       // V_MODE 0: [P,H,page_size,D]
+  int64_t vpb, vph, vpn;
+  int T;
+};
+
+// the 64 rows of tile `blk`: rows below `keep` out of the ring slot of the tile, the others out of k_new (row - s); rows past
+// the end read row len - 1, as k_load_rows<CLAMP> (the caller ignores them).  A row at or above keep has 0 <= row - s < n.
+template <int D>
+__device__ __forceinline__ void k_load_rows_ring(const uint16_t* knew, const int64_t ksn, const uint16_t* ring_slot, const int blk,
+                                                 const int keep, const int s, const int n, const int len,
+                                                 uint4 (&raw)[QuantGeom<D, 64>::NP]) {
+  using G = QuantGeom<D, 64>;
+  const int row0 = blk * 64 + (int)threadIdx.x / G::TPR;
+#pragma unroll
+  for (int i = 0; i < G::NP; ++i) {
+    const int row = min(row0 + i * G::RPP, len - 1);
+    const uint16_t* src = row < keep ? ring_slot + (row & 63) * D : knew + (int64_t)max(min(row - s, n - 1), 0) * ksn;
+    raw[i] = *reinterpret_cast<const uint4*>(src);
+  }
+}
+
+template <int D, bool BF16, bool TRITON, bool PER_THREAD>
+__device__ __forceinline__ void kv_rows_k_tile(const QuantParams& p, const uint16_t* knew, const int64_t ksn,
+                                               const uint16_t* ring_slot, const int blk, const int keep, const int s, const int n,
+                                               const int h, const int b, const int H, unsigned int (*gmax)[64]) {
+  using G = QuantGeom<D, 64>;
+  if (threadIdx.x < 64) gmax[0][threadIdx.x] = 0u;
+  const int tc = (int)threadIdx.x % G::TPR;
+  uint4 raw[G::NP];
+  k_load_rows_ring<D>(knew + tc * 8, ksn, ring_slot + tc * 8, blk, keep, s, n, p.N, raw);
+  const uint4 mbits = *reinterpret_cast<const uint4*>(p.mean + ((int64_t)b * H + h) * D + tc * 8);
+  __syncthreads();  // gmax zeroed
+  if (blk < p.N / 64) k_quant_block<D, BF16, TRITON, PER_THREAD, false>(p, blk, h, b, raw, mbits, gmax[0], gmax[1], [] {});
+  else k_quant_block<D, BF16, TRITON, PER_THREAD, true>(p, blk, h, b, raw, mbits, gmax[0], gmax[1], [] {});
+}
+
+template <int D, bool BF16, bool TRITON, int V_MODE>
+__global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_rows_paged_kernel(const KvAppendParams a, const KvPageTable pt,
+                                                                                          const KvRowsParams r) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[2][64];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[V_MODE == 1 ? G::BLKS * G::IMG : 4];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const int len = kv_len_of(a.kv_lens, b, a.k.N);
+  if (len == 0) return;
+  const int s = kv_len_of(a.start_lens, b, a.k.N);
+  const int keep = min(s, len);                // rows below are the cache's own
+  const int n = min(max(len - s, 0), r.T);     // rows of k_new / v_new that may be loaded
+  const int t0 = min(s, len - 1) >> 6;
+  const int ntile = (len + 63) >> 6;
+  const int tmask = (1 << pt.shift) - 1;
+  if ((int)blockIdx.x < a.k_slots) {
+    const int blk = t0 + blockIdx.x;
+    if (blk >= ntile) return;
+    QuantParams p = a.k;
+    p.N = len;
+    const int64_t page = kv_page_of(pt, b, blk);
+    const int64_t back = (blk & tmask) - blk;  // tile inside the page - logical tile (<= 0)
+    p.out += page * p.osb + back * p.o_blk - b * p.osb;
+    p.scale += page * p.ss_b + back * p.ss_blk - b * p.ss_b;
+    const uint16_t* knew = r.k_new + b * r.ksb + h * r.ksh;
+    uint16_t* ring = r.k_tail + ((int64_t)b * H + h) * (2 * 64 * D);
+    const int keep_here = blockIdx.x == 0 ? keep : 0;  // slot 0 alone reads the ring
+    if (p.gran == SAGE_GRAN_PER_THREAD)
+      kv_rows_k_tile<D, BF16, TRITON, true>(p, knew, r.ksn, ring + (blk & 1) * 64 * D, blk, keep_here, s, n, h, b, H, gmax);
+    else
+      kv_rows_k_tile<D, BF16, TRITON, false>(p, knew, r.ksn, ring + (blk & 1) * 64 * D, blk, keep_here, s, n, h, b, H, gmax);
+    if (blockIdx.x != 0) return;
+    // ... and alone writes it: the rows of [s, len) that lie in the tiles tl - 1 and tl (at most 128)
+    __syncthreads();
+    const int lo = max(s, 64 * (ntile - 2));
+    const int cnt = (len - lo) * (D / 8);  // <= 0: no new rows
+    for (int c = threadIdx.x; c < cnt; c += 256) {
+      const int row = lo + c / (D / 8), col = (c % (D / 8)) * 8;
+      const uint4 u = *reinterpret_cast<const uint4*>(knew + (int64_t)min(row - s, n - 1) * r.ksn + col);
+      *reinterpret_cast<uint4*>(ring + (row & 127) * D + col) = u;
+    }
+    return;
+  }
+  const int unit = t0 / G::BLKS + ((int)blockIdx.x - a.k_slots);
+  if (unit * G::BLKS >= ntile || (n == 0 && V_MODE == 0)) return;
+  const int tg = threadIdx.x / G::TPR, tc = threadIdx.x % G::TPR;
+  const int blk = unit * G::BLKS + tg / 16, row0 = blk * 64 + 4 * (tg % 16);
+  const uint16_t* vnew = r.v_new + b * r.vsb + h * r.vsh + tc * 8;
+  if constexpr (V_MODE == 0) {
+    if (row0 >= len || row0 + 4 <= s) return;
+    uint16_t* dst = r.v_pool + kv_page_of(pt, b, blk) * r.vpb + h * r.vph + (int64_t)((blk & tmask) * 64) * r.vpn + tc * 8;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = row0 + i;
+      if (row >= s && row < len && row - s < n)
+        *reinterpret_cast<uint4*>(dst + (int64_t)(row & 63) * r.vpn) = *reinterpret_cast<const uint4*>(vnew + (int64_t)(row - s) * r.vsn);
+    }
+  } else {
+    float mean[8], rcp[8];
+    {
+      const float* cf = a.v_coef + (((int64_t)b * H + h) * 2) * D + tc * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { mean[j] = cf[j]; rcp[j] = cf[D + j]; }
+    }
+    uint4 raw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      raw[i] = make_uint4(0u, 0u, 0u, 0u);  // (rows below keep are replaced by the pool's bytes, rows >= len become zeros)
+      if (n > 0) raw[i] = *reinterpret_cast<const uint4*>(vnew + (int64_t)max(min(row0 + i - s, n - 1), 0) * r.vsn);
+    }
+    v_quant_to_image<D, BF16, true>(raw, len, unit, mean, rcp, tile);
+    __syncthreads();
+    for (int c = threadIdx.x; c < G::BLKS * D * 4; c += 256) {
+      const int bo = c / (D * 4), cc = c % (D * 4), d = cc >> 2, ch = cc & 3;
+      const int ob_blk = unit * G::BLKS + bo;
+      if (ob_blk * 64 >= len) continue;
+      // dword k of chunk ch holds the tokens tok0 + 8 k .. + 3 of the block, byte i token + i (v_quant_to_image)
+      const int old0 = keep - (ob_blk * 64 + 32 * (ch & 1) + 4 * (ch >> 1));  // old tokens of dword k: clamp(old0 - 8 k, 0, 4)
+      if (old0 >= 28) continue;                                                // a chunk of old tokens alone
+      uint4 u = *reinterpret_cast<const uint4*>(&tile[bo * G::IMG + d * 16 + 4 * (d >> 3) + ch * 4]);
+      uint8_t* dst = a.v.out + kv_page_of(pt, b, ob_blk) * a.v.ob + h * a.v.oh + (int64_t)d * a.v.od + (ob_blk & tmask) * a.v.o_tile + ch * 16;
+      if (old0 > 0) {
+        const uint4 o = *reinterpret_cast<const uint4*>(dst);
+        const auto mix = [&](uint32_t nw, uint32_t ol, int k) {
+          const int no = min(max(old0 - 8 * k, 0), 4);
+          const uint32_t m = no >= 4 ? 0xffffffffu : (1u << (8 * no)) - 1u;
+          return (ol & m) | (nw & ~m);
+        };
+        u = make_uint4(mix(u.x, o.x, 0), mix(u.y, o.y, 1), mix(u.z, o.z, 2), mix(u.w, o.w, 3));
+      }
+      *reinterpret_cast<uint4*>(dst) = u;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: sub_mean_f16
 // ------------------------------------------------------------------------------------------------
 template <bool BF16>
@@ -1405,4 +1563,72 @@ extern "C" int sage_kv_cache_append_paged(const sage_tensor* k_pool, const sage_
   pt.shift = page_size == 64 ? 0 : page_size == 128 ? 1 : 2;
   return kv_cache_append(k_pool, v_pool, dtype, B, H, max_pages * page_size, D, km, k8_pool, k_scale_pool, gran, rounding,
                          v8_pool, v_coef, start_lens, kv_lens, max_new, &pt, num_pages, stream);
+}
+
+// ---- paged KV cache without fp16 pools (include/sageattn_hip_paged_rows.h): every check, then one launch
+extern "C" int sage_kv_cache_append_rows_paged(const sage_tensor* k_new, const sage_tensor* v_new, int dtype, int B, int H, int T,
+                                               int D, const void* km, void* k_tail, const sage_tensor* k8_pool,
+                                               float* k_scale_pool, int gran, int rounding, const sage_tensor* v_pool,
+                                               const sage_tensor* v8_pool, const float* v_coef, const int32_t* block_table,
+                                               int64_t table_stride, int max_pages, int page_size, int num_pages,
+                                               const int32_t* start_lens, const int32_t* kv_lens, sage_stream_t stream) {
+  if (page_size != 64 && page_size != 128 && page_size != 256) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!kv_lens_ok(block_table) || max_pages < 1 || num_pages < 1 || table_stride < max_pages) return SAGE_ERR_INVALID_ARGUMENT;
+  if ((int64_t)max_pages * page_size > INT_MAX) return SAGE_ERR_TOO_LARGE;
+  if (!km || !aligned16(km) || !kv_lens_ok(start_lens) || !kv_lens_ok(kv_lens) || T < 1) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!k_tail || !aligned16(k_tail) || (v_pool != nullptr) == (v8_pool != nullptr)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v_new, 8) || (v_pool && !tensor_ok(v_pool, 8))) return SAGE_ERR_INVALID_ARGUMENT;
+  if (v8_pool && (!v_coef || !aligned16(v_coef) || !tensor_ok(v8_pool, 16))) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
+  if (B <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  QuantCall c;  // (x = k_new stands for the rows: the parameters are those of one page of page_size rows, as the paged append's)
+  if (const int s = quant_check(c, k_new, dtype, num_pages, H, page_size, D, km, k8_pool, k_scale_pool, gran, 1, 64, 64, 1.0f,
+                                rounding, nullptr, 1, nullptr))
+    return s;
+  // the bytes inside one (page, head) slice stay below 2^31, as the attention kernels need them
+  const int64_t lim = (int64_t)1 << 31;
+  if ((int64_t)page_size * k8_pool->stride_n + D >= lim) return SAGE_ERR_TOO_LARGE;
+  if (v_pool && ((int64_t)page_size * v_pool->stride_n + D) * 2 >= lim) return SAGE_ERR_TOO_LARGE;
+  if (v8_pool && (int64_t)D * v8_pool->stride_n + page_size >= lim) return SAGE_ERR_TOO_LARGE;
+  const int N = max_pages * page_size;
+  c.p.N = N;
+  KvAppendParams a;
+  a.k = c.p;
+  a.v = VPrepParams();
+  a.v_coef = v_coef;
+  if (v8_pool) {
+    a.v.out = (uint8_t*)v8_pool->data; a.v.ob = v8_pool->stride_b; a.v.oh = v8_pool->stride_h; a.v.od = v8_pool->stride_n; a.v.o_tile = 64;
+  }
+  a.start_lens = start_lens;
+  a.kv_lens = kv_lens;
+  KvPageTable pt;
+  pt.table = block_table;
+  pt.stride = table_stride;
+  pt.shift = page_size == 64 ? 0 : page_size == 128 ? 1 : 2;
+  KvRowsParams r;
+  r.k_new = (const uint16_t*)k_new->data; r.ksb = k_new->stride_b; r.ksh = k_new->stride_h; r.ksn = k_new->stride_n;
+  r.v_new = (const uint16_t*)v_new->data; r.vsb = v_new->stride_b; r.vsh = v_new->stride_h; r.vsn = v_new->stride_n;
+  r.k_tail = (uint16_t*)k_tail;
+  r.v_pool = v_pool ? (uint16_t*)v_pool->data : nullptr;
+  r.vpb = v_pool ? v_pool->stride_b : 0; r.vph = v_pool ? v_pool->stride_h : 0; r.vpn = v_pool ? v_pool->stride_n : 0;
+  r.T = T;
+  // the slots of sage_kv_cache_append_paged with max_new = T (FP16 / BF16 P.V: the V units copy rows)
+  const int ntile = (N + 63) / 64;
+  const int k_slots = std::min((std::min(T, N) + 63) / 64 + 1, ntile);
+  a.k_slots = k_slots;
+  const int blks = by_dim(D, [](auto d) { return VQuantGeom<decltype(d)::value>::BLKS; });
+  const int v_slots = blks == 1 ? k_slots : std::min(k_slots / blks + 1, (ntile + blks - 1) / blks);
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    by_flag(c.bf16, [&](auto bf) {
+      by_flag(rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        by_flag(v8_pool != nullptr, [&](auto f8) {
+          hipLaunchKernelGGL((kv_cache_append_rows_paged_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value,
+                                                                decltype(f8)::value ? 1 : 0>),
+                             dim3(k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a, pt, r);
+        });
+      });
+    });
+  });
+  return launch_status();
 }

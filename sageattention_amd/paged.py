@@ -13,8 +13,10 @@ The block table is passed on every call and is not stored; it and the lengths ar
 of their own, ``torch.ops.sageattention_amd_paged``: ``kv_cache_append_paged`` (it mutates the state pools) and
 ``attn_splitkv_paged[_lse]`` / ``attn_splitkv_causal_paged[_lse]``; everything traces under ``torch.compile(fullgraph=True)``.
 
-Not built: page sizes below 64 (a 16-key page cannot hold a scale group), dropping the fp16 K pool, paged forms of the dense,
-``kvlen`` and block-sparse operators, moving frozen statistics without preparing again, and pages shared between sequences
+A cache that owns every pool and keeps no fp16 K pool is ``SagePagedRowCache`` (paged_rows.py).
+
+Not built: page sizes below 64 (a 16-key page cannot hold a scale group), paged forms of the dense, ``kvlen`` and block-sparse
+operators, moving frozen statistics without preparing again, and pages shared between sequences
 (prefix sharing needs frozen statistics shared by the sequences that use the page)."""
 from typing import Any, Optional
 
@@ -153,6 +155,12 @@ class SagePagedKVCache:
         self.page_size = L.dims(k_pool, tensor_layout)[2]
         self.k8 = self.k_scale = self.km = self.v8 = self.v_scale = self.v_coef = None
 
+    # what sageattn_splitkv_paged reads of a cache
+    dtype = property(lambda self: self.k.dtype)
+    device = property(lambda self: self.k.device)
+    head_dim = property(lambda self: self.k.size(-1))
+    num_kv_heads = property(lambda self: L.dims(self.k, self.tensor_layout)[1])
+
     @classmethod
     def prepare(cls, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, kv_lens: torch.Tensor,
                 pv: str = "fp16", qk_quant_gran: str = "per_thread", tensor_layout: str = "HND",
@@ -262,6 +270,9 @@ class SagePagedKVCache:
         return c
 
 
+_CACHE_TYPES = [SagePagedKVCache]  # ... and SagePagedRowCache (paged_rows.py), whose pools the same kernels read
+
+
 def sageattn_splitkv_paged(q: torch.Tensor, cache: SagePagedKVCache, block_table: torch.Tensor, kv_lens: torch.Tensor,
                            num_splits: Optional[int] = None, causal: bool = False, q_fold: int = 1,
                            sm_scale: Optional[float] = None, return_lse: bool = False, **refused: Any):
@@ -273,28 +284,30 @@ def sageattn_splitkv_paged(q: torch.Tensor, cache: SagePagedKVCache, block_table
 
     ``num_splits``: 1..16, or None for ``splitkv_num_splits(B, Hq, M, max_pages * page_size)``; 1 runs the paged split kernel
     with one split.  What ``sageattn_splitkv_cached`` refuses is refused here in the same words."""
-    if not isinstance(cache, SagePagedKVCache):
+    if not isinstance(cache, tuple(_CACHE_TYPES)):
         raise TypeError(f"cache must be a SagePagedKVCache, got {type(cache).__name__}")
     if isinstance(causal, torch.Tensor) or not isinstance(causal, (bool, int)):
         raise TypeError(f"causal must be a bool, got {type(causal).__name__}")
     causal = bool(causal)
     op_name = "sageattn_splitkv_causal" if causal else "sageattn_splitkv"
-    block_table = _check_block_table(block_table, q.size(0), cache.k.device)
+    block_table = _check_block_table(block_table, q.size(0), cache.device)
+    # (shapes only: a cache without fp16 pools has its INT8 K pool in their shape)
+    k_like, v_like = (cache.k, cache.v) if isinstance(cache, SagePagedKVCache) else (cache.k8, cache.k8)
     if kv_lens is None:
         raise TypeError("kv_lens must be an int32 tensor of shape [B]")
-    kv_lens, ns, M = core._splitkv_front(op_name, causal, q, cache.k, cache.v, kv_lens, num_splits, cache.tensor_layout,
+    kv_lens, ns, M = core._splitkv_front(op_name, causal, q, k_like, v_like, kv_lens, num_splits, cache.tensor_layout,
                                          cache.pv, cache.qk_quant_gran, refused)
     if isinstance(q_fold, bool) or not isinstance(q_fold, int):
         raise TypeError(f"q_fold must be an int >= 1, got {type(q_fold).__name__}")
     if q_fold < 1 or M % q_fold != 0 or (q_fold != 1 and not causal):
         raise ValueError(f"q_fold must be >= 1 and divide the {M} query rows (and 1 unless causal), got {q_fold}")
-    if q.dtype != cache.k.dtype or q.device != cache.k.device:
+    if q.dtype != cache.dtype or q.device != cache.device:
         raise ValueError("q must have the dtype and device of the cache's k")
-    D = cache.k.size(-1)
+    D = cache.head_dim
     if q.size(-1) != D:
         raise ValueError(f"q must have the cache's head_dim {D}, got {q.size(-1)}")
     B, Hq = L.dims(q, cache.tensor_layout)[:2]
-    Hk = L.dims(cache.k, cache.tensor_layout)[1]
+    Hk = cache.num_kv_heads
     if Hq % Hk != 0:
         raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
     if cache.km.size(0) != B:
