@@ -60,8 +60,8 @@
  * A cache that owns every pool and keeps no fp16 K pool: sageattn_hip_paged_rows.h.
  *
  * NOT BUILT: page sizes below 64 (a 16-key page cannot hold a scale group); paged forms of the dense, kvlen and block-sparse
- * operators; moving frozen statistics without preparing again; pages shared between sequences
- * (prefix sharing needs frozen statistics shared by the sequences that use the page).
+ * operators; moving frozen statistics without preparing again.  Pages are not shared between sequences -- the frozen
+ * statistics are per sequence; a prefix the sequences share is a sequence of its own: sageattn_hip_prefix.h.
  */
 #ifndef SAGEATTN_HIP_PAGED_H
 #define SAGEATTN_HIP_PAGED_H

@@ -46,8 +46,8 @@
  *    (s_b below the old length); it excludes two rollbacks in a row past two tile boundaries: a ring of two slots then no
  *    longer holds the tile the sequence fell back into.
  *
- * NOT BUILT: the same for the contiguous cache of sageattn_hip_kvcache.h; moving frozen statistics without preparing again;
- * pages shared between sequences.
+ * NOT BUILT: the same for the contiguous cache of sageattn_hip_kvcache.h; moving frozen statistics without preparing again.
+ * A prefix the sequences share is a sequence of its own: sageattn_hip_prefix.h.
  */
 #ifndef SAGEATTN_HIP_PAGED_ROWS_H
 #define SAGEATTN_HIP_PAGED_ROWS_H

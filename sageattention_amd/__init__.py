@@ -14,6 +14,7 @@ from .ulysses import ulysses_sageattn  # noqa: F401  (head parallel, RCCL all-to
 from .kvcache import SageKVCache, sageattn_splitkv_cached  # a persistent quantized KV cache for the split-KV operators
 from .paged import SagePagedKVCache, sageattn_splitkv_paged  # ... kept in pages of one pool, addressed through a block table
 from .paged_rows import SagePagedRowCache  # ... that owns every pool and takes the step's new rows: no fp16 K pool
+from .prefix import sageattn_splitkv_paged_prefix  # ... with a prefix the sequences share, stored and read once
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen", "ring_sageattn",
@@ -21,5 +22,5 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "sparge_plan", "sageattn_tile_mass", "plan_recall", "sparge_tune", "SpargeTuning", "sageattn_kvlen",
            "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits",
            "sageattn_splitkv_causal", "SageKVCache", "sageattn_splitkv_cached",
-           "SagePagedKVCache", "sageattn_splitkv_paged", "SagePagedRowCache"]
+           "SagePagedKVCache", "sageattn_splitkv_paged", "SagePagedRowCache", "sageattn_splitkv_paged_prefix"]
 __version__ = "0.2.0"

@@ -32,6 +32,9 @@ SOURCES = [
     # ... and the paged twins of the two (K / V tiles out of the pages a block table names)
     ("sage_attn_splitkv_paged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("sage_attn_splitkv_causal_paged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # shared-prefix attention on the paged cache: the merge of the two segments (no attention kernel of its own; contraction
+    # off: the LSE tails round product and sum separately)
+    ("sage_attn_prefix.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -160,6 +163,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_kvcache.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged_rows.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_prefix.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}

@@ -149,12 +149,25 @@ PAGED_ROWS_SIGNATURES = {
     "sage_kv_cache_append_rows_paged": (_I, [_P, _P, _I, _I, _I, _I, _I, _V, _V, _P, _V, _I, _I, _P, _P, _V] + _TABLE + [_V, _V, _V]),
 }
 
+# include/sageattn_hip_prefix.h.  The attention entries: the operands of the paged ones | B Hq Hk M D | qk_gran warpq sm_scale |
+# table | kv_lens | prefix_table max_prefix_pages prefix_len km_p [v_scale_p] | prefix_splits num_splits q_fold workspace
+# workspace_bytes stream
+_PREFIX_HEAD = [_I] * 5 + _QUANT["fusedq"] + _TABLE + [_V] + [_V, _I, _V, _V]
+_PREFIX_TAIL = [_I, _I, _I, _V, c_size_t, _V]
+PREFIX_SIGNATURES = {
+    "sage_prefix_workspace_bytes": (c_size_t, [_I] * 6),
+    "sage_attn_fusedq_pv_f16_splitkv_paged_prefix": (_I, [_P, _I, _P, _P, _I, _P, _I, _V, _V, _V] + _PREFIX_HEAD + _PREFIX_TAIL),
+    "sage_attn_fusedq_pv_f8_splitkv_paged_prefix": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _PREFIX_HEAD + [_V] + _PREFIX_TAIL),
+}
+
 
 def bind(cdll, missing_ok=True):
-    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES and PAGED_ROWS_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES and
+    PREFIX_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
-    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
+                              **PREFIX_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -28,4 +28,14 @@ static int launch_4wave_kernel(const AttnCall& c, hipStream_t st, int grid, Kern
   });
 }
 
+// slot count of a merge kernel (splitkv_merge_kernel, sage_attn_splitkv.hip; prefix_merge_kernel, sage_attn_prefix.hip) as a
+// compile-time constant: the first of 2, 4, 8, 16 that holds S
+template <class F>
+static void by_slots(int count, F&& f) {
+  if (count <= 2) f(std::integral_constant<int, 2>{});
+  else if (count <= 4) f(std::integral_constant<int, 4>{});
+  else if (count <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+
 }  // namespace sage

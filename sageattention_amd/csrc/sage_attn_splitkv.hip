@@ -114,15 +114,6 @@ int launch_splitkv_attn(const AttnCall& c, hipStream_t st) {
   });
 }
 
-// slot count of the merge kernel as a compile-time constant: the first of 2, 4, 8, 16 that holds S
-template <class F>
-static void by_slots(int count, F&& f) {
-  if (count <= 2) f(std::integral_constant<int, 2>{});
-  else if (count <= 4) f(std::integral_constant<int, 4>{});
-  else if (count <= 8) f(std::integral_constant<int, 8>{});
-  else f(std::integral_constant<int, 16>{});
-}
-
 // the merge of a split-KV call, causal (c.splitkv_causal) or not
 int launch_splitkv_merge(const AttnCall& c, hipStream_t st) {
   const AttnParams& p = c.p;

@@ -188,6 +188,10 @@ int launch_splitkv_merge(const AttnCall& c, hipStream_t st);
 // kernel in the place of the two above, then the same merge
 int launch_splitkv_paged_attn(const AttnCall& c, hipStream_t st);
 int launch_splitkv_causal_paged_attn(const AttnCall& c, hipStream_t st);
+// ... of a shared-prefix call (include/sageattn_hip_prefix.h; sage_attn_prefix.hip), which goes through the two launches above
+// itself -- attn_launch would append the merge of ONE segment -- and then through this one: the merge of the prefix call's and
+// the suffix call's partial slots, each segment with the correction its split 0 parked at c.p.lse, into suffix.p.o and `lse`
+int launch_prefix_merge(const AttnCall& prefix, const AttnCall& suffix, float* lse, hipStream_t st);
 // bytes of the workspace of a split-KV call: the partial outputs fp32 [S,B,Hq,M,D], then their base-2 LSEs fp32 [S,B,Hq,M]
 inline int64_t splitkv_bytes(int B, int Hq, int M, int D, int S) {
   return (int64_t)S * B * Hq * M * ((int64_t)D + 1) * 4;

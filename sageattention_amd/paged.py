@@ -16,8 +16,9 @@ of their own, ``torch.ops.sageattention_amd_paged``: ``kv_cache_append_paged`` (
 A cache that owns every pool and keeps no fp16 K pool is ``SagePagedRowCache`` (paged_rows.py).
 
 Not built: page sizes below 64 (a 16-key page cannot hold a scale group), paged forms of the dense, ``kvlen`` and block-sparse
-operators, moving frozen statistics without preparing again, and pages shared between sequences
-(prefix sharing needs frozen statistics shared by the sequences that use the page)."""
+operators, and moving frozen statistics without preparing again.  Pages are not shared between sequences -- the frozen
+statistics are per sequence; a prefix the sequences share is a sequence of its own: ``sageattn_splitkv_paged_prefix``
+(prefix.py, include/sageattn_hip_prefix.h)."""
 from typing import Any, Optional
 
 import torch

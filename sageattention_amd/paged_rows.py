@@ -15,8 +15,8 @@ attention} captures into one HIP graph.  The op lives in a namespace of its own,
 ``torch.ops.sageattention_amd_paged_rows.kv_cache_append_rows_paged`` (it mutates the pools and the tail), and traces under
 ``torch.compile(fullgraph=True)``.
 
-Not built: the same for the contiguous ``SageKVCache``, moving frozen statistics without preparing again, and pages shared
-between sequences (prefix sharing)."""
+Not built: the same for the contiguous ``SageKVCache`` and moving frozen statistics without preparing again.  A prefix the
+sequences share is a sequence of its own: ``sageattn_splitkv_paged_prefix`` (prefix.py)."""
 from typing import Optional
 
 import torch
