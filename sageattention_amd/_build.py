@@ -10,6 +10,7 @@ LIB = os.path.join(HERE, "libsageattn_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # (source, extra flags).  The quantizers need exact IEEE semantics (bit-exact vs the oracle).
 SOURCES = [
     ("sage_quant.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
@@ -35,6 +36,11 @@ SOURCES = [
     # shared-prefix attention on the paged cache: the merge of the two segments (no attention kernel of its own; contraction
     # off: the LSE tails round product and sum separately)
     ("sage_attn_prefix.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
+    # split-KV attention on the MXFP4 V image of the cache (the same body, its third P.V mode), and the stand-alone quantizer of
+    # that image (exact arithmetic, as sage_quant.hip, which holds the cache append).  New code is compiled without packed fp32
+    # operations altogether
+    ("sage_attn_splitkv_v4.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
+    ("sage_fp4.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -91,6 +97,7 @@ def _check_occupancy(src, compiler_output):
                             re.search(r"attn_i8_splitkv_causal_kernelILi64E(Lb[01]E){3}EE", name) or  # ... with the diagonal
                             re.search(r"attn_i8_splitkv_paged_kernelILi64E(Lb[01]E){3}EE", name) or       # ... out of pages
                             re.search(r"attn_i8_splitkv_causal_paged_kernelILi64E(Lb[01]E){3}EE", name) or
+                            re.search(r"attn_i8_splitkv(_causal)?_v4_kernelILi64ELb[01]EEE", name) or     # ... on the FP4 V image
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
                             re.search(r"attn_i8_blocksparse_pvskip_kernelILi64ELb[01]ELb0ELb[01]EEE", name) or
                             # the block-sparse kernels with key lengths, held to the lines of their twins above
@@ -164,6 +171,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged_rows.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_prefix.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_fp4.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -207,6 +215,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_causal.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_paged.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_causal_paged.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_v4.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -160,14 +160,27 @@ PREFIX_SIGNATURES = {
     "sage_attn_fusedq_pv_f8_splitkv_paged_prefix": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _PREFIX_HEAD + [_V] + _PREFIX_TAIL),
 }
 
+# include/sageattn_hip_fp4.h.  The quantizer: v dtype | B H N D | img scale kv_lens stream.  The append: the K arguments of
+# sage_kv_cache_append | img scale | start_lens kv_lens max_new stream.  The attention entries: those of the f8 split-KV forms
+# with (v_img, ..., v_img_scale) in the place of (v_fp8, ..., v_scale) and no v_mean
+_F4_OPERANDS = [_P, _I, _P, _P, _P, _I] + [_V] * 4   # q q_dtype k8 v_img o o_dtype | k_scale km v_img_scale lse
+FP4_SIGNATURES = {
+    "sage_quant_v_mxfp4": (_I, [_P, _I, _I, _I, _I, _I, _P, _V, _V, _V]),
+    "sage_kv_cache_append_v4": (_I, [_P, _P, _I, _I, _I, _I, _I, _V, _P, _V, _I, _I, _P, _V, _V, _V, _I, _V]),
+    "sage_attn_fusedq_pv_f4_splitkv": _attn("fusedq_pv_f4", _SPLITKV, operands=_F4_OPERANDS, is_causal=False,
+                                            quant=_QUANT["fusedq"]),
+    "sage_attn_fusedq_pv_f4_splitkv_causal": _attn("fusedq_pv_f4", _SPLITKV[:2] + [_I] + _SPLITKV[2:], operands=_F4_OPERANDS,
+                                                   is_causal=False, quant=_QUANT["fusedq"]),
+}
+
 
 def bind(cdll, missing_ok=True):
-    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES and
-    PREFIX_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
+    PREFIX_SIGNATURES and FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
-                              **PREFIX_SIGNATURES}.items():
+                              **PREFIX_SIGNATURES, **FP4_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

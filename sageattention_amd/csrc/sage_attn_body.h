@@ -23,14 +23,26 @@
   static_assert(!SPLITKV || (!HAS_MASK && !SPARSE && !KVLEN && NWAVES == 4),
                 "split-KV: 4 waves, no attn_mask, no block map (its optional lengths are its own: p.kv_lens may be null)");
   static_assert(!PAGED || SPLITKV, "block tables: the split-KV kernels only");
+  // PV_FP4 (attn_i8_splitkv_v4_kernel / attn_i8_splitkv_causal_v4_kernel, sage_attn_splitkv_v4.hip, which define the macro; the
+  // rule: include/sageattn_hip_fp4.h): a third P.V mode on top of PV_FP8 -- P, the row sums, the lazy rescale and the LSE are the
+  // FP8 mode's -- in which the A operand V^T is e2m1 with an e8m0 scale per lane and tile.  What differs is marked PV_FP4 below:
+  // the V tile ([D][32] bytes), its swizzle and copies, the scale register, the MFMA and the epilogue without a V scale.
+  // Its statements stand under the macro, not under `if constexpr`: a name that a lambda of the loop mentions is captured by
+  // that lambda in EVERY kernel, and the FP8 head_dim-64 block-sparse kernels then come out with other instruction streams.
+#ifdef SAGE_ATTN_BODY_PV_FP4
+  constexpr bool PV_FP4 = true;
+  static_assert(PV_FP8 && SPLITKV && !PAGED && NWAVES == 4, "FP4 V: the 4-wave split-KV kernels on top of the FP8 mode");
+#else
+  constexpr bool PV_FP4 = false;
+#endif
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
   constexpr int DT = D / 32;          // 32-wide d tiles of O^T
   constexpr int KBYTES = 64 * D;      // one K tile (int8)
-  constexpr int VBYTES = PV_FP8 ? 64 * D : 64 * D * 2;  // one V tile: fp16 [64][D] or e4m3 [D][64]
+  constexpr int VBYTES = PV_FP4 ? 32 * D : PV_FP8 ? 64 * D : 64 * D * 2;  // one V tile: fp16 [64][D], e4m3 [D][64] or e2m1 [D][32 B]
   constexpr int KCH = D / 16;         // 16-B chunks per K row
-  constexpr int VCH = PV_FP8 ? 4 : D / 8;       // 16-B chunks per V tile row (fp8: a V^T row holds 64 tokens)
+  constexpr int VCH = PV_FP4 ? 2 : PV_FP8 ? 4 : D / 8;  // 16-B chunks per V tile row (fp8: a V^T row holds 64 tokens; fp4: in 32 B)
   constexpr int VROWS = PV_FP8 ? D : 64;        // rows of the V tile image
   constexpr int KC = (64 * KCH + T - 1) / T;    // chunks per thread
   constexpr int VC = (VROWS * VCH + T - 1) / T;
@@ -369,7 +381,8 @@
   // last valid byte + 1 of the (b, h_kv) slice: row N-1 = row (N-1)%64 of tile (N-1)/64 (dense layouts: (N-1)*stride_n)
   const int last_t = (N_ - 1) >> 6, last_r = (N_ - 1) & 63;
   const unsigned k_bytes = (unsigned)((int64_t)last_t * k_tile_stride + (int64_t)last_r * p.ksn + D);
-  const unsigned v_bytes = PV_FP8 ? (unsigned)((int64_t)last_t * v_tile_stride + (int64_t)(D - 1) * p.vsn + 64)
+  const unsigned v_bytes = PV_FP4 ? (unsigned)((int64_t)last_t * v_tile_stride + (int64_t)(D - 1) * p.vsn + 32)
+                           : PV_FP8 ? (unsigned)((int64_t)last_t * v_tile_stride + (int64_t)(D - 1) * p.vsn + 64)
                                   : (unsigned)((int64_t)last_t * v_tile_stride + ((int64_t)last_r * p.vsn + D) * 2);
   const v4i k_rsrc = make_rsrc(kg, k_bytes), v_rsrc_dma = make_rsrc(vg, v_bytes);
   // LDS-DMA (buffer_load ... lds): a wave instruction writes 64 x 16 B = 1 KiB of LDS LINEARLY (wave-uniform
@@ -385,7 +398,18 @@
   }
 #pragma unroll
   for (int i = 0; i < VC; ++i) {
-    const int c = tid + i * T, vr = c / VCH, pos = c % VCH;
+    // (PV_FP4 at head_dim 64: a tile has 128 chunks for 256 threads.  The counted waits of the four-slot ring need every wave
+    //  to issue the same number of copies per tile, so waves 2 and 3 copy the chunks of waves 0 and 1 again, to the same
+    //  place: the same bytes, out of L2)
+    const int c = PV_FP4 ? (tid + i * T) % (VROWS * VCH) : tid + i * T, vr = c / VCH, pos = c % VCH;
+#ifdef SAGE_ATTN_BODY_PV_FP4
+    if constexpr (PV_FP4) {
+      // V^T row vr (= channel) of 32 bytes: the 16 lanes of a ds_read_b128 pass read 16 consecutive rows, and rows r and r + 8
+      // (256 bytes apart) meet in the same 4 banks; XOR with bit 3 of the row sends them to the two different 16-byte
+      // halves, and the reads of the 32 channels x 2 lane halves are conflict free
+      v_voff[i] = vr * (int)p.vsn + ((pos ^ ((vr >> 3) & 1)) << 4);
+    } else
+#endif
     if constexpr (PV_FP8) {
       v_voff[i] = vr * (int)p.vsn + ((pos ^ ((vr >> 2) & 3)) << 4);  // V^T row vr (= channel), 16-B chunk swizzle
     } else {
@@ -452,6 +476,13 @@
     } else {
 #pragma unroll
     for (int i = 0; i < VC; ++i) {
+#ifdef SAGE_ATTN_BODY_PV_FP4
+      if constexpr (PV_FP4) {  // every wave copies (above): half as many 16-byte chunks per tile as the FP8 mode
+        lds_dma16(v_rsrc_dma, (unsigned)(RING * KBYTES + buf * VBYTES + ((wave * 64 + i * T) % (VROWS * VCH)) * 16), v_voff[i],
+                  j * v_tile_stride);
+        continue;
+      }
+#endif
       if (!(VC * T == VROWS * VCH || wave * 64 + i * T < VROWS * VCH)) continue;
       lds_dma16(v_rsrc_dma, (unsigned)(RING * KBYTES + buf * VBYTES + (wave * 64 + i * T) * 16), v_voff[i], j * v_tile_stride);
     }
@@ -466,6 +497,45 @@
   const char* v_rd8[2];  // fp8: V^T row r (+32*dt immediate), 16-B chunks 2*hh and 2*hh+1
 #pragma unroll
   for (int c = 0; c < 2; ++c) v_rd8[c] = v_lds + (r * 64 + (((2 * hh + c) ^ ((r >> 2) & 3)) << 4));
+#ifdef SAGE_ATTN_BODY_PV_FP4
+  // PV_FP4: the lane's 32 nibbles are ONE 16-byte chunk, hh, of row r (+32*dt immediate); and the scale bytes.  The D / 32
+  // bytes of lane (r, hh) -- channels r, r + 32, ... of the tile, [hh][c % 32][c / 32] -- are one load per tile at lane * D / 32
+  // of the tile's 2 * D bytes, straight into a VGPR: vs4 holds those of the tile whose P.V comes next.  The load of tile j + 1
+  // is issued behind the P.V MFMAs of tile j, from inline asm like the tile copies and for the same reason (hipcc would wait
+  // for it with vmcnt(0), draining every copy in flight); it is the youngest vector-memory operation until the next tile's
+  // copies, which are NDMA per wave, so dma_wait_keep<NDMA> in front of the next P.V is its wait.  The counted wait at the end
+  // of an iteration then sees NDMA + 1 operations per iteration and keeps 2 * NDMA: stricter than needed, never weaker.
+  int vs4 = 0;
+  const uint8_t* vs_head = nullptr;
+  const int vs_lane = lane * (D / 32);
+  (void)vs4; (void)vs_head; (void)vs_lane;
+  if constexpr (PV_FP4) {
+    v_rd8[0] = v_rd8[1] = v_lds + (r * 32 + ((hh ^ ((r >> 3) & 1)) << 4));
+    vs_head = reinterpret_cast<const uint8_t*>(p.v_scale) + (((int64_t)b * p.Hk + hk) * ((p.N + 63) >> 6) + sk_t0) * (2 * D);
+    if constexpr (D == 128) vs4 = *reinterpret_cast<const int*>(vs_head + vs_lane);  // tile 0 (the compiler's own wait)
+    else vs4 = *reinterpret_cast<const uint16_t*>(vs_head + vs_lane);
+  }
+  auto load_vscale = [&](const int j) __attribute__((always_inline)) {  // scale bytes of tile j of the moved operands -> vs4
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint8_t* const tp = vs_head + (int64_t)j * (2 * D);
+    if constexpr (D == 128) asm volatile("global_load_dword %0, %1, %2" : "+v"(vs4) : "v"(vs_lane), "s"(tp) : "memory");
+    else asm volatile("global_load_ushort %0, %1, %2" : "+v"(vs4) : "v"(vs_lane), "s"(tp) : "memory");
+#endif
+  };
+  // the P.V MFMA of channel block dt: A = e2m1 (cbsz 4; the upper four registers of the operand are not live), B = e4m3, the
+  // A scale byte dt of vs4, the B scale 2^0
+  auto pv4_mfma = [&](const int dt, const v4i vf, const v8i pb, const v16f c) __attribute__((always_inline)) -> v16f {
+    v8i a;
+    a.s0123 = vf;
+    a.s4567 = vf;
+    switch (dt) {
+      case 0: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, c, 4, 0, 0, vs4, 0, 0x7f7f7f7f);
+      case 1: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, c, 4, 0, 1, vs4, 0, 0x7f7f7f7f);
+      case 2: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, c, 4, 0, 2, vs4, 0, 0x7f7f7f7f);
+      default: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, c, 4, 0, 3, vs4, 0, 0x7f7f7f7f);
+    }
+  };
+#endif
   const char* v_rd[DT];  // fp16: V^T fragment via tr-read: row 4*hh + q4 (+32*mt+16*s(+8) immediate), window dt
   {
     const int i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3, g = (lane >> 4) & 1;
@@ -835,7 +905,7 @@
 
   // tile copies a wave issues per iteration (full tiles): the unit of the counted waits of the four-slot ring
   constexpr int NDMA = KC + VC;
-  static_assert(RING == 2 || (KC * T == 64 * KCH && VC * T == VROWS * VCH), "four-slot ring: every wave copies full shares");
+  static_assert(RING == 2 || (KC * T == 64 * KCH && (PV_FP4 || VC * T == VROWS * VCH)), "four-slot ring: every wave copies full shares");
   const int last_tile = ntiles - 1;
   // list position of a read-ahead -> key tile.  Dense: clamped to the last tile; block-sparse: the padded list is read blindly
   auto ahead = [&](const int pos) __attribute__((always_inline)) -> int {
@@ -1037,6 +1107,13 @@
         sb[mt] = ks == 0 ? mfma_s_first(a, qf[ks]) : __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qf[ks], sb[mt], 0, 0, 0);
       };
       auto v_frag8 = [&](const int dt) __attribute__((always_inline)) -> v8i {
+#ifdef SAGE_ATTN_BODY_PV_FP4
+        if constexpr (PV_FP4) {  // one 16-byte read per MFMA: the lane's 32 nibbles
+          v8i a4 = {0, 0, 0, 0, 0, 0, 0, 0};
+          a4.s0123 = *reinterpret_cast<const v4i*>(v_rd8[0] + (vb + dt * 32 * 32));
+          return a4;
+        }
+#endif
         const int base = vb + dt * 32 * 64;
         v8i a;
         a.s0123 = *reinterpret_cast<const v4i*>(v_rd8[0] + base);
@@ -1085,10 +1162,18 @@
       // P.V beside the row max of S(j+1)
       if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(SPARSE ? bw1 : j + 1, sb); }
       int mxa = sb[0][0], mxb = sb[0][2];
+#if defined(SAGE_ATTN_BODY_PV_FP4) && defined(__HIP_DEVICE_COMPILE__)
+      // the scale bytes of this tile have landed: only this iteration's copies are younger
+      asm volatile("s_waitcnt vmcnt(%1)" : "+v"(vs4) : "n"(NDMA) : "memory");
+#endif
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         if (dt + 2 < DT) vf[dt + 2] = v_frag8(dt + 2);
+#ifdef SAGE_ATTN_BODY_PV_FP4
+        acc_o[dt] = pv4_mfma(dt, vf[dt].s0123, pb, acc_o[dt]);
+#else
         acc_o[dt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf[dt], pb, acc_o[dt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+#endif
         if constexpr (NEXT != 2) {
 #pragma unroll
           for (int idx = dt * (32 / DT); idx < (dt + 1) * (32 / DT); ++idx) {
@@ -1100,6 +1185,9 @@
         SAGE_FENCE();
       }
 #undef SAGE_FENCE
+#ifdef SAGE_ATTN_BODY_PV_FP4
+      if constexpr (NEXT != 2) load_vscale(min(j + 1, last_tile));  // behind the last MFMA that reads vs4
+#endif
       if constexpr (NEXT != 2) {
         float mx;
         if constexpr (KTHREAD) mx = max_raw((__int_as_float(mxa) - kBiasF) * b0, (__int_as_float(mxb) - kBiasF) * b1);
@@ -1326,7 +1414,7 @@
   //    run-time slots (fast_iter, NEXT = 1 / 2): C2 +0.8 %, C2-fp8 +1.6 %, (8,32,2048,128) causal +3.5 %.
   //  * FP8 PV at head_dim 128: the compiler-scheduled body.  With the stream variants instantiated
   //    their MAIN loop came out 0.3-1 % slower (different register assignment), more than the tail tiles return.
-  constexpr bool STREAM_TAIL = !(PV_FP8 && D == 128);
+  constexpr bool STREAM_TAIL = !(PV_FP8 && D == 128) || PV_FP4;  // (PV_FP4: the stream is the mode's only P.V)
   if constexpr (STREAM_TAIL) {
     for (; j + 1 < wave_tiles; ++j) {
       fast_iter(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, j, s_cur, s_nxt, sc0, sc1, nsc0, nsc1);
@@ -1386,7 +1474,7 @@
           float x[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) x[e] = acc_o[dt][4 * g4 + e] * inv;
-          if constexpr (PV_FP8) {
+          if constexpr (PV_FP8 && !PV_FP4) {  // (PV_FP4: the block scales went into the MFMA; p.v_scale holds their bytes)
             const float4 vs = *reinterpret_cast<const float4*>(p.v_scale + ((int64_t)b * p.Hk + hk) * D + d0 + 4 * hh_l);
             x[0] *= vs.x; x[1] *= vs.y; x[2] *= vs.z; x[3] *= vs.w;
           }

@@ -20,8 +20,10 @@
 #include "../../include/sageattn_hip_kvcache.h"
 #include "../../include/sageattn_hip_paged.h"
 #include "../../include/sageattn_hip_paged_rows.h"
+#include "../../include/sageattn_hip_fp4.h"
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
+#include "sage_fp4_kernels.h"
 
 namespace sage {
 
@@ -934,6 +936,35 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_kernel(c
   }
 }
 
+// The cache with an MXFP4 V image (include/sageattn_hip_fp4.h, sage_kv_cache_append_v4): the same grid, the same K slots and
+// the same K tile body; a V slot is unit t0_b / BLKS + i of the image, quantized from the bound rows by v4_quant_unit
+// (sage_fp4_kernels.h), which stores the unit's tiles from t0_b on.  No coefficients: the scale groups live inside a tile.
+// (A kernel of its own, not a mode of kv_cache_append_kernel: the instantiations of that one keep their instruction streams.)
+template <int D, bool BF16, bool TRITON>
+// (four workgroups per CU at both head dims: the V unit holds its 32 values and their maxima in registers)
+__global__ __launch_bounds__(256, 4) void kv_cache_append_v4_kernel(const KvAppendParams a, const V4Image img) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[2][64];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[V4QuantGeom<D>::LDS];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const int len = kv_len_of(a.kv_lens, b, a.k.N);
+  if (len == 0) return;
+  const int t0 = min(kv_len_of(a.start_lens, b, a.k.N), len - 1) >> 6;
+  const int ntile = (len + 63) >> 6;
+  if ((int)blockIdx.x < a.k_slots) {
+    const int blk = t0 + blockIdx.x;
+    if (blk >= ntile) return;
+    QuantParams p = a.k;
+    p.N = len;
+    if (p.gran == SAGE_GRAN_PER_THREAD) kv_append_k_tile<D, BF16, TRITON, true>(p, blk, h, b, H, gmax);
+    else kv_append_k_tile<D, BF16, TRITON, false>(p, blk, h, b, H, gmax);
+    return;
+  }
+  const int unit = t0 / G::BLKS + ((int)blockIdx.x - a.k_slots);
+  if (unit * G::BLKS >= ntile) return;
+  v4_quant_unit<D, BF16>(a.v.v, a.v.sb, a.v.sh, a.v.sn, len, img, unit, t0, h, b, lds);
+}
+
 // The paged form (sage_kv_cache_append_paged): the same grid, the same slots in logical tiles, the same K block and V unit
 // bodies.  A K slot moves its pointers to the page of its tile -- after that, tile `blk` of batch b IS the tile of the page,
 // and kv_append_k_tile runs unchanged (km stays that of batch b); a V slot runs kv_append_v_unit_paged.
@@ -1545,6 +1576,44 @@ extern "C" int sage_kv_cache_append(const sage_tensor* k, const sage_tensor* v, 
                                     const int32_t* kv_lens, int max_new, sage_stream_t stream) {
   return kv_cache_append(k, v, dtype, B, H, N, D, km, k_int8, k_scale, gran, rounding, v_fp8, v_coef, start_lens, kv_lens,
                          max_new, nullptr, 0, stream);
+}
+
+// ---- the cache with an MXFP4 V image (include/sageattn_hip_fp4.h): the checks and slots of kv_cache_append, one launch
+extern "C" int sage_kv_cache_append_v4(const sage_tensor* k, const sage_tensor* v, int dtype, int B, int H, int N, int D,
+                                       const void* km, const sage_tensor* k_int8, float* k_scale, int gran, int rounding,
+                                       const sage_tensor* img, uint8_t* scale, const int32_t* start_lens,
+                                       const int32_t* kv_lens, int max_new, sage_stream_t stream) {
+  if (!km || !aligned16(km) || !kv_lens_ok(start_lens) || !kv_lens_ok(kv_lens) || max_new < 1) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v, 8) || !tensor_ok(img, 16) || !scale || !aligned16(scale)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
+  if (B <= 0 || N <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  QuantCall c;
+  if (const int s = quant_check(c, k, dtype, B, H, N, D, km, k_int8, k_scale, gran, 1, 64, 64, 1.0f, rounding, nullptr, 1, nullptr))
+    return s;
+  KvAppendParams a;
+  a.k = c.p;
+  a.v = VPrepParams();
+  a.v.v = (const uint16_t*)v->data; a.v.sb = v->stride_b; a.v.sh = v->stride_h; a.v.sn = v->stride_n;
+  a.v_coef = nullptr;
+  a.start_lens = start_lens;
+  a.kv_lens = kv_lens;
+  const int ntile = (N + 63) / 64;
+  a.k_slots = std::min((std::min(max_new, N) + 63) / 64 + 1, ntile);  // as kv_cache_append
+  const int blks = by_dim(D, [](auto d) { return VQuantGeom<decltype(d)::value>::BLKS; });
+  const int v_slots = blks == 1 ? a.k_slots : std::min(a.k_slots / blks + 1, (ntile + blks - 1) / blks);
+  V4Image o;
+  o.img = (uint8_t*)img->data; o.ob = img->stride_b; o.oh = img->stride_h; o.od = img->stride_n;
+  o.scale = scale; o.sh = (int64_t)ntile * 2 * D; o.sb = o.sh * H;
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    by_flag(c.bf16, [&](auto bf) {
+      by_flag(rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        hipLaunchKernelGGL((kv_cache_append_v4_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value>),
+                           dim3(a.k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a, o);
+      });
+    });
+  });
+  return launch_status();
 }
 
 // ---- paged KV cache (include/sageattn_hip_paged.h): the table's own arguments, then the checks and the launch above

@@ -271,3 +271,92 @@ def sageattn_compilable(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tenso
         sm_scale = q.size(-1) ** -0.5
     op = _NS.attn_lse if return_lse else _NS.attn
     return op(q, k, v, tensor_layout, bool(is_causal), float(sm_scale), pv, qk_quant_gran)
+
+
+# ---- torch.ops.sageattention_amd_fp4: the MXFP4 V image of the KV cache (fp4.py; include/sageattn_hip_fp4.h) --------------------
+# A namespace of its own, as the other caches have: ``quant_v_mxfp4`` (it fills the caller's img and scale),
+# ``kv_cache_append_v4`` (it mutates the state) and ``attn_splitkv[_causal]_v4[_lse]``.  The image is uint8 [B,Hk,D,32*T] and
+# its scale bytes uint8 [B,Hk,T,2*D], T = ceil(N/64), in both tensor layouts.  Everything traces under
+# ``torch.compile(fullgraph=True)`` and captures into a HIP graph: lengths are read on the device only.
+from . import _lib as L  # noqa: E402
+
+_NS4 = "sageattention_amd_fp4"
+
+
+def _img_desc(img):
+    return L.SageTensor(img.data_ptr(), img.stride(0), img.stride(1), img.stride(2))
+
+
+@torch.library.custom_op(f"{_NS4}::quant_v_mxfp4", mutates_args=("img", "scale"))
+def quant_v_mxfp4(v: torch.Tensor, img: torch.Tensor, scale: torch.Tensor, kv_lens: Optional[torch.Tensor],
+                  tensor_layout: str) -> None:
+    """sage_quant_v_mxfp4: the tiles below ceil(len_b / 64) of every batch, one launch"""
+    B, H, N, D = L.dims(v, tensor_layout)
+    with torch.cuda.device(v.device):
+        L.check(L.lib().sage_quant_v_mxfp4(L.desc(v, tensor_layout), L.dtype_code(v.dtype), B, H, N, D, _img_desc(img),
+                                           scale.data_ptr(), L.ptr(kv_lens), L.stream_ptr(v.device)), "sage_quant_v_mxfp4")
+
+
+@quant_v_mxfp4.register_fake
+def _(v, img, scale, kv_lens, tensor_layout):
+    return None
+
+
+@torch.library.custom_op(f"{_NS4}::kv_cache_append_v4", mutates_args=("k8", "k_scale", "v4", "v4_scale"))
+def kv_cache_append_v4(k: torch.Tensor, v: torch.Tensor, km: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor,
+                       v4: torch.Tensor, v4_scale: torch.Tensor, start_lens: torch.Tensor, kv_lens: torch.Tensor,
+                       max_new: int, tensor_layout: str, qk_quant_gran: str) -> None:
+    """sage_kv_cache_append_v4 on the tensors of a cache: one launch for K and the image"""
+    B, H, N, D = L.dims(k, tensor_layout)
+    gran, rnd = core._k_pairing(qk_quant_gran)
+    with torch.cuda.device(k.device):
+        L.check(L.lib().sage_kv_cache_append_v4(
+            L.desc(k, tensor_layout), L.desc(v, tensor_layout), L.dtype_code(k.dtype), B, H, N, D, km.data_ptr(),
+            L.desc(k8, tensor_layout), k_scale.data_ptr(), gran, rnd, _img_desc(v4), v4_scale.data_ptr(), start_lens.data_ptr(),
+            kv_lens.data_ptr(), int(max_new), L.stream_ptr(k.device)), "sage_kv_cache_append_v4")
+
+
+@kv_cache_append_v4.register_fake
+def _(k, v, km, k8, k_scale, v4, v4_scale, start_lens, kv_lens, max_new, tensor_layout, qk_quant_gran):
+    return None
+
+
+def _register_attn_v4(name, causal, with_lse):
+    """attn_splitkv[_causal]_v4[_lse]: sage_attn_fusedq_pv_f4_splitkv[_causal] on the operands of a cache -- the workspace, the
+    attention launch over the splits and the merge; num_splits 0 = ``core.splitkv_num_splits``; o is contiguous in q's shape"""
+    params = ("Tensor q, Tensor k8, Tensor k_scale, Tensor km, Tensor v4, Tensor v4_scale, Tensor? kv_lens, SymInt num_splits, "
+              + "SymInt q_fold, " * causal + "str tensor_layout, float sm_scale, str qk_quant_gran")
+
+    def body(q, k8, k_scale, km, v4, v4_scale, kv_lens, num_splits, *rest):
+        tensor_layout, sm_scale, qk_quant_gran = rest[-3:]
+        B, Hq, M, D = L.dims(q, tensor_layout)
+        _, Hk, N, _ = L.dims(k8, tensor_layout)
+        num_splits = num_splits or core.splitkv_num_splits(B, Hq, M, N)
+        with torch.cuda.device(q.device):
+            q = core._abi_view(q)  # (a view the C ABI cannot address travels as a contiguous copy, as in the operators)
+            lib = L.lib()
+            o = torch.empty(q.size(), dtype=q.dtype, device=q.device)
+            lse = torch.empty((B, Hq, M), dtype=torch.float32, device=q.device) if with_lse else None
+            ws = torch.empty(lib.sage_splitkv_workspace_bytes(B, Hq, M, D, num_splits), dtype=torch.uint8, device=q.device)
+            fn = "sage_attn_fusedq_pv_f4_splitkv" + "_causal" * causal
+            L.check(getattr(lib, fn)(
+                L.desc(q, tensor_layout), L.dtype_code(q.dtype), L.desc(k8, tensor_layout), _img_desc(v4), L.desc(o, tensor_layout),
+                L.dtype_code(o.dtype), k_scale.data_ptr(), km.data_ptr(), v4_scale.data_ptr(), L.ptr(lse), B, Hq, Hk, M, N, D,
+                core._GRAN_CODE[qk_quant_gran], 32, float(sm_scale), L.ptr(kv_lens), num_splits,
+                *((int(rest[0]),) if causal else ()), ws.data_ptr(), ws.numel(), L.stream_ptr(q.device)), fn)
+        return (o, lse) if with_lse else o
+
+    def fake(q, k8, k_scale, km, v4, v4_scale, kv_lens, num_splits, *rest):
+        o = q.new_empty(q.shape)
+        return (o, _lse_like(q, rest[-3])) if with_lse else o
+
+    op = torch.library.custom_op(f"{_NS4}::{name}", body, mutates_args=(),
+                                 schema=f"({params}) -> {'(Tensor, Tensor)' if with_lse else 'Tensor'}")
+    op.register_fake(fake)
+    return op
+
+
+attn_splitkv_v4 = _register_attn_v4("attn_splitkv_v4", False, False)
+attn_splitkv_v4_lse = _register_attn_v4("attn_splitkv_v4_lse", False, True)
+attn_splitkv_causal_v4 = _register_attn_v4("attn_splitkv_causal_v4", True, False)
+attn_splitkv_causal_v4_lse = _register_attn_v4("attn_splitkv_causal_v4_lse", True, True)
