@@ -56,8 +56,11 @@
  * lengths, causal alignment and q_fold, and the same arithmetic for P, the row sums and the LSE in the same order -- lse is
  * bit-identical to the FP8 form's on the same K operands.  There is no per-channel V scale in the epilogue.
  *
- * NOT BUILT: paged caches; the uncached and dense operators (their pre-pass reads fp16 V: no bytes are saved); FP4 / FP6
- * for P or for Q / K (which would also double the MFMA rate); V smoothing.
+ * The image for a cache kept in pages: sageattn_hip_paged_fp4.h.
+ *
+ * NOT BUILT: an FP4 image for the paged cache without fp16 pools (sageattn_hip_paged_rows.h: it would need an fp16 V tail per
+ * sequence) and the shared-prefix operator on the paged FP4 cache; the uncached and dense operators (their pre-pass reads
+ * fp16 V: no bytes are saved); FP4 / FP6 for P or for Q / K (which would also double the MFMA rate); V smoothing.
  */
 #ifndef SAGEATTN_HIP_FP4_H
 #define SAGEATTN_HIP_FP4_H

@@ -173,14 +173,21 @@ FP4_SIGNATURES = {
                                                    is_causal=False, quant=_QUANT["fusedq"]),
 }
 
+# include/sageattn_hip_paged_fp4.h: the two of sageattn_hip_paged.h that have a V image, with (img_pool, scale_pool) in the place
+# of (v8_pool, v_coef) and (v_img_pool, ..., v_img_scale_pool) in the place of (v8_pool, ..., v_scale)
+PAGED_FP4_SIGNATURES = {
+    "sage_kv_cache_append_paged_v4": PAGED_SIGNATURES["sage_kv_cache_append_paged"],
+    "sage_attn_fusedq_pv_f4_splitkv_paged": (_I, _F4_OPERANDS + _PAGED_TAIL),
+}
+
 
 def bind(cdll, missing_ok=True):
     """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
-    PREFIX_SIGNATURES and FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    PREFIX_SIGNATURES, FP4_SIGNATURES and PAGED_FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
-                              **PREFIX_SIGNATURES, **FP4_SIGNATURES}.items():
+                              **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -31,7 +31,9 @@
   // that lambda in EVERY kernel, and the FP8 head_dim-64 block-sparse kernels then come out with other instruction streams.
 #ifdef SAGE_ATTN_BODY_PV_FP4
   constexpr bool PV_FP4 = true;
-  static_assert(PV_FP8 && SPLITKV && !PAGED && NWAVES == 4, "FP4 V: the 4-wave split-KV kernels on top of the FP8 mode");
+  // (PAGED as well: attn_i8_splitkv_paged_v4_kernel / attn_i8_splitkv_causal_paged_v4_kernel, sage_attn_splitkv_paged_v4.hip; the
+  //  rule: include/sageattn_hip_paged_fp4.h -- the image and the scale bytes are pools of pages, marked PV_FP4 && PAGED below)
+  static_assert(PV_FP8 && SPLITKV && NWAVES == 4, "FP4 V: the 4-wave split-KV kernels on top of the FP8 mode");
 #else
   constexpr bool PV_FP4 = false;
 #endif
@@ -444,6 +446,11 @@
     pg_klast = (unsigned)(last_r * (int)p.ksn + D);
     pg_vfull = PV_FP8 ? (unsigned)((D - 1) * (int)p.vsn + 64) : (unsigned)((63 * (int)p.vsn + D) * 2);
     pg_vlast = PV_FP8 ? pg_vfull : (unsigned)((last_r * (int)p.vsn + D) * 2);
+#ifdef SAGE_ATTN_BODY_PV_FP4
+    // the image pool [P,Hk,D,32*tpp]: a tile is 32 bytes of every channel row.  The ragged tile needs no shorter descriptor, as
+    // in the FP8 mode: the append wrote its zero nibbles
+    if constexpr (PV_FP4) pg_vfull = pg_vlast = (unsigned)((D - 1) * (int)p.vsn + 32);
+#endif
   }
   // K(j) -> K buffer `buf` (PAGED: out of page `page`)
   auto dma_k = [&](const int j, const int buf, const int page = 0) __attribute__((always_inline)) {
@@ -470,6 +477,12 @@
       const v4i rs = make_rsrc_uniform(base, j == last_t ? pg_vlast : pg_vfull);
 #pragma unroll
       for (int i = 0; i < VC; ++i) {
+#ifdef SAGE_ATTN_BODY_PV_FP4
+        if constexpr (PV_FP4) {  // every wave copies, as below: at head_dim 64 waves 2 and 3 repeat the chunks of waves 0 and 1
+          lds_dma16_fresh(rs, (unsigned)(RING * KBYTES + buf * VBYTES + ((wave * 64 + i * T) % (VROWS * VCH)) * 16), v_voff[i], 0);
+          continue;
+        }
+#endif
         if (!(VC * T == VROWS * VCH || wave * 64 + i * T < VROWS * VCH)) continue;
         lds_dma16_fresh(rs, (unsigned)(RING * KBYTES + buf * VBYTES + (wave * 64 + i * T) * 16), v_voff[i], 0);
       }
@@ -511,13 +524,28 @@
   (void)vs4; (void)vs_head; (void)vs_lane;
   if constexpr (PV_FP4) {
     v_rd8[0] = v_rd8[1] = v_lds + (r * 32 + ((hh ^ ((r >> 3) & 1)) << 4));
+    if constexpr (PAGED) {
+      // the scale pool [P,Hk,tpp,2*D]: vs_head is head hk of page 0; the tile's page comes with the call (below)
+      vs_head = reinterpret_cast<const uint8_t*>(p.v_scale) + (int64_t)hk * ((2 * D) << p.bt_shift);
+    } else {
     vs_head = reinterpret_cast<const uint8_t*>(p.v_scale) + (((int64_t)b * p.Hk + hk) * ((p.N + 63) >> 6) + sk_t0) * (2 * D);
     if constexpr (D == 128) vs4 = *reinterpret_cast<const int*>(vs_head + vs_lane);  // tile 0 (the compiler's own wait)
     else vs4 = *reinterpret_cast<const uint16_t*>(vs_head + vs_lane);
+    }
   }
-  auto load_vscale = [&](const int j) __attribute__((always_inline)) {  // scale bytes of tile j of the moved operands -> vs4
+  // PAGED: the 2 * D bytes of tile j lie in the page the tile's copies come from: scale pool + page * page stride + hk * head
+  // stride + (tile in page) * 2 * D, a 64-bit address formed on the scalar unit like the descriptors of the copies.  `page` is
+  // the id the loop already holds (bw1, requested an iteration ahead and clamped like every read-ahead).  The counted waits
+  // hold as they are: the address is scalar arithmetic on a value that has landed -- no vector-memory operation and no scalar
+  // load is added, so a wave still issues NDMA copies and this one load per tile, in the same order.
+  auto vscale_at = [&](const int j, const int page) __attribute__((always_inline)) -> const uint8_t* {
+    if constexpr (PAGED)
+      return vs_head + (int64_t)page * ((int64_t)p.Hk * ((2 * D) << p.bt_shift)) + ((sk_t0 + j) & pg_tmask) * (2 * D);
+    else return vs_head + (int64_t)j * (2 * D);
+  };
+  auto load_vscale = [&](const int j, const int page = 0) __attribute__((always_inline)) {  // scale bytes of tile j of the moved operands -> vs4
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint8_t* const tp = vs_head + (int64_t)j * (2 * D);
+    const uint8_t* const tp = vscale_at(j, page);
     if constexpr (D == 128) asm volatile("global_load_dword %0, %1, %2" : "+v"(vs4) : "v"(vs_lane), "s"(tp) : "memory");
     else asm volatile("global_load_ushort %0, %1, %2" : "+v"(vs4) : "v"(vs_lane), "s"(tp) : "memory");
 #endif
@@ -919,6 +947,13 @@
 #pragma unroll
     for (int i = 0; i < 5; ++i) bs_first[i] = page_at(i);
   }
+#ifdef SAGE_ATTN_BODY_PV_FP4
+  if constexpr (PV_FP4 && PAGED) {  // the scale bytes of tile 0, out of the first page (the compiler's own wait, as above)
+    const uint8_t* const tp = vscale_at(0, bs_first[0]);
+    if constexpr (D == 128) vs4 = *reinterpret_cast<const int*>(tp + vs_lane);
+    else vs4 = *reinterpret_cast<const uint16_t*>(tp + vs_lane);
+  }
+#endif
   if constexpr (SPARSE) {
     if constexpr (RING == 2) {
       dma_k(bs_first[0], 0);
@@ -1186,7 +1221,10 @@
       }
 #undef SAGE_FENCE
 #ifdef SAGE_ATTN_BODY_PV_FP4
-      if constexpr (NEXT != 2) load_vscale(min(j + 1, last_tile));  // behind the last MFMA that reads vs4
+      if constexpr (NEXT != 2) {  // behind the last MFMA that reads vs4
+        if constexpr (PAGED) load_vscale(min(j + 1, last_tile), bw1);  // (bw1: the page of that tile)
+        else load_vscale(min(j + 1, last_tile));
+      }
 #endif
       if constexpr (NEXT != 2) {
         float mx;

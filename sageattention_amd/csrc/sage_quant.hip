@@ -21,6 +21,7 @@
 #include "../../include/sageattn_hip_paged.h"
 #include "../../include/sageattn_hip_paged_rows.h"
 #include "../../include/sageattn_hip_fp4.h"
+#include "../../include/sageattn_hip_paged_fp4.h"
 #include "sage_entry.h"
 #include "sage_fp8_kernels.h"
 #include "sage_fp4_kernels.h"
@@ -1008,6 +1009,42 @@ __global__ __launch_bounds__(256, D == 64 ? 5 : 4) void kv_cache_append_paged_ke
   }
 }
 
+// The paged cache with an MXFP4 V image (include/sageattn_hip_paged_fp4.h, sage_kv_cache_append_paged_v4).
+// The grid and the K slots of kv_cache_append_paged_kernel -- kv_append_k_tile behind the page pointer shift -- and the V
+// slots of kv_cache_append_v4_kernel in their paged form: v4_quant_unit_paged (sage_fp4_kernels.h), which looks the rows and the
+// tiles of each 64-token block up through kv_page_of.  `img` describes the pools.
+// (A kernel of its own: the instantiations of the other append kernels keep their instruction streams.)
+template <int D, bool BF16, bool TRITON>
+__global__ __launch_bounds__(256, 4) void kv_cache_append_paged_v4_kernel(const KvAppendParams a, const V4Image img,
+                                                                           const KvPageTable pt) {
+  using G = VQuantGeom<D>;
+  __shared__ unsigned int gmax[2][64];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[V4QuantGeom<D>::LDS];
+  const int h = blockIdx.y, b = blockIdx.z, H = gridDim.y;
+  const int len = kv_len_of(a.kv_lens, b, a.k.N);
+  if (len == 0) return;
+  const int t0 = min(kv_len_of(a.start_lens, b, a.k.N), len - 1) >> 6;
+  const int ntile = (len + 63) >> 6;
+  if ((int)blockIdx.x < a.k_slots) {
+    const int blk = t0 + blockIdx.x;
+    if (blk >= ntile) return;
+    QuantParams p = a.k;
+    p.N = len;
+    const int64_t page = kv_page_of(pt, b, blk);
+    const int64_t back = (blk & ((1 << pt.shift) - 1)) - blk;  // tile inside the page - logical tile (<= 0)
+    p.x += page * p.xsb + back * 64 * p.xsn - b * p.xsb;
+    p.out += page * p.osb + back * p.o_blk - b * p.osb;
+    p.scale += page * p.ss_b + back * p.ss_blk - b * p.ss_b;
+    if (p.gran == SAGE_GRAN_PER_THREAD) kv_append_k_tile<D, BF16, TRITON, true>(p, blk, h, b, H, gmax);
+    else kv_append_k_tile<D, BF16, TRITON, false>(p, blk, h, b, H, gmax);
+    return;
+  }
+  const int unit = t0 / G::BLKS + ((int)blockIdx.x - a.k_slots);
+  if (unit * G::BLKS >= ntile) return;
+  v4_quant_unit_paged<D, BF16>(a.v.v, a.v.sb, a.v.sh, a.v.sn, len, img, pt.shift,
+                               [&](const int blk) { return kv_page_of(pt, b, blk); }, unit, t0, h, lds);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The paged cache without fp16 pools (include/sageattn_hip_paged_rows.h, sage_kv_cache_append_rows_paged): the same grid and
 // the same slots in logical tiles as kv_cache_append_paged_kernel, but the rows come from the step's k_new / v_new [B,H,T,D]
@@ -1632,6 +1669,61 @@ extern "C" int sage_kv_cache_append_paged(const sage_tensor* k_pool, const sage_
   pt.shift = page_size == 64 ? 0 : page_size == 128 ? 1 : 2;
   return kv_cache_append(k_pool, v_pool, dtype, B, H, max_pages * page_size, D, km, k8_pool, k_scale_pool, gran, rounding,
                          v8_pool, v_coef, start_lens, kv_lens, max_new, &pt, num_pages, stream);
+}
+
+// ---- the paged cache with an MXFP4 V image (include/sageattn_hip_paged_fp4.h): the table's own arguments, the checks of
+// sage_kv_cache_append_v4 on the pools (the quantizer's parameters are those of one page of page_size rows), the slots of
+// kv_cache_append in logical tiles, one launch
+extern "C" int sage_kv_cache_append_paged_v4(const sage_tensor* k_pool, const sage_tensor* v_pool, int dtype, int B, int H, int D,
+                                             const void* km, const sage_tensor* k8_pool, float* k_scale_pool, int gran,
+                                             int rounding, const sage_tensor* img_pool, uint8_t* scale_pool,
+                                             const int32_t* block_table, int64_t table_stride, int max_pages, int page_size,
+                                             int num_pages, const int32_t* start_lens, const int32_t* kv_lens, int max_new,
+                                             sage_stream_t stream) {
+  if (page_size != 64 && page_size != 128 && page_size != 256) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!kv_lens_ok(block_table) || max_pages < 1 || num_pages < 1 || table_stride < max_pages) return SAGE_ERR_INVALID_ARGUMENT;
+  if ((int64_t)max_pages * page_size > INT_MAX) return SAGE_ERR_TOO_LARGE;
+  if (!km || !aligned16(km) || !kv_lens_ok(start_lens) || !kv_lens_ok(kv_lens) || max_new < 1) return SAGE_ERR_INVALID_ARGUMENT;
+  if (!tensor_ok(v_pool, 8) || !tensor_ok(img_pool, 16) || !scale_pool || !aligned16(scale_pool)) return SAGE_ERR_INVALID_ARGUMENT;
+  if (img_pool->stride_n < page_size / 2) return SAGE_ERR_INVALID_ARGUMENT;  // a row holds the page's tiles, 32 bytes each
+  if (gran != SAGE_GRAN_PER_BLOCK && gran != SAGE_GRAN_PER_THREAD) return SAGE_ERR_INVALID_ARGUMENT;  // the K granularities
+  if (B <= 0) return SAGE_ERR_INVALID_ARGUMENT;
+  // the attention kernel addresses a (page, head) slice of the image through a 32-bit offset
+  if ((int64_t)D * img_pool->stride_n + page_size / 2 >= ((int64_t)1 << 31)) return SAGE_ERR_TOO_LARGE;
+  QuantCall c;
+  if (const int s = quant_check(c, k_pool, dtype, num_pages, H, page_size, D, km, k8_pool, k_scale_pool, gran, 1, 64, 64, 1.0f,
+                                rounding, nullptr, 1, nullptr))
+    return s;
+  const int N = max_pages * page_size;
+  c.p.N = N;
+  KvAppendParams a;
+  a.k = c.p;
+  a.v = VPrepParams();
+  a.v.v = (const uint16_t*)v_pool->data; a.v.sb = v_pool->stride_b; a.v.sh = v_pool->stride_h; a.v.sn = v_pool->stride_n;
+  a.v_coef = nullptr;
+  a.start_lens = start_lens;
+  a.kv_lens = kv_lens;
+  const int ntile = (N + 63) / 64;
+  a.k_slots = std::min((std::min(max_new, N) + 63) / 64 + 1, ntile);  // as kv_cache_append
+  const int blks = by_dim(D, [](auto d) { return VQuantGeom<decltype(d)::value>::BLKS; });
+  const int v_slots = blks == 1 ? a.k_slots : std::min(a.k_slots / blks + 1, (ntile + blks - 1) / blks);
+  V4Image o;
+  o.img = (uint8_t*)img_pool->data; o.ob = img_pool->stride_b; o.oh = img_pool->stride_h; o.od = img_pool->stride_n;
+  o.scale = scale_pool; o.sh = (int64_t)(page_size / 64) * 2 * D; o.sb = o.sh * H;
+  KvPageTable pt;
+  pt.table = block_table;
+  pt.stride = table_stride;
+  pt.shift = page_size == 64 ? 0 : page_size == 128 ? 1 : 2;
+  launch_begin();
+  by_dim(D, [&](auto d) {
+    by_flag(c.bf16, [&](auto bf) {
+      by_flag(rounding == SAGE_ROUND_TRITON, [&](auto tr) {
+        hipLaunchKernelGGL((kv_cache_append_paged_v4_kernel<decltype(d)::value, decltype(bf)::value, decltype(tr)::value>),
+                           dim3(a.k_slots + v_slots, H, B), dim3(256), 0, (hipStream_t)stream, a, o, pt);
+      });
+    });
+  });
+  return launch_status();
 }
 
 // ---- paged KV cache without fp16 pools (include/sageattn_hip_paged_rows.h): every check, then one launch

@@ -15,8 +15,11 @@ The K half (``k8``, ``k_scale``, the frozen ``km``) is that of ``SageKVCache``, 
 ``torch.ops.sageattention_amd_fp4`` (ops.py); everything traces under ``torch.compile(fullgraph=True)`` and captures into a
 HIP graph.
 
-Not built: paged caches; the uncached and dense operators (their pre-pass reads fp16 V, so no bytes are saved); FP4 / FP6 for
-P or for Q / K (which would also double the MFMA rate); V smoothing."""
+The same image for a cache kept in pages: ``SagePagedKVCacheV4`` (paged_fp4.py).
+
+Not built: an FP4 image for ``SagePagedRowCache`` and the shared-prefix operator on the paged FP4 cache; the uncached and dense
+operators (their pre-pass reads fp16 V, so no bytes are saved); FP4 / FP6 for P or for Q / K (which would also double the MFMA
+rate); V smoothing."""
 from typing import Any, Optional
 
 import torch
