@@ -17,6 +17,7 @@ from .paged_rows import SagePagedRowCache  # ... that owns every pool and takes 
 from .prefix import sageattn_splitkv_paged_prefix  # ... with a prefix the sequences share, stored and read once
 from .fp4 import quant_v_mxfp4, SageKVCacheV4, sageattn_splitkv_v4  # the cache with V as an MXFP4 image: half the FP8 V bytes
 from .paged_fp4 import SagePagedKVCacheV4, sageattn_splitkv_paged_v4  # ... that image for the cache kept in pages
+from .ragged import RaggedQPlan, ragged_q_plan, sageattn_splitkv_paged_ragged  # packed queries of a mixed batch on the paged cache
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen", "ring_sageattn",
@@ -25,5 +26,6 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "sageattn_tile_mass_kvlen", "plan_recall_kvlen", "sparge_tune_kvlen", "sageattn_splitkv", "splitkv_num_splits",
            "sageattn_splitkv_causal", "SageKVCache", "sageattn_splitkv_cached",
            "SagePagedKVCache", "sageattn_splitkv_paged", "SagePagedRowCache", "sageattn_splitkv_paged_prefix",
-           "quant_v_mxfp4", "SageKVCacheV4", "sageattn_splitkv_v4", "SagePagedKVCacheV4", "sageattn_splitkv_paged_v4"]
+           "quant_v_mxfp4", "SageKVCacheV4", "sageattn_splitkv_v4", "SagePagedKVCacheV4", "sageattn_splitkv_paged_v4",
+           "RaggedQPlan", "ragged_q_plan", "sageattn_splitkv_paged_ragged"]
 __version__ = "0.2.0"

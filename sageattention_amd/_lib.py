@@ -180,14 +180,25 @@ PAGED_FP4_SIGNATURES = {
     "sage_attn_fusedq_pv_f4_splitkv_paged": (_I, _F4_OPERANDS + _PAGED_TAIL),
 }
 
+# include/sageattn_hip_ragged.h.  The plan: cu_seqlens_q B total_tokens q_fold items n_items stream.  The attention entries: the
+# operands of the paged ones | B Hq Hk total_tokens D | qk_gran warpq sm_scale | table | kv_lens cu_seqlens_q items n_items
+# num_splits q_fold workspace workspace_bytes stream
+_RAGGED_TAIL = [_I] * 5 + _QUANT["fusedq"] + _TABLE + [_V, _V, _V, _I, _I, _I, _V, c_size_t, _V]
+RAGGED_SIGNATURES = {
+    "sage_ragged_q_plan": (_I, [_V, _I, _I, _I, _V, _I, _V]),
+    "sage_ragged_workspace_bytes": (c_size_t, [_I] * 4),
+    "sage_attn_fusedq_pv_f16_splitkv_paged_ragged": (_I, [_P, _I, _P, _P, _I, _P, _I, _V, _V, _V] + _RAGGED_TAIL),
+    "sage_attn_fusedq_pv_f8_splitkv_paged_ragged": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _RAGGED_TAIL),
+}
+
 
 def bind(cdll, missing_ok=True):
     """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
-    PREFIX_SIGNATURES, FP4_SIGNATURES and PAGED_FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES and RAGGED_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
-                              **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES}.items():
+                              **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES, **RAGGED_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

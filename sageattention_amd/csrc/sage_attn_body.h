@@ -37,6 +37,17 @@
 #else
   constexpr bool PV_FP4 = false;
 #endif
+  // RAGGED (attn_i8_splitkv_causal_paged_ragged_kernel, sage_attn_splitkv_ragged.hip, which defines the macro; the rule:
+  // include/sageattn_hip_ragged.h): packed queries [total_tokens, Hq, D] with a cu_seqlens_q on the paged causal split-KV form.
+  // A workgroup is one entry (b, qb) of a work list instead of a point of a B x nqb grid, M_ is the sequence's own T_b * g, and
+  // the fold of the GQA group into rows is done by the Q addresses.  Its statements stand under the macro for the reason given
+  // above: every other kernel keeps its text.
+#ifdef SAGE_ATTN_BODY_RAGGED
+  constexpr bool RAGGED = true;
+#else
+  constexpr bool RAGGED = false;
+#endif
+  static_assert(!RAGGED || (CAUSAL && SPLITKV && PAGED && !PV_FP4), "ragged queries: the paged causal split-KV kernel, FP16 / BF16 / FP8 P.V");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -77,6 +88,28 @@
     split = lid % p.num_splits;
     lid /= p.num_splits;
   }
+#ifdef SAGE_ATTN_BODY_RAGGED
+  // The id above the split is (head, work item), items of one head neighbours; p.nqb is the list's length.  The item names the
+  // sequence and its q-block: one scalar load, and a slot the plan left unused (b < 0) leaves before any barrier.  p.Hq counts
+  // the heads of the FOLDED view (Hq / g), p.M the packed rows total_tokens * g.  T_b is clamped so that the sequence's tokens
+  // lie inside the packed tensors whatever cu holds: no load or store below can leave them.
+  const int h = lid / p.nqb;
+  const int2 rq_item = uniform_load_i32x2(p.rq_items + 2 * (lid % p.nqb));
+  const int b = rq_item.x, qb = rq_item.y;
+  if (b < 0) return;
+  const int bh = h * p.B + b;
+  const int hk = h / (p.Hq / p.Hk);
+  const int bh_row = bh;
+  (void)bh; (void)bh_row;
+  const int rq_total = p.M / p.q_fold;
+  const int rq_lo = min(max(uniform_load_i32(p.cu_q + b), 0), rq_total);
+  const int rq_T = min(max(uniform_load_i32(p.cu_q + b + 1) - rq_lo, 0), rq_total - rq_lo);
+  int M_ = rq_T * p.q_fold, N_ = p.N;
+  if (qb * QB >= M_) return;
+  const int rq_row0 = rq_lo * p.q_fold;  // the sequence's first row of the packed, folded view
+  const int64_t q_boff = 0, k_boff = 0, v_boff = 0, o_boff = 0;  // (the non-paged, non-fused addresses: not used here)
+  (void)q_boff; (void)o_boff;
+#else
   int qb = lid % p.nqb;
   const int bh = lid / p.nqb;
   // (b, h) of the id: heads within a batch -- except with per-batch key lengths, where the batches alternate within a head.
@@ -109,6 +142,7 @@
       return;
     }
   }
+#endif
   if constexpr (KVLEN) {  // per-batch key lengths: wave-uniform, before any barrier.  Everything below follows N_ -- the tile
                           // range, the tail mask and the K / V descriptors, which end with row N_ - 1 (rows beyond read as zeros)
     N_ = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
@@ -229,7 +263,11 @@
   v4i qf[KS];
   float qsc;
   auto prepare_q = [&]() __attribute__((always_inline)) {
+#ifdef SAGE_ATTN_BODY_RAGGED
+  if constexpr (false) {  // (no INT8-Q form)
+#else
   if (p.q_f16 == nullptr) {
+#endif
     const int8_t* qp = p.q + q_boff + h * p.qsh + (int64_t)rowc * p.qsn + 16 * hh;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const v4i*>(qp + 32 * ks);
@@ -243,7 +281,15 @@
     // chunks [32*ks + 16*hh, +16) of its row: exactly the bytes of its B fragments.  Same arithmetic as K1, so q8 and
     // the scales are bit-identical to the stand-alone quantizer; rows >= M are zeros, as there.
     const bool valid = row < M_;
+#ifdef SAGE_ATTN_BODY_RAGGED
+    // row r of the folded view is head h * g + r % g of token cu[b] + r / g of q [total_tokens, Hq, D], read in place (p.qsn:
+    // the token stride, p.qsh: the head stride).  The divide is the one the diagonal pays; rows >= M_ load the last row's bytes
+    const int rq_t = valid ? row / p.q_fold : rq_T - 1;
+    const int rq_i = valid ? row - rq_t * p.q_fold : p.q_fold - 1;
+    const uint16_t* qp = p.q_f16 + (int64_t)(rq_lo + rq_t) * p.qsn + (int64_t)(h * p.q_fold + rq_i) * p.qsh + 16 * hh;
+#else
     const uint16_t* qp = p.q_f16 + q_boff + h * p.qsh + (int64_t)rowc * p.qsn + 16 * hh;
+#endif
     uint4 raw[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -290,11 +336,17 @@
     const float lse_corr = swap_sum(dot);
     // (the two forms are spelled out under `if constexpr`, as is the km pointer above: with `(!SPLITKV || split == 0)` as a term
     //  of the one condition, the FP8 head_dim-64 block-sparse kernels came out with another instruction stream)
+#ifdef SAGE_ATTN_BODY_RAGGED
+    // (lse is [total_tokens, Hq]: the slot of the row's token and un-folded head)
+    if (split == 0 && p.lse && hh == 0 && valid)
+      p.lse[(int64_t)(rq_lo + rq_t) * (p.Hq * p.q_fold) + h * p.q_fold + rq_i] = lse_corr;
+#else
     if constexpr (SPLITKV) {
       if (split == 0 && p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
     } else {
       if (p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
     }
+#endif
     if constexpr (triton) {  // rows with equal r % 8 inside the 32-row block (quant_per_thread.py:27-36)
       amax = fmaxf(amax, __shfl_xor(amax, 8));
       amax = fmaxf(amax, __shfl_xor(amax, 16));
@@ -1502,7 +1554,12 @@
     // the output type (rounded, it has the bits the epilogue below stores), and the raw base-2 LSE.  The workspace is dense:
     // a lane's run of 4 channels is one 16-byte store.
     if (row_l < M_) {
+#ifdef SAGE_ATTN_BODY_RAGGED
+      // (the workspace is indexed by packed row: [S, Hq / g, total_tokens * g])
+      const int64_t srow = ((int64_t)split * p.Hq + h) * p.M + rq_row0 + row_l;
+#else
       const int64_t srow = ((((int64_t)split * p.B + b) * p.Hq + h) * M_ + row_l);
+#endif
       float* const wp = p.sk_o + srow * D + 4 * hh_l;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)

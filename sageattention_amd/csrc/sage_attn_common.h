@@ -10,7 +10,10 @@ struct AttnParams {
   const int8_t* k; int64_t ksb, ksh, ksn;
   const uint8_t* v; int64_t vsb, vsh, vsn;  // byte pointer; strides in ELEMENTS of v's dtype
   uint16_t* o; int64_t osb, osh, osn;
-  const float* q_scale; const float* k_scale; const float* v_scale; const float* v_mean;
+  // (ragged paged split-KV -- attn_i8_splitkv_causal_paged_ragged_kernel, include/sageattn_hip_ragged.h -- has no v_mean: its work
+  //  list shares the word.  rq_items int32 [nqb][2], the pairs (sequence, q-block) of sage_ragged_q_plan, b = -1 in unused slots;
+  //  there cu_q is cu_seqlens_q, B the number of sequences, Hq the heads of the folded view, M the packed rows total_tokens * g)
+  const float* q_scale; const float* k_scale; const float* v_scale; union { const float* v_mean; const int32_t* rq_items; };
   float* lse;
   int B, Hq, Hk, M, N;
   int nqb;      // query blocks per (b,h)
@@ -181,6 +184,15 @@ __device__ __forceinline__ int uniform_load_i32(const int* ptr) {
   return *(const __attribute__((address_space(4))) int*)(ptr);
 #else
   return 0;
+#endif
+}
+// (8 bytes, 8-byte aligned: one s_load_dwordx2)
+__device__ __forceinline__ int2 uniform_load_i32x2(const int* ptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const v2i v = *(const __attribute__((address_space(4))) v2i*)(ptr);
+  return make_int2(v[0], v[1]);
+#else
+  return make_int2(0, 0);
 #endif
 }
 __device__ __forceinline__ float uniform_load1(const float* ptr) {
