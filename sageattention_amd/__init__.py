@@ -18,6 +18,7 @@ from .prefix import sageattn_splitkv_paged_prefix  # ... with a prefix the seque
 from .fp4 import quant_v_mxfp4, SageKVCacheV4, sageattn_splitkv_v4  # the cache with V as an MXFP4 image: half the FP8 V bytes
 from .paged_fp4 import SagePagedKVCacheV4, sageattn_splitkv_paged_v4  # ... that image for the cache kept in pages
 from .ragged import RaggedQPlan, ragged_q_plan, sageattn_splitkv_paged_ragged  # packed queries of a mixed batch on the paged cache
+from .window import sageattn_splitkv_paged_window, sageattn_splitkv_paged_ragged_window  # ... with a sliding window and sink logits
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen", "ring_sageattn",
@@ -27,5 +28,6 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "sageattn_splitkv_causal", "SageKVCache", "sageattn_splitkv_cached",
            "SagePagedKVCache", "sageattn_splitkv_paged", "SagePagedRowCache", "sageattn_splitkv_paged_prefix",
            "quant_v_mxfp4", "SageKVCacheV4", "sageattn_splitkv_v4", "SagePagedKVCacheV4", "sageattn_splitkv_paged_v4",
-           "RaggedQPlan", "ragged_q_plan", "sageattn_splitkv_paged_ragged"]
+           "RaggedQPlan", "ragged_q_plan", "sageattn_splitkv_paged_ragged",
+           "sageattn_splitkv_paged_window", "sageattn_splitkv_paged_ragged_window"]
 __version__ = "0.2.0"

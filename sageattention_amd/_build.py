@@ -45,6 +45,8 @@ SOURCES = [
     ("sage_attn_splitkv_paged_v4.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     # ragged queries on the paged cache: the work list, the causal paged kernel on packed queries and its merge
     ("sage_attn_splitkv_ragged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
+    # sliding window and sink logits on the paged cache: the causal paged kernel and its ragged twin with a two-sided limit
+    ("sage_attn_splitkv_window.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -102,6 +104,7 @@ def _check_occupancy(src, compiler_output):
                             re.search(r"attn_i8_splitkv_paged_kernelILi64E(Lb[01]E){3}EE", name) or       # ... out of pages
                             re.search(r"attn_i8_splitkv_causal_paged_kernelILi64E(Lb[01]E){3}EE", name) or
                             re.search(r"attn_i8_splitkv_causal_paged_ragged_kernelILi64E(Lb[01]E){3}EE", name) or  # ... packed queries
+                            re.search(r"attn_i8_splitkv_causal_paged(_ragged)?_window_kernelILi64E(Lb[01]E){3}EE", name) or  # ... windowed
                             re.search(r"attn_i8_splitkv(_causal)?_v4_kernelILi64ELb[01]EEE", name) or     # ... on the FP4 V image
                             re.search(r"attn_i8_splitkv(_causal)?_paged_v4_kernelILi64ELb[01]EEE", name) or  # ... in pages
                             # ... with the P.V skip; not its two bf16-V variants (172 / 176: two waves)
@@ -180,6 +183,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_fp4.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged_fp4.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_ragged.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_window.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -226,6 +230,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_v4.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_paged_v4.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_ragged.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_window.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -191,14 +191,21 @@ RAGGED_SIGNATURES = {
     "sage_attn_fusedq_pv_f8_splitkv_paged_ragged": (_I, [_P, _I, _P, _P, _P, _I, _V, _V, _V, _V] + _RAGGED_TAIL),
 }
 
+# include/sageattn_hip_window.h: the paged and the ragged attention entries, each followed by window sinks
+WINDOW_SIGNATURES = {
+    f"{name}_window": (res, args + [_I, _V])
+    for name, (res, args) in {**PAGED_SIGNATURES, **RAGGED_SIGNATURES}.items() if name.startswith("sage_attn_")
+}
+
 
 def bind(cdll, missing_ok=True):
     """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
-    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES and RAGGED_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES, RAGGED_SIGNATURES and WINDOW_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
-                              **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES, **RAGGED_SIGNATURES}.items():
+                              **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES, **RAGGED_SIGNATURES,
+                              **WINDOW_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

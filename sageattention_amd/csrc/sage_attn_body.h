@@ -48,6 +48,18 @@
   constexpr bool RAGGED = false;
 #endif
   static_assert(!RAGGED || (CAUSAL && SPLITKV && PAGED && !PV_FP4), "ragged queries: the paged causal split-KV kernel, FP16 / BF16 / FP8 P.V");
+  // WINDOW (attn_i8_splitkv_causal_paged_window_kernel and its ragged twin, sage_attn_splitkv_window.hip, which defines the macro
+  // and the int `sw_window` >= 1; the rule: include/sageattn_hip_window.h): row r attends the keys t + off_b - window + 1 <= j <=
+  // t + off_b only.  The tile range of a q-block then starts at the tile of its first row's lower limit, a lane holds a lower
+  // limit beside lim_l, and the tiles that need the lower mask run in front of the fast loop.  Under the macro as above.
+#ifdef SAGE_ATTN_BODY_WINDOW
+  constexpr bool WINDOW = true;
+#define SAGE_TILE_MASKED(t) ((t) >= n_plain || (t) < sw_nlm)
+#else
+  constexpr bool WINDOW = false;
+#define SAGE_TILE_MASKED(t) ((t) >= n_plain)
+#endif
+  static_assert(!WINDOW || (CAUSAL && SPLITKV && PAGED && !PV_FP4), "sliding window: the paged causal split-KV kernel, FP16 / BF16 / FP8 P.V");
   constexpr int T = NWAVES * 64;
   constexpr int QB = NWAVES * 32;
   constexpr int KS = D / 32;          // k-steps of the int8 QK^T MFMA
@@ -168,9 +180,22 @@
   if constexpr (SPLITKV) {
     int len_b = p.N;
     if (p.kv_lens) len_b = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
+#ifdef SAGE_ATTN_BODY_WINDOW
+    // The q-block's keys lie between the lower limit of its first row and the upper limit of its last row < M: the tiles
+    // [sw_tlo, sw_tlo + sw_nt), cut into the splits' ranges like the batch's tiles otherwise.  No tile below sw_tlo is named
+    // from here on, so no table entry below max(off_b - window + 1, 0) / page_size is read.  (window <= p.N: the host clamps it)
+    const int sw_off = len_b - M_ / p.q_fold;
+    const int sw_lo = max((qb * QB) / p.q_fold + sw_off - sw_window + 1, 0);
+    const int sw_hi = min(min((qb + 1) * QB - 1, M_ - 1) / p.q_fold + sw_off, len_b - 1);
+    if (sw_hi < 0) return;
+    const int sw_tlo = sw_lo >> 6, sw_nt = (sw_hi >> 6) - sw_tlo + 1, tps_b = (sw_nt + p.num_splits - 1) / p.num_splits;
+    sk_t0 = sw_tlo + split * tps_b;
+    const int t1 = min(sk_t0 + tps_b, sw_tlo + sw_nt);
+#else
     const int ntk_b = (len_b + 63) >> 6, tps_b = (ntk_b + p.num_splits - 1) / p.num_splits;
     sk_t0 = split * tps_b;
     const int t1 = min(sk_t0 + tps_b, ntk_b);
+#endif
     if (sk_t0 >= t1) return;
     N_ = min(len_b, t1 << 6) - (sk_t0 << 6);
     if constexpr (CAUSAL) sk_off = (len_b - (sk_t0 << 6)) - M_ / p.q_fold;
@@ -256,6 +281,12 @@
     sk_tok0 = q0 / p.q_fold;
     sk_tok1 = min(q0 + 31, M_ - 1) / p.q_fold;
   }
+#ifdef SAGE_ATTN_BODY_WINDOW
+  // The FIRST key (of the moved operands) the lane's row may attend is lim_l - window + 1: no register of its own, it is formed
+  // from lim_l where a tile is masked (a row whose lim_l is held at -1 has no key whatever its lower limit is).  sw_nlm, the
+  // tiles of this wave that need the lower mask: tile j does iff 64 * j < the lower limit of the wave's last row < M
+  const int sw_nlm = (max(sk_tok1 + sk_off - sw_window + 1, 0) + 63) >> 6;
+#endif
 
   // ---- Q^T fragments (B operand), resident for the whole kernel, and the per-row q scale
   // (a lambda: it runs AFTER the first K/V tile copies have been issued, below -- nothing in it depends on them, and with
@@ -777,10 +808,26 @@
     int lim;
     if constexpr (CAUSAL && SPLITKV) lim = min(N_ - 1, lim_l) - (j << 6) - 4 * hh_l;
     else lim = min(N_ - 1, CAUSAL ? row_l : 0x7fffffff) - (j << 6) - 4 * hh_l;
+#ifdef SAGE_ATTN_BODY_WINDOW
+    // two-sided, lo <= key <= lim, in two passes of the same select so that only one limit is live at a time; the lower one
+    // where the tile needs it (wave uniform).  A tile that needs neither limit keeps every bit
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) <= lim) ? s[mt][e] : kMaskedI;
+    if (j < sw_nlm) {
+      const int lo = lim_l - (sw_window - 1) - (j << 6) - 4 * hh_l;
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) >= lo) ? s[mt][e] : kMaskedI;
+    }
+#else
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) <= lim) ? s[mt][e] : kMaskedI;
+#endif
   };
   auto mask_scores = [&](const uint32_t bits, v16i (&s)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1172,7 +1219,7 @@
             sb[mt] = ks == 0 ? mfma_s_first(kf, qf[ks]) : __builtin_amdgcn_mfma_i32_32x32x32_i8(kf, qf[ks], sb[mt], 0, 0, 0);
             kf = kn;
           }
-          if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(SPARSE ? bw1 : j + 1, sb); }
+          if constexpr (NEXT == 1) { if (SAGE_TILE_MASKED(j + 1)) mask_limit(SPARSE ? bw1 : j + 1, sb); }
           mx_cur = row_max(sb, b0, b1);
         }
       }
@@ -1247,7 +1294,7 @@
       p_sum();
       l_run += psum;
       // P.V beside the row max of S(j+1)
-      if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(SPARSE ? bw1 : j + 1, sb); }
+      if constexpr (NEXT == 1) { if (SAGE_TILE_MASKED(j + 1)) mask_limit(SPARSE ? bw1 : j + 1, sb); }
       int mxa = sb[0][0], mxb = sb[0][2];
 #if defined(SAGE_ATTN_BODY_PV_FP4) && defined(__HIP_DEVICE_COMPILE__)
       // the scale bytes of this tile have landed: only this iteration's copies are younger
@@ -1397,7 +1444,7 @@
       }
       // tail: P.V of quarter 3 beside the row max of S(j+1)
       p_sum(3, pf);
-      if constexpr (NEXT == 1) { if (j + 1 >= n_plain) mask_limit(SPARSE ? bw1 : j + 1, sb); }
+      if constexpr (NEXT == 1) { if (SAGE_TILE_MASKED(j + 1)) mask_limit(SPARSE ? bw1 : j + 1, sb); }
       int mxa = sb[0][0], mxb = sb[0][2];
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
@@ -1440,6 +1487,52 @@
   float nsc0 = 0.f, nsc1 = 0.f;
   int j = 0;
   constexpr std::integral_constant<int, 0> kPlainNext{};
+#ifdef SAGE_ATTN_BODY_WINDOW
+  // The left prologue.  Tile 0 got both limits above; iteration j masks tile j + 1, so the tiles 1 .. sw_nlm - 1 take sw_nlm - 1
+  // iterations with run-time ring slots in front of the fast loop: the stream of the wave's last tiles (NEXT = 1), or at FP8 PV
+  // and head_dim 128 the compiler-scheduled body, for the reason given at STREAM_TAIL below.  The fast loop's slots are
+  // compile-time constants that start at 0, so the count is rounded up to a multiple of the ring -- masking a tile that needs
+  // none changes no bit -- or, where the wave has no more tiles than that, to all but its last: the fast loop is then empty
+  // (n_fast <= wave_tiles - 1) and the tail goes on from there.  These iterations copy like every other one and drain every
+  // copy, so the counted waits of the four-slot ring hold behind them.  The read pointers go back to slot 0.
+  {
+    const int sw_nl = sw_nlm > 1 ? min((sw_nlm - 1 + RING - 1) / RING * RING, wave_tiles - 1) : 0;
+    if constexpr (!(PV_FP8 && D == 128)) {
+      for (; j < sw_nl; ++j) {
+        fast_iter(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, j, s_cur, s_nxt, sc0, sc1, nsc0, nsc1);
+        s_cur[0] = s_nxt[0]; s_cur[1] = s_nxt[1];
+        sc0 = nsc0; sc1 = nsc1;
+      }
+    } else {
+      for (; j < sw_nl; ++j) {  // (the tail body below with a successor; RING == 4 here)
+        maybe_rescale(mx_cur);
+        dma_k(min(j + RING, last_tile), j % RING, page_at(j + RING));
+        load_v(min(j + RING - 1, last_tile), (j + RING - 1) % RING, page_at(j + RING - 1));
+        tile_scales(j + 1, nsc0, nsc1, page_at(j + 1));
+        qk((j + 1) % RING, s_nxt);
+        if (SAGE_TILE_MASKED(j + 1)) mask_limit(j + 1, s_nxt);
+        softmax_pv(j, j % RING, s_cur, sc0, sc1, std::true_type{});
+        mx_cur = row_max(s_nxt, nsc0, nsc1);
+        dma_wait_all();
+        __syncthreads();
+        s_cur[0] = s_nxt[0]; s_cur[1] = s_nxt[1];
+        sc0 = nsc0; sc1 = nsc1;
+      }
+      if (sw_nl > 0) {  // what the fast loop holds an iteration ahead: the scales of tile j + 1 and the pages of tiles j + 1 .. j + 4
+        bw1 = page_at(j + 1); bw2 = page_at(j + 2); bw3 = page_at(j + 3); bw4 = page_at(j + 4);
+        kk_nxt = load_kscales(min(j + 1, ntiles - 1), bw1);
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) k_rd[ks] -= k_slot * KBYTES;
+    if constexpr (PV_FP8) { v_rd8[0] -= v_slot * VBYTES; v_rd8[1] -= v_slot * VBYTES; }
+    else {
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) v_rd[dt] -= v_slot * VBYTES;
+    }
+    k_slot = v_slot = 0;
+  }
+#endif
   if constexpr (RING == 4) {
     // four-slot ring: the slot pattern repeats every four tiles
     for (; j + 3 < n_fast; j += 4) {
@@ -1524,7 +1617,7 @@
         const int jt = tile_at(j + 1);
         tile_scales(jt, nsc0, nsc1, page_at(j + 1));
         qk((j + 1) % RING, s_nxt);
-        if (j + 1 >= n_plain) mask_limit(jt, s_nxt);  // a plain last tile (N % 64 == 0, no diagonal) needs none
+        if (SAGE_TILE_MASKED(j + 1)) mask_limit(jt, s_nxt);  // a plain last tile (N % 64 == 0, no diagonal) needs none
       }
       if constexpr (PVSKIP) {
         if (pv_skip(j, mx_cur)) ++n_skipped; else softmax_pv(j, j % RING, s_cur, sc0, sc1, std::true_type{});
@@ -1652,3 +1745,4 @@
     if (p.pv_skipped && row_l == q0 && hh_l == 0)
       p.pv_skipped[((int64_t)bh_row * p.nqb + qb) * 4 + wave] = pv_rows ? n_skipped : 0;
   }
+#undef SAGE_TILE_MASKED
