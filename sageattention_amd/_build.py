@@ -47,6 +47,9 @@ SOURCES = [
     ("sage_attn_splitkv_ragged.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     # sliding window and sink logits on the paged cache: the causal paged kernel and its ragged twin with a two-sided limit
     ("sage_attn_splitkv_window.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
+    # decode attention on the paged cache: one wave per split, a kernel text of its own (contraction off: it has the bits of
+    # the causal paged split-KV kernel)
+    ("sage_attn_decode.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -184,6 +187,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_paged_fp4.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_ragged.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_window.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -231,6 +235,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_paged_v4.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_ragged.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_window.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_decode.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -290,6 +290,24 @@ def sageattn_splitkv_paged(q: torch.Tensor, cache: SagePagedKVCache, block_table
     if isinstance(causal, torch.Tensor) or not isinstance(causal, (bool, int)):
         raise TypeError(f"causal must be a bool, got {type(causal).__name__}")
     causal = bool(causal)
+    block_table, kv_lens, ns, M = _attn_front(q, cache, block_table, kv_lens, num_splits, causal, q_fold, refused)
+    D = cache.head_dim
+    B, Hq = L.dims(q, cache.tensor_layout)[:2]
+    if num_splits is None:  # (from the logical capacity: the pool's third dim is one page)
+        ns = core.splitkv_num_splits(B, Hq, M, block_table.size(1) * cache.page_size)
+    if sm_scale is None:
+        sm_scale = D ** -0.5
+    fp8 = cache.pv == "fp8"
+    fold = (q_fold,) if causal else ()
+    op = getattr(torch.ops.sageattention_amd_paged,
+                 f"attn_splitkv{'_causal' if causal else ''}_paged{'_lse' if return_lse else ''}")
+    return op(q, cache.k8, cache.k_scale, cache.km, cache.v8 if fp8 else cache.v, cache.v_scale if fp8 else None, block_table,
+              kv_lens, ns, *fold, cache.tensor_layout, float(sm_scale), cache.qk_quant_gran)
+
+
+def _attn_front(q, cache, block_table, kv_lens, num_splits, causal, q_fold, refused):
+    """The argument checks of ``sageattn_splitkv_paged`` behind the cache's type, shared with ``sageattn_decode_paged``
+    (decode.py) so that both refuse in the same words.  -> (block_table, kv_lens, num_splits or the contiguous rule's value, M)"""
     op_name = "sageattn_splitkv_causal" if causal else "sageattn_splitkv"
     block_table = _check_block_table(block_table, q.size(0), cache.device)
     # (shapes only: a cache without fp16 pools has its INT8 K pool in their shape)
@@ -313,13 +331,4 @@ def sageattn_splitkv_paged(q: torch.Tensor, cache: SagePagedKVCache, block_table
         raise ValueError(f"num_qo_heads ({Hq}) must be divisible by num_kv_heads ({Hk})")
     if cache.km.size(0) != B:
         raise ValueError(f"q has {B} sequences, the cache {cache.km.size(0)}")
-    if num_splits is None:  # (from the logical capacity: the pool's third dim is one page)
-        ns = core.splitkv_num_splits(B, Hq, M, block_table.size(1) * cache.page_size)
-    if sm_scale is None:
-        sm_scale = D ** -0.5
-    fp8 = cache.pv == "fp8"
-    fold = (q_fold,) if causal else ()
-    op = getattr(torch.ops.sageattention_amd_paged,
-                 f"attn_splitkv{'_causal' if causal else ''}_paged{'_lse' if return_lse else ''}")
-    return op(q, cache.k8, cache.k_scale, cache.km, cache.v8 if fp8 else cache.v, cache.v_scale if fp8 else None, block_table,
-              kv_lens, ns, *fold, cache.tensor_layout, float(sm_scale), cache.qk_quant_gran)
+    return block_table, kv_lens, ns, M
