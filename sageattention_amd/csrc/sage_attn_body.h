@@ -203,8 +203,23 @@
   // block-sparse: the list row of this (b, h, q-block) = its count, then the ascending tile indices, padded with the last
   // valid one for kBlockListPad entries so that every read-ahead below is blind.  The first entries are requested together
   // with the count: one scalar round trip in front of the first tile copies.
+  // SAGE_KS_TAIL: the tile loop issues its scalar loads -- the K scales of tile j+2 and the list entry / page that enters the
+  // window -- at the END of an iteration instead of at its head (see load_kscales); the window then holds one entry more,
+  // bw_nx, and the prologue requests six entries.  Not the windowed kernels: their head_dim-64 instantiations sit at the
+  // three-waves-per-SIMD line, and with the loads at the end one of them spilled (24 bytes of scratch); with the scale load
+  // alone there another took 180 registers.  A preprocessor switch and not a constant: register allocation of these
+  // instantiations follows the program text, dead statements included.
+#ifdef SAGE_ATTN_BODY_WINDOW
+#define SAGE_KS_TAIL 0
+#else
+#define SAGE_KS_TAIL 1
+#endif
   const int* bsl = nullptr;
+#if SAGE_KS_TAIL
+  int bs_count = 0, bs_first[6] = {0, 0, 0, 0, 0, 0};
+#else
   int bs_count = 0, bs_first[5] = {0, 0, 0, 0, 0};
+#endif
   float pv_thr = 0.f;  // PVSKIP: the head's threshold (sage_attn_*_blocksparse_pvskip), in base-2 logit units below
   (void)pv_thr;
   if constexpr (SPARSE) {
@@ -213,7 +228,7 @@
     if constexpr (PVSKIP) pv_thr = uniform_load1(p.pv_thresh + h);
     ++bsl;
 #pragma unroll
-    for (int i = 0; i < 5; ++i) bs_first[i] = uniform_load_i32(bsl + i);
+    for (int i = 0; i < 5 + SAGE_KS_TAIL; ++i) bs_first[i] = uniform_load_i32(bsl + i);  // (position 5 <= count + kBlockListPad - 1)
     if constexpr (KVLEN) {
       // The list is the caller's, made for N keys and read-only: of a batch that ends earlier only the entries < ntk_b =
       // ceil(len_b / 64) count, and the list ascends, so they are a prefix.  Its length by a ballot count over the row: every
@@ -734,7 +749,11 @@
   };
   // dequantisation scales of tile j: …sm80.cu:131, 4 per 64 keys, index (c%8)/2 = 2*hh + ((reg&3)>>1)
   // wave-uniform address: the scales of a tile come through the scalar cache (s_load_dwordx4, lgkmcnt), not through
-  // vmcnt where they would queue behind the tile DMA.  The lane-half select is an fma with a zeroed partner
+  // vmcnt where they would queue behind the tile DMA.  Scalar loads share lgkmcnt with the LDS reads and return out of
+  // order, so while one is in flight the compiler can wait for an LDS result only with lgkmcnt(0), which waits for the
+  // scalar load as well.  The tile loop therefore issues this load at the END of an iteration, in front of the copy wait
+  // and the barrier where the wave idles anyway, never between the barrier and the first K-fragment wait of a tile: there
+  // its whole round trip would stand in front of the tile's first S MFMA.  The lane-half select is an fma with a zeroed partner
   // (x*q + z*0 is exactly x*q) instead of two v_mov + v_cndmask per scale: SGPR operands feed the VALU directly.
   float qsc_lo = 0.f, qsc_hi = 0.f;  // = hh ? (0, qsc) : (qsc, 0), set once the Q scale is known (prologue)
   // (PAGED: out of the scale row of page `page`, [P, Hk, tpp * (4 | 1)]: the same load at the same depth)
@@ -1042,9 +1061,9 @@
   auto page_at = [&](const int pos) __attribute__((always_inline)) -> int {
     if constexpr (PAGED) return uniform_load_i32(pg_row + ((sk_t0 + min(pos, last_tile)) >> p.bt_shift)); else return 0;
   };
-  if constexpr (PAGED) {  // the pages of the first five tiles, requested together: one scalar round trip in front of the first copies
+  if constexpr (PAGED) {  // the pages of the first tiles, requested together: one scalar round trip in front of the first copies
 #pragma unroll
-    for (int i = 0; i < 5; ++i) bs_first[i] = page_at(i);
+    for (int i = 0; i < 5 + SAGE_KS_TAIL; ++i) bs_first[i] = page_at(i);
   }
 #ifdef SAGE_ATTN_BODY_PV_FP4
   if constexpr (PV_FP4 && PAGED) {  // the scale bytes of tile 0, out of the first page (the compiler's own wait, as above)
@@ -1139,12 +1158,19 @@
 
   // fast loop, unrolled by two so that S(j) / S(j+1) swap roles without register copies
   float4 kk_nxt = load_kscales(SPARSE ? bs_first[1] : min(1, ntiles - 1), bs_first[1]);
-  // block-sparse: the key tiles at list positions j+1 .. j+RING, in SGPRs.  Iteration j requests the entry of position
-  // j+RING+1 next to the scale load and shifts it in at its end, so the tile of every copy and of the scale load of
-  // position j+2 is known a whole iteration before it is used: no scalar round trip in front of a copy or a K-fragment wait.
-  // PAGED: the same window holds the PAGES of the tiles min(j+1 .. j+RING, last_tile), requested and shifted the same way.
+  // block-sparse: the key tiles at list positions j+1 .. j+RING, in SGPRs, and in bw_nx the entry of position j+RING+1.
+  // Iteration j shifts the window at its end and then requests the entry of position j+RING+2 next to the scale load, so
+  // the tile of every copy and of the scale load of position j+2 is known a whole iteration before it is used: no scalar
+  // round trip in front of a copy or a K-fragment wait.
+  // PAGED: the same window holds the PAGES of the tiles min(j+1 .. j+RING+1, last_tile), requested and shifted the same way.
+  // (!SAGE_KS_TAIL: no bw_nx; iteration j requests the entry of position j+RING+1 at its head and shifts it in at its end)
+#if SAGE_KS_TAIL
+  int bw1 = bs_first[1], bw2 = bs_first[2], bw3 = bs_first[3], bw4 = bs_first[4], bw_nx = bs_first[RING + 1];
+  (void)bw1; (void)bw2; (void)bw3; (void)bw4; (void)bw_nx;
+#else
   int bw1 = bs_first[1], bw2 = bs_first[2], bw3 = bs_first[3], bw4 = bs_first[4];
   (void)bw1; (void)bw2; (void)bw3; (void)bw4;
+#endif
   int k_slot = 0, v_slot = 0;  // slots the LDS read pointers point at (moved by the run-time-slot tiles only)
   // NEXT (second tag): what follows tile j for this wave.
   //   0  a plain tile: the fast loops.  Ring slots are compile-time (R = j % RING), every LDS offset an immediate.
@@ -1161,9 +1187,9 @@
               V_WR = DYN ? (j + RING - 1) % RING : (R + RING - 1) % RING;
     // The first K fragment of S(j+1) is read BEFORE the tile copies are issued: the first S MFMA needs it at once, and the
     // copies are inline asm with a memory clobber, so the compiler cannot hoist the read across them itself (+0.2..0.8 %).
-    // scales of tile j+1 were fetched during the previous iteration; those of tile j+2 are fetched first thing here: the
-    // scalar load shares lgkmcnt with the LDS reads, so it must be in flight long before the first wait on a K fragment
-    // (left to hipcc it is issued right in front of that wait and every iteration pays a scalar-cache round trip)
+    // scales of tile j+1 were requested at the end of the previous iteration, in front of its wait and barrier (below):
+    // the scalar load shares lgkmcnt with the LDS reads, so the wait on this K fragment is an lgkmcnt(0) that also waits
+    // for every scalar load in flight -- none may be issued between the barrier and the first S MFMA
     if constexpr (DYN) {
       // run-time slots without extra address registers: the read pointers themselves move to the slots of this tile (the
       // fast loops, which need them at the region base, are over) and every offset below stays an immediate
@@ -1182,6 +1208,12 @@
       v_slot = V_RD;
     }
     v4i kf_early = qf[0];
+#if SAGE_KS_TAIL
+    if constexpr (NEXT != 2) {
+      scales_from(kk_nxt, b0, b1);
+      kf_early = *reinterpret_cast<const v4i*>(k_rd[0] + (DYN ? 0 : K_RD * KBYTES));
+    }
+#else
     int bw_in = RING == 2 ? bw2 : bw4;  // block-sparse: the entry that enters the window (the wave's last tile: none)
     if constexpr (NEXT != 2) {
       scales_from(kk_nxt, b0, b1);
@@ -1190,6 +1222,7 @@
       if constexpr (PAGED) bw_in = page_at(j + RING + 1);
       kf_early = *reinterpret_cast<const v4i*>(k_rd[0] + (DYN ? 0 : K_RD * KBYTES));
     }
+#endif
     __builtin_amdgcn_sched_barrier(0);
     maybe_rescale(mx_cur);
     if constexpr (RING == 2) {
@@ -1471,10 +1504,26 @@
     // tile's wait and barrier, where a wave idles anyway: hipcc sank it below the barrier in one of the two unrolled
     // bodies, i.e. in front of the next tile's first MFMA (C3 +1.1 %)
     __builtin_amdgcn_sched_barrier(0);
+#if !SAGE_KS_TAIL
     if constexpr (SPARSE || PAGED) {  // the window moves on by one list position
       if constexpr (RING == 2) { bw1 = bw2; bw2 = bw_in; }
       else { bw1 = bw2; bw2 = bw3; bw3 = bw4; bw4 = bw_in; }
     }
+#else
+    if constexpr (SPARSE || PAGED) {  // the window moves on by one list position
+      if constexpr (RING == 2) { bw1 = bw2; bw2 = bw_nx; }
+      else { bw1 = bw2; bw2 = bw3; bw3 = bw4; bw4 = bw_nx; }
+    }
+    // The scalar loads of the iteration stand HERE, in front of the tile's wait and barrier: the scales of tile j+2 (bw1 is
+    // its list entry / page by now) and the window entry of position j+RING+2.  Their round trip passes while the wave waits
+    // for its copies and for the other waves, and the first lgkmcnt(0) of the next tile finds them landed (see load_kscales).
+    if constexpr (NEXT != 2) {
+      kk_nxt = load_kscales(SPARSE ? bw1 : min(j + 2, ntiles - 1), bw1);
+      if constexpr (SPARSE) bw_nx = tile_at(j + RING + 2);
+      if constexpr (PAGED) bw_nx = page_at(j + RING + 2);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#endif
     if constexpr (RING == 2) {
       dma_wait_all();  // two-slot ring: every copy of this wave has landed before the barrier publishes the tiles
     } else if constexpr (DYN) {
@@ -1520,6 +1569,9 @@
       }
       if (sw_nl > 0) {  // what the fast loop holds an iteration ahead: the scales of tile j + 1 and the pages of tiles j + 1 .. j + 4
         bw1 = page_at(j + 1); bw2 = page_at(j + 2); bw3 = page_at(j + 3); bw4 = page_at(j + 4);
+#if SAGE_KS_TAIL
+        bw_nx = page_at(j + 5);
+#endif
         kk_nxt = load_kscales(min(j + 1, ntiles - 1), bw1);
       }
     }
