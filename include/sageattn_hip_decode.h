@@ -36,8 +36,10 @@
  * M > 32: SAGE_ERR_UNSUPPORTED (use sage_attn_fusedq_pv_*_splitkv_paged).  D is 64 or 128, qk_gran per warp or per thread,
  * P.V fp16, bf16 or fp8, page_size 64, 128 or 256, as there.
  *
- * NOT BUILT: the FP4 paged caches (the obvious next step: it is where the bytes matter most); the contiguous caches; the
- * ragged, window, sink and shared-prefix forms; more than 16 splits; more than 32 rows; a merge inside the attention launch.
+ * The paged MXFP4 V cache has its own entry: sageattn_hip_decode_fp4.h.
+ *
+ * NOT BUILT: the contiguous caches; the ragged, window, sink and shared-prefix forms; more than 16 splits; more than 32 rows;
+ * a merge inside the attention launch.
  */
 #ifndef SAGEATTN_HIP_DECODE_H
 #define SAGEATTN_HIP_DECODE_H

@@ -48,7 +48,7 @@ SOURCES = [
     # sliding window and sink logits on the paged cache: the causal paged kernel and its ragged twin with a two-sided limit
     ("sage_attn_splitkv_window.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     # decode attention on the paged cache: one wave per split, a kernel text of its own (contraction off: it has the bits of
-    # the causal paged split-KV kernel)
+    # the causal paged split-KV kernel), and in the same text its twin on the paged MXFP4 V cache
     ("sage_attn_decode.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
@@ -188,6 +188,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_ragged.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_window.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode_fp4.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}

@@ -205,16 +205,22 @@ DECODE_SIGNATURES = {
     for name, (res, args) in PAGED_SIGNATURES.items() if name.startswith("sage_attn_")
 }
 
+# include/sageattn_hip_decode_fp4.h: the same for the paged FP4 attention entry
+DECODE_FP4_SIGNATURES = {
+    name.replace("_splitkv_paged", "_decode_paged"): (res, args[:-len(_PAGED_TAIL)] + _DECODE_TAIL)
+    for name, (res, args) in PAGED_FP4_SIGNATURES.items() if name.startswith("sage_attn_")
+}
+
 
 def bind(cdll, missing_ok=True):
     """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
-    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES, RAGGED_SIGNATURES, WINDOW_SIGNATURES and DECODE_SIGNATURES symbol
-    ``cdll`` has and return it.  An older library
+    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES, RAGGED_SIGNATURES, WINDOW_SIGNATURES, DECODE_SIGNATURES and
+    DECODE_FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
                               **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES, **RAGGED_SIGNATURES,
-                              **WINDOW_SIGNATURES, **DECODE_SIGNATURES}.items():
+                              **WINDOW_SIGNATURES, **DECODE_SIGNATURES, **DECODE_FP4_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -22,15 +22,26 @@
 //    included: they are zero rows with the limit of their row index, as there), the row sums (on the matrix pipe for FP16 P.V
 //    at head_dim 64), P packing, the P.V accumulation order, the normalised fp32 partial and the raw base-2 LSE.  Only the
 //    placement of the instructions is this kernel's own.  The merge is splitkv_merge_kernel<.., CAUSAL = true>, unchanged.
+//
+// attn_i8_decode_paged_v4_kernel (the rule: include/sageattn_hip_decode_fp4.h) is the same text, sage_attn_decode_body.h, on the
+// paged MXFP4 V cache, with the bits of attn_i8_splitkv_causal_paged_v4_kernel.  What is its own is marked PV_FP4 there: V never
+// touches LDS.  In the image the A fragment of lane (r, hh) for channel block dt is 16 contiguous bytes of the pool -- chunk hh
+// of the 32-byte tile row of channel r + 32 * dt -- and in a one-wave workgroup no other wave wants them, so the lane loads its
+// D / 32 fragments and its scale word of tile j + 1 straight into registers, behind the last P.V MFMA of tile j.  The ring is
+// the K ring alone (16 KiB at head_dim 128), and the loads stand in the K copies' order of counted waits: NK copies, D / 32
+// fragment loads and one scale load per tile.
 #include <climits>
 #include "../../include/sageattn_hip_decode.h"
+#include "../../include/sageattn_hip_decode_fp4.h"
 #include "sage_attn_launch.h"
 
 namespace sage {
 
 constexpr int kDecodeRing = 2;       // K slots and V slots of a wave's ring
 constexpr int kDecodeMaxRows = 32;   // one wave: one 32-row MFMA block of query rows
-constexpr size_t decode_lds_bytes(int D, bool pv_fp8) { return (size_t)kDecodeRing * (64 * D + (pv_fp8 ? 64 * D : 128 * D)); }
+constexpr size_t decode_lds_bytes(int D, bool pv_fp8, bool pv_fp4 = false) {
+  return (size_t)kDecodeRing * (64 * D + (pv_fp4 ? 0 : pv_fp8 ? 64 * D : 128 * D));
+}
 
 // every LDS read the wave has issued has returned (the scalar loads in flight share the counter and land as well): in front of
 // the copies that re-fill a slot the wave has read
@@ -40,472 +51,38 @@ __device__ __forceinline__ void lds_reads_done() {
 #endif
 }
 
+// The wave is one text for both kernels (sage_attn_decode_body.h), included INTO each as the shared attention body is: as a
+// __forceinline__ device template hipcc allocated every register of the existing twelve instantiations anew.
 template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>
 __global__ __launch_bounds__(64) void attn_i8_decode_paged_kernel(const AttnParams p) {
-  static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
-  constexpr int KS = D / 32;                        // k-steps of the int8 QK^T MFMA
-  constexpr int DT = D / 32;                        // 32-wide d tiles of O^T
-  constexpr int KBYTES = 64 * D;                    // one K tile (int8)
-  constexpr int VBYTES = PV_FP8 ? 64 * D : 128 * D; // one V tile: e4m3 [D][64] or 16-bit [64][D]
-  constexpr int KCH = D / 16;                       // 16-byte chunks per K row
-  constexpr int VCH = PV_FP8 ? 4 : D / 8;           // ... per row of the V image
-  constexpr int VROWS = PV_FP8 ? D : 64;
-  constexpr int NK = 64 * KCH / 64, NV = VROWS * VCH / 64;  // copies of 64 x 16 bytes per tile
-  static_assert(kDecodeRing * (NK + NV) < 64, "the counted waits: vmcnt is a 6-bit counter");
+  constexpr bool PV_FP4 = false;
+#define SAGE_ATTN_DECODE_BODY_OF_KERNEL
+#include "sage_attn_decode_body.h"
+#undef SAGE_ATTN_DECODE_BODY_OF_KERNEL
+}
 
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const k_lds = smem;
-  char* const v_lds = smem + kDecodeRing * KBYTES;
-
-  // ---- block -> (b, h, split), XCD aware: the splits of a head are neighbours, then the batches of a head
-  const int nwg = gridDim.x;
-  int lid;
-  {
-    const int orig = blockIdx.x, xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-    lid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
-  }
-  const int split = lid % p.num_splits;
-  const int bh = lid / p.num_splits;
-  const int h = bh / p.B, b = bh % p.B;
-  const int hk = h / (p.Hq / p.Hk);
-  const int M_ = p.M;
-
-  // ---- the split's range of logical tiles and the diagonal in its coordinates (wave uniform; an empty split returns at once)
-  const int len_b = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
-  const int ntk_b = (len_b + 63) >> 6, tps_b = (ntk_b + p.num_splits - 1) / p.num_splits;
-  const int sk_t0 = split * tps_b;
-  const int t1 = min(sk_t0 + tps_b, ntk_b);
-  if (sk_t0 >= t1) return;
-  const int N_ = min(len_b, t1 << 6) - (sk_t0 << 6);         // keys from the split's first one to its end
-  const int sk_off = (len_b - (sk_t0 << 6)) - M_ / p.q_fold;  // off_b in the split's coordinates
-  const int sk_end = (M_ - 1) / p.q_fold + sk_off + 1;        // key bound of the last row < M
-  if (sk_end <= 0) return;
-  const int ntiles = (min(N_, sk_end) + 63) >> 6;
-  const int last_tile = ntiles - 1;
-  // tiles [0, n_plain) need no mask: they end before the sequence does and at or before the limit of row 0
-  int n_plain = ntiles;
-  if (N_ & 63) n_plain = min(n_plain, N_ >> 6);
-  n_plain = min(n_plain, (max(sk_off, -1) + 1) >> 6);
-
-  const int lane = threadIdx.x;
-  const int r = lane & 31, hh = lane >> 5;
-  const int row = r;
-  const int rowc = min(row, M_ - 1);
-  // the last key (of the split's coordinates) the lane's row may attend; every negative limit is held at -1
-  const int lim_l = max(row / p.q_fold + sk_off, -1);
-
-  // ---- Q^T fragments (B operand) and the row's scale: the fused Q quantizer of the shared body on the wave's 32 rows.  Lane
-  //      (r, hh) owns the 16-column chunks [32 * ks + 16 * hh, +16) of its row; rows >= M load the last row's bytes and are zeros.
-  v4i qf[KS];
-  float qsc;
-  auto prepare_q = [&]() __attribute__((always_inline)) {
-    const bool valid = row < M_;
-    const uint16_t* qp = p.q_f16 + b * p.qsb + h * p.qsh + (int64_t)rowc * p.qsn + 16 * hh;
-    uint4 raw[KS][2];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      raw[ks][0] = *reinterpret_cast<const uint4*>(qp + 32 * ks);
-      raw[ks][1] = *reinterpret_cast<const uint4*>(qp + 32 * ks + 8);
-    }
-    // the LSE correction q . k_mean: computed and parked in the caller's LSE slot by split 0 only; the merge consumes it
-    const uint16_t* kmp = (p.km && p.lse && split == 0) ? p.km + ((int64_t)b * p.Hk + hk) * D + 16 * hh : nullptr;
-    auto fused_q = [&](auto bf16_tag) __attribute__((always_inline)) {
-      constexpr bool QBF = decltype(bf16_tag)::value;
-      if (!valid) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) raw[ks][0] = raw[ks][1] = make_uint4(0u, 0u, 0u, 0u);
-      }
-      float amax = 0.f, dot = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          float f[8];
-          unpack8<QBF>(raw[ks][c], f);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
-          if (kmp) {
-            float g[8];
-            const uint4 uk = *reinterpret_cast<const uint4*>(kmp + 32 * ks + 8 * c);
-            unpack8<QBF>(uk, g);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dot += f[e] * g[e];
-          }
-        }
-      amax = swap_max(amax);  // the other half of the row
-      const float lse_corr = swap_sum(dot);
-      if (split == 0 && p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
-      if constexpr (KTHREAD) {  // per thread: rows with equal r % 8 of the 32-row block share a scale
-        amax = fmaxf(amax, __shfl_xor(amax, 8));
-        amax = fmaxf(amax, __shfl_xor(amax, 16));
-      } else {                  // per warp: warpq rows (16 or 32) share a scale
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-        if (p.warpq == 32) amax = fmaxf(amax, __shfl_xor(amax, 16));
-      }
-      const float a_c = fmaxf(amax, 0.0000001f);
-      const float sc = KTHREAD ? amax / 127.f + 0.0000001f : a_c / 127.f;
-      const float inv = 127.f / a_c;
-      const float rcp_sc = 1.0f / sc;
-      const bool rcp_bad = !(fabsf(rcp_sc) < 3.0e38f);
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        uint32_t w[4];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          float f[8];
-          unpack8<QBF>(raw[ks][c], f);
-          int qv[8];
-          if constexpr (KTHREAD) {
-            // x / sc correctly rounded before the half-away rounding: the reciprocal product unless a value of the wave's chunk
-            // lands near a rounding boundary, then the exact division decides for that chunk
-            bool near = false;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qv[e] = round_half_away_fast(f[e] * rcp_sc, near);
-            if (__builtin_amdgcn_ballot_w64(near || rcp_bad) != 0) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                float y = f[e] / sc;
-                y = y + (y >= 0.f ? 0.5f : -0.5f);
-                qv[e] = min(max((int)y, -128), 127);
-              }
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qv[e] = (int)rintf(f[e] * inv);
-          }
-          w[2 * c] = pack_i8x4(qv[0], qv[1], qv[2], qv[3]);
-          w[2 * c + 1] = pack_i8x4(qv[4], qv[5], qv[6], qv[7]);
-        }
-        qf[ks][0] = (int)w[0]; qf[ks][1] = (int)w[1]; qf[ks][2] = (int)w[2]; qf[ks][3] = (int)w[3];
-      }
-      qsc = sc * p.logit_mult;
-    };
-    if (p.q_bf16) fused_q(std::true_type{}); else fused_q(std::false_type{});
-  };
-
-  // ---- staging (pool -> LDS by LDS-DMA).  A wave instruction writes 64 x 16 bytes of LDS linearly, so the bank swizzle of
-  //      the tile image is applied to the per-lane SOURCE offset: copy i of a tile moves the chunks 64 * i + lane.
-  int k_voff[NK], v_voff[NV];
-#pragma unroll
-  for (int i = 0; i < NK; ++i) {
-    const int c = lane + 64 * i, kr = c / KCH, pos = c % KCH;
-    k_voff[i] = kr * (int)p.ksn + ((pos ^ k_swz<D>(kr)) << 4);
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = lane + 64 * i, vr = c / VCH, pos = c % VCH;
-    if constexpr (PV_FP8) {
-      v_voff[i] = vr * (int)p.vsn + ((pos ^ ((vr >> 2) & 3)) << 4);  // V^T row vr (= channel)
-    } else {
-      const int cc = (((pos >> 2) ^ v_win_swz<D>(vr)) << 2) | (pos & 3);
-      v_voff[i] = (vr * (int)p.vsn + cc * 8) * 2;
-    }
-  }
-  // Tile j of the split is logical tile sk_t0 + j of the batch: tile (sk_t0 + j) % tpp of the page that entry (sk_t0 + j) / tpp
-  // of the batch's table row names.  Its descriptor: words 0-1 the 64-bit address pool + page * page stride + hk * head stride
-  // + tile * tile bytes, word 2 the bytes of the tile -- of the batch's last tile those up to row len_b - 1, so the rows behind
-  // it reach the LDS as zeros.  Only a tile's own bytes go through a 32-bit offset.
-  const int8_t* const pg_k = p.k + hk * p.ksh;
-  const uint8_t* const pg_v = p.v + hk * p.vsh * (PV_FP8 ? 1 : 2);
-  const float* const pg_ks = p.k_scale + hk * p.ks_h;
-  const int* const pg_row = p.block_table + (int64_t)b * p.bt_stride;
-  const int pg_tmask = (1 << p.bt_shift) - 1;
-  const int last_t = (N_ - 1) >> 6, last_r = (N_ - 1) & 63;
-  const unsigned pg_kfull = (unsigned)(63 * (int)p.ksn + D), pg_klast = (unsigned)(last_r * (int)p.ksn + D);
-  const unsigned pg_vfull = PV_FP8 ? (unsigned)((D - 1) * (int)p.vsn + 64) : (unsigned)((63 * (int)p.vsn + D) * 2);
-  const unsigned pg_vlast = PV_FP8 ? pg_vfull : (unsigned)((last_r * (int)p.vsn + D) * 2);
-  // the page of the tile at position `pos`, clamped to the range's last tile: no entry at or beyond ceil(len_b / page_size) is read
-  auto page_at = [&](const int pos) __attribute__((always_inline)) -> int {
-    return uniform_load_i32(pg_row + ((sk_t0 + min(pos, last_tile)) >> p.bt_shift));
-  };
-  auto dma_k = [&](const int j, const int slot, const int page) __attribute__((always_inline)) {
-    const uint64_t base = reinterpret_cast<uint64_t>(pg_k) + (uint64_t)((int64_t)page * p.ksb) +
-                          (uint64_t)(((sk_t0 + j) & pg_tmask) * p.k_tile_bytes);
-    const v4i rs = make_rsrc_uniform(base, j == last_t ? pg_klast : pg_kfull);
-    // (the LDS offset as ONE running scalar: as known constants hipcc keeps every copy's offset of every slot in a register
-    //  of its own for the whole loop, and the scalar file overflows into VCC)
-    unsigned off = (unsigned)(slot * KBYTES);
-    asm volatile("" : "+s"(off));
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-      lds_dma16_fresh(rs, off, k_voff[i], 0);
-      off += 1024;
-    }
-  };
-  auto dma_v = [&](const int j, const int slot, const int page) __attribute__((always_inline)) {
-    const uint64_t base = reinterpret_cast<uint64_t>(pg_v) + (uint64_t)((int64_t)page * p.vsb * (PV_FP8 ? 1 : 2)) +
-                          (uint64_t)(((sk_t0 + j) & pg_tmask) * p.v_tile_bytes);
-    const v4i rs = make_rsrc_uniform(base, j == last_t ? pg_vlast : pg_vfull);
-    unsigned off = (unsigned)(kDecodeRing * KBYTES + slot * VBYTES);
-    asm volatile("" : "+s"(off));
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      lds_dma16_fresh(rs, off, v_voff[i], 0);
-      off += 1024;
-    }
-  };
-
-  // ---- lane-constant LDS read addresses (slot 0; the slot is an immediate offset)
-  const char* k_rd[KS];  // K A-fragment: row r (+ 32 * mt), chunk 2 * ks + hh
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) k_rd[ks] = k_lds + (r * D + (((2 * ks + hh) ^ k_swz<D>(r)) << 4));
-  const char* v_rd8[2];  // fp8: V^T row r (+ 32 * dt), 16-byte chunks 2 * hh and 2 * hh + 1
-#pragma unroll
-  for (int c = 0; c < 2; ++c) v_rd8[c] = v_lds + (r * 64 + (((2 * hh + c) ^ ((r >> 2) & 3)) << 4));
-  const char* v_rd[DT];  // 16-bit: V^T fragment by transposing read: row 4 * hh + q4 (+ 16 * quarter, + 8), window dt
-  {
-    const int i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3, g = (lane >> 4) & 1;
-    const int rv = 4 * hh + q4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) v_rd[dt] = v_lds + (rv * (2 * D) + ((dt ^ v_win_swz<D>(rv)) << 6) + 32 * g + 8 * p4);
-  }
-
-  // ---- state
-  v16f acc_o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc_o[dt][e] = 0.f;
-  float m_run = -1e30f;
-  float l_run = 0.f;  // the lane's partial row sum of the unrounded p (its 32 of a tile's 64 keys)
-  // FP16 P.V at head_dim 64: the row sums of the ROUNDED P on the matrix pipe, one v_mfma_f32_16x16x32_f16 per 16-key quarter
-  // with a 0 / 1 selector as A: elements 0 / 1 of the accumulator hold the sums of queries l % 16 and l % 16 + 16
-  constexpr bool MROW = !PV_FP8 && !V_BF16 && D == 64;
-  v4f l4 = {0.f, 0.f, 0.f, 0.f};
-  v8h sel8;
-  {
-    const _Float16 one = (((lane >> 4) & 1) == (lane & 1)) ? (_Float16)1.0f : (_Float16)0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sel8[e] = one;
-  }
-  // The int32 accumulator of S^T starts at the bit pattern of 1.5 * 2^23: reinterpreted as fp32 the accumulated integer IS the
-  // float 12582912 + S, so the logit needs no convert.  A masked score is the bit pattern of -inf: below every real score as an
-  // integer, and exp2 of it is exactly 0.
-  constexpr int kBiasI = 0x4B400000;
-  constexpr float kBiasF = 12582912.0f;
-  constexpr int kMaskedI = (int)0xFF800000u;
-  v16i bias;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) bias[e] = kBiasI;
-  asm volatile("" : "+v"(bias));  // resident: one wave per workgroup has registers to spare
-
-  // S^T = K . Q^T of one tile (2 x 32 keys x 32 rows) out of K slot `slot`
-  auto qk = [&](const int slot, v16i (&s)[2]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const v4i a = *reinterpret_cast<const v4i*>(k_rd[ks] + (slot * KBYTES + mt * 32 * D));
-        s[mt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, qf[ks], ks == 0 ? bias : s[mt], 0, 0, 0);
-      }
-  };
-  // dequantisation scales of a tile through the scalar cache: 4 per 64 keys (per thread) or 1, index 2 * hh + ((reg & 3) >> 1)
-  float qsc_lo = 0.f, qsc_hi = 0.f;
-  auto load_kscales = [&](const int j, const int page) __attribute__((always_inline)) -> float4 {
-    const float* sp = pg_ks + (int64_t)page * p.ks_b + ((sk_t0 + j) & pg_tmask) * p.ks_t;
-    if constexpr (KTHREAD) return uniform_load4(sp);
-    else return make_float4(uniform_load1(sp), 0.f, 0.f, 0.f);
-  };
-  auto scales_from = [&](const float4 kk, float& sc0, float& sc1) __attribute__((always_inline)) {
-    if constexpr (KTHREAD) {
-      sc0 = __builtin_fmaf(kk.z, qsc_hi, kk.x * qsc_lo);
-      sc1 = __builtin_fmaf(kk.w, qsc_hi, kk.y * qsc_lo);
-    } else {
-      sc0 = sc1 = qsc * kk.x;
-    }
-  };
-  // sequence end and diagonal: register e of block mt holds key 64 * j + 32 * mt + (e & 3) + 8 * (e >> 2) + 4 * hh
-  auto mask_limit = [&](const int j, v16i (&s)[2]) __attribute__((always_inline)) {
-    const int lim = min(N_ - 1, lim_l) - (j << 6) - 4 * hh;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) <= lim) ? s[mt][e] : kMaskedI;
-  };
-  // row max of a tile's logits from the raw integers (the scales are positive)
-  auto row_max = [&](const v16i (&s)[2], const float sc0, const float sc1) __attribute__((always_inline)) -> float {
-    int mxa = s[0][0], mxb = s[0][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        if (e & 2) mxb = max(mxb, s[mt][e]); else mxa = max(mxa, s[mt][e]);
-      }
-    float mx;
-    if constexpr (KTHREAD) mx = max_raw((__int_as_float(mxa) - kBiasF) * sc0, (__int_as_float(mxb) - kBiasF) * sc1);
-    else mx = (__int_as_float(max(mxa, mxb)) - kBiasF) * sc0;
-    return swap_max(mx);
-  };
-  // lazy rescale: only when some row's maximum grew by more than the threshold (fp8: p carries the exponent offset 8.807 - 3)
-  constexpr float kLazyThr = PV_FP8 ? 3.0f : 6.0f;
-  constexpr float kPOff = PV_FP8 ? 8.807f - 3.0f : 0.f;
-  float m_thr = m_run + kLazyThr;
-  auto maybe_rescale = [&](const float mx) __attribute__((always_inline)) {
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx > m_thr) != 0, 0)) {
-      const float m_new = fmaxf(m_run, mx);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      m_run = m_new;
-      m_thr = m_new + kLazyThr;
-      l_run *= alpha;
-      if constexpr (MROW) l4 *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc_o[dt][e] *= alpha;
-    }
-  };
-  // p = exp2(t - m) and O^T += V^T . P^T of one tile out of V slot `slot`
-  auto softmax_pv = [&](const int slot, const v16i (&s)[2], const float sc0, const float sc1) __attribute__((always_inline)) {
-    const float c0 = __builtin_fmaf(-kBiasF, sc0, kPOff - m_run), c1 = __builtin_fmaf(-kBiasF, sc1, kPOff - m_run);
-    auto prob = [&](const int mt, const int e) __attribute__((always_inline)) -> float {
-      const bool g1 = (e & 2) != 0;
-      return __builtin_amdgcn_exp2f(__builtin_fmaf(__int_as_float(s[mt][e]), g1 ? sc1 : sc0, g1 ? c1 : c0));
-    };
-    if constexpr (!PV_FP8) {
-      // quarters of 16 keys: the quarter's P pairs (row sums in pair order), then its P.V MFMAs
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int mt = q >> 1, sq = q & 1;
-        v8h pf;
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          const v2f pp = {prob(mt, 8 * sq + e), prob(mt, 8 * sq + e + 1)};
-          v2h ph;
-          if constexpr (V_BF16) ph = __builtin_bit_cast(v2h, __builtin_convertvector(pp, v2bf));
-          else ph = __builtin_convertvector(pp, v2h);
-          pf[e] = ph[0];
-          pf[e + 1] = ph[1];
-          if constexpr (!MROW) {
-            l_run += pp[0];
-            l_run += pp[1];
-          }
-        }
-        if constexpr (MROW) l4 = __builtin_amdgcn_mfma_f32_16x16x32_f16(sel8, pf, l4, 0, 0, 0);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const char* base = v_rd[dt] + (slot * VBYTES + 16 * q * (2 * D));
-          const v4s_vs lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_vs*)(base));
-          const v4s_vs hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_vs*)(base + 8 * (2 * D)));
-          v8h a;
-          a.s0123 = __builtin_bit_cast(v4h, lo);
-          a.s4567 = __builtin_bit_cast(v4h, hi);
-          if constexpr (V_BF16)
-            acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, pf), acc_o[dt], 0, 0, 0);
-          else
-            acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pf, acc_o[dt], 0, 0, 0);
-        }
-      }
-    } else {
-      // all 64 keys in one K = 64 MFMA per d tile; P^T bytes in accumulator order 16 * mt + reg
-      v8i pb;
-      float psum = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        const int mt = w >> 2, e0 = 4 * (w & 3);
-        const float p0 = prob(mt, e0), p1 = prob(mt, e0 + 1), p2 = prob(mt, e0 + 2), p3 = prob(mt, e0 + 3);
-        psum += p0; psum += p1; psum += p2; psum += p3;
-        int pk = 0;
-        pk = __builtin_amdgcn_cvt_pk_fp8_f32(p0, p1, pk, false);  // OCP e4m3, RNE
-        pk = __builtin_amdgcn_cvt_pk_fp8_f32(p2, p3, pk, true);
-        pb[w] = pk;
-      }
-      l_run += psum;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int base = slot * VBYTES + dt * 32 * 64;
-        v8i a;
-        a.s0123 = *reinterpret_cast<const v4i*>(v_rd8[0] + base);
-        a.s4567 = *reinterpret_cast<const v4i*>(v_rd8[1] + base);
-        acc_o[dt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, pb, acc_o[dt], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-      }
-    }
-  };
-
-  // ---- prologue: the pages of the first tiles in one scalar round trip, K(0), K(1) and V(0) in flight beside the Q quantizer
-  const int pg0 = page_at(0);
-  int pg1 = page_at(1), pg2 = page_at(2);  // the pages of tiles j + 1 and j + 2 (clamped) while iteration j runs
-  dma_k(0, 0, pg0);
-  if (ntiles > 1) dma_k(1, 1, pg1);
-  dma_v(0, 0, pg0);
-  prepare_q();
-  qsc_lo = hh ? 0.f : qsc;
-  qsc_hi = hh ? qsc : 0.f;
-  if (ntiles > 1) dma_wait_keep<NK + NV>(); else dma_wait_keep<NV>();  // K(0) has landed
-
-  v16i s_a[2], s_b[2];
-  float a0, a1, b0 = 0.f, b1 = 0.f, mx_cur;
-  qk(0, s_a);
-  scales_from(load_kscales(0, pg0), a0, a1);
-  if (n_plain <= 0) mask_limit(0, s_a);
-  mx_cur = row_max(s_a, a0, a1);
-  float4 kk_nxt = load_kscales(min(1, last_tile), pg1);
-
-  // Iteration j: S(j) and its row maximum are known.  SLOT = j % 2 at compile time: K(j) and V(j) live in slot SLOT, K(j + 1)
-  // and V(j + 1) in the other one.
-  auto iter = [&](auto slot_tag, const int j, v16i (&sa)[2], v16i (&sb)[2], float& c0, float& c1, float& n0, float& n1)
-      __attribute__((always_inline)) {
-    constexpr int SLOT = decltype(slot_tag)::value;
-    const bool has_next = j + 1 < ntiles;
-    // the copies of this iteration: K(j + 2) over K(j), whose S is done, and V(j + 1) over V(j - 1), whose P.V is done.  Then
-    // the counted wait: everything older than this iteration's copies has landed, K(j + 1) and V(j) among it.
-    lds_reads_done();
-    const int pg3 = page_at(j + 3);
-    if (j + 2 < ntiles) {
-      dma_k(j + 2, SLOT, pg2);
-      dma_v(j + 1, SLOT ^ 1, pg1);
-      dma_wait_keep<NK + NV>();
-    } else if (has_next) {
-      dma_v(j + 1, SLOT ^ 1, pg1);
-      dma_wait_keep<NV>();
-    } else {
-      dma_wait_all();
-    }
-    maybe_rescale(mx_cur);
-    if (has_next) {  // S(j + 1): independent of the softmax of tile j, so its MFMAs run beside the exponentials
-      scales_from(kk_nxt, n0, n1);
-      kk_nxt = load_kscales(min(j + 2, last_tile), pg2);
-      qk(SLOT ^ 1, sb);
-      if (j + 1 >= n_plain) mask_limit(j + 1, sb);
-    }
-    softmax_pv(SLOT, sa, c0, c1);
-    if (has_next) mx_cur = row_max(sb, n0, n1);
-    pg1 = pg2;
-    pg2 = pg3;
-  };
-  int j = 0;
-  for (; j + 1 < ntiles; j += 2) {
-    iter(std::integral_constant<int, 0>{}, j, s_a, s_b, a0, a1, b0, b1);
-    iter(std::integral_constant<int, 1>{}, j + 1, s_b, s_a, b0, b1, a0, a1);
-  }
-  if (j < ntiles) iter(std::integral_constant<int, 0>{}, j, s_a, s_b, a0, a1, b0, b1);
-
-  // ---- epilogue: the normalised fp32 partial of the split and its raw base-2 LSE into the workspace slot of (split, b, h, row)
-  const float l_tot = MROW ? ((row & 16) ? l4[1] : l4[0]) : swap_sum(l_run);
-  const float inv = 1.0f / l_tot;
-  if (row < M_) {
-    const int64_t srow = ((((int64_t)split * p.B + b) * p.Hq + h) * M_ + row);
-    float* const wp = p.sk_o + srow * D + 4 * hh;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d0 = 32 * dt + 8 * g4;
-        float x[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = acc_o[dt][4 * g4 + e] * inv;
-        if constexpr (PV_FP8) {
-          const float4 vs = *reinterpret_cast<const float4*>(p.v_scale + ((int64_t)b * p.Hk + hk) * D + d0 + 4 * hh);
-          x[0] *= vs.x; x[1] *= vs.y; x[2] *= vs.z; x[3] *= vs.w;
-        }
-        *reinterpret_cast<float4*>(wp + d0) = make_float4(x[0], x[1], x[2], x[3]);
-      }
-    if (hh == 0) p.sk_lse[srow] = m_run + log2f(l_tot) - kPOff;
-  }
+// ... on the paged MXFP4 V cache: P.V on the e2m1 image out of registers, P and everything before it as the FP8 mode
+template <int D, bool KTHREAD>
+__global__ __launch_bounds__(64) void attn_i8_decode_paged_v4_kernel(const AttnParams p) {
+  constexpr bool V_BF16 = false, PV_FP8 = true, PV_FP4 = true;
+#define SAGE_ATTN_DECODE_BODY_OF_KERNEL
+#include "sage_attn_decode_body.h"
+#undef SAGE_ATTN_DECODE_BODY_OF_KERNEL
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static int launch_decode_attn(const AttnCall& c, hipStream_t st, int grid) {
+static int launch_decode_attn(const AttnCall& c, bool pv_fp4, hipStream_t st, int grid) {
+  if (pv_fp4)
+    return by_dim(c.D, [&](auto d) {
+      return by_flag(c.kthread, [&](auto k) {
+        constexpr int D = decltype(d)::value;
+        constexpr size_t smem = decode_lds_bytes(D, true, true);
+        void (*kern)(const AttnParams) = attn_i8_decode_paged_v4_kernel<D, decltype(k)::value>;
+        if (!allow_lds((const void*)kern, smem)) return (int)SAGE_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), smem, st, c.p);
+        return launch_status();
+      });
+    });
   return by_dim(c.D, [&](auto d) {
     return by_flag(c.pv_fp8, [&](auto fp8) {
       constexpr int D = decltype(d)::value;
@@ -525,10 +102,11 @@ static int launch_decode_attn(const AttnCall& c, hipStream_t st, int grid) {
 }
 
 // What is the decode form's own is checked here, the rest as sage_attn_fusedq_pv_*_splitkv_paged(causal = 1) checks it; nothing
-// is enqueued before every check has passed.
+// is enqueued before every check has passed.  pv_fp4: v is the image pool and v_scale carries the scale pool's bytes, as in
+// sage_attn_fusedq_pv_f4_splitkv_paged.
 static int decode_entry(const sage_tensor* q, int q_dtype, const sage_tensor* k8, const sage_tensor* v, int v_dtype,
                         const sage_tensor* o, int o_dtype, const float* k_scale, const void* km, bool pv_fp8,
-                        const float* v_scale, float* lse, int B, int Hq, int Hk, int M, int D, int qk_gran, int warpq,
+                        bool pv_fp4, const float* v_scale, float* lse, int B, int Hq, int Hk, int M, int D, int qk_gran, int warpq,
                         float sm_scale, const int32_t* block_table, int64_t table_stride, int max_pages, int page_size,
                         int num_pages, const int32_t* kv_lens, int num_splits, int q_fold, void* workspace,
                         size_t workspace_bytes, sage_stream_t stream) {
@@ -539,6 +117,8 @@ static int decode_entry(const sage_tensor* q, int q_dtype, const sage_tensor* k8
       table_stride > INT_MAX)
     return SAGE_ERR_INVALID_ARGUMENT;
   if ((int64_t)max_pages * page_size > INT_MAX) return SAGE_ERR_TOO_LARGE;
+  // a row of the image holds the page's tiles side by side: narrower, a tile's loads would reach into the next channel
+  if (pv_fp4 && v && v->stride_n < page_size / 2) return SAGE_ERR_INVALID_ARGUMENT;
   if (M > kDecodeMaxRows) return SAGE_ERR_UNSUPPORTED;  // (more rows: sage_attn_fusedq_pv_*_splitkv_paged)
   AttnArgs a;
   a.q = q; a.q_dtype = q_dtype; a.k8 = k8; a.v = v; a.v_dtype = v_dtype; a.o = o; a.o_dtype = o_dtype; a.k_scale = k_scale;
@@ -552,7 +132,8 @@ static int decode_entry(const sage_tensor* q, int q_dtype, const sage_tensor* k8
   AttnCall c;
   if (const int s = attn_check(c, a)) return s;
   if ((int64_t)B * Hq * num_splits > INT_MAX) return SAGE_ERR_TOO_LARGE;
-  const int s = launch_decode_attn(c, (hipStream_t)stream, B * Hq * num_splits);
+  if (pv_fp4) c.p.v_tile_bytes = 32;  // a tile of the image is 32 bytes of every channel row
+  const int s = launch_decode_attn(c, pv_fp4, (hipStream_t)stream, B * Hq * num_splits);
   return s ? s : launch_splitkv_merge(c, (hipStream_t)stream);
 }
 
@@ -567,7 +148,7 @@ extern "C" int sage_attn_fusedq_pv_f16_decode_paged(const sage_tensor* q, int q_
                                                     const int32_t* block_table, int64_t table_stride, int max_pages,
                                                     int page_size, int num_pages, const int32_t* kv_lens, int num_splits,
                                                     int q_fold, void* workspace, size_t workspace_bytes, sage_stream_t stream) {
-  return decode_entry(q, q_dtype, k8_pool, v_pool, v_dtype, o, o_dtype, k_scale_pool, km, false, nullptr, lse, B, Hq, Hk, M, D,
+  return decode_entry(q, q_dtype, k8_pool, v_pool, v_dtype, o, o_dtype, k_scale_pool, km, false, false, nullptr, lse, B, Hq, Hk, M, D,
                       qk_gran, warpq, sm_scale, block_table, table_stride, max_pages, page_size, num_pages, kv_lens, num_splits,
                       q_fold, workspace, workspace_bytes, stream);
 }
@@ -579,7 +160,21 @@ extern "C" int sage_attn_fusedq_pv_f8_decode_paged(const sage_tensor* q, int q_d
                                                    const int32_t* block_table, int64_t table_stride, int max_pages,
                                                    int page_size, int num_pages, const int32_t* kv_lens, int num_splits,
                                                    int q_fold, void* workspace, size_t workspace_bytes, sage_stream_t stream) {
-  return decode_entry(q, q_dtype, k8_pool, v8_pool, SAGE_F16, o, o_dtype, k_scale_pool, km, true, v_scale, lse, B, Hq, Hk, M, D,
+  return decode_entry(q, q_dtype, k8_pool, v8_pool, SAGE_F16, o, o_dtype, k_scale_pool, km, true, false, v_scale, lse, B, Hq, Hk, M, D,
                       qk_gran, warpq, sm_scale, block_table, table_stride, max_pages, page_size, num_pages, kv_lens, num_splits,
                       q_fold, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sage_attn_fusedq_pv_f4_decode_paged(const sage_tensor* q, int q_dtype, const sage_tensor* k8_pool,
+                                                   const sage_tensor* v_img_pool, const sage_tensor* o, int o_dtype,
+                                                   const float* k_scale_pool, const void* km, const uint8_t* v_img_scale_pool,
+                                                   float* lse, int B, int Hq, int Hk, int M, int D, int qk_gran, int warpq,
+                                                   float sm_scale, const int32_t* block_table, int64_t table_stride,
+                                                   int max_pages, int page_size, int num_pages, const int32_t* kv_lens,
+                                                   int num_splits, int q_fold, void* workspace, size_t workspace_bytes,
+                                                   sage_stream_t stream) {
+  return decode_entry(q, q_dtype, k8_pool, v_img_pool, SAGE_F16, o, o_dtype, k_scale_pool, km, true, true,
+                      reinterpret_cast<const float*>(v_img_scale_pool), lse, B, Hq, Hk, M, D, qk_gran, warpq, sm_scale,
+                      block_table, table_stride, max_pages, page_size, num_pages, kv_lens, num_splits, q_fold, workspace,
+                      workspace_bytes, stream);
 }

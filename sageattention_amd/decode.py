@@ -14,8 +14,10 @@ does the arithmetic of that kernel's first wave in that wave's order.  Nothing d
 Ops: ``torch.ops.sageattention_amd_decode.attn_decode_paged[_lse]``; they trace under ``torch.compile(fullgraph=True)`` and
 capture into a HIP graph whose replay follows a table and lengths rewritten in place.
 
-Not built: the FP4 paged caches (the obvious next step: it is where the bytes matter most), the contiguous caches, the ragged,
-window, sink and shared-prefix forms, more than 16 splits, more than 32 rows, and a merge inside the attention launch."""
+The paged MXFP4 V cache has an operator of its own, ``sageattn_decode_paged_v4`` (decode_fp4.py).
+
+Not built: the contiguous caches, the ragged, window, sink and shared-prefix forms, more than 16 splits, more than 32 rows, and
+a merge inside the attention launch."""
 from typing import Any, Optional
 
 import torch

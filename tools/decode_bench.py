@@ -16,7 +16,11 @@ over the attention kernel's time.  Shapes (B, Hq, T, N, D), folded by g = 4 (Hk 
   (8, 32, 1, 8192, 128)     a decode step                         (64, 32, 1, 8192, 128)   ... of a large batch
   (1, 32, 1, 65536, 128)    one long sequence                     (8, 32, 4, 8192, 128)    4 speculative tokens: q [8, 8, 16, 128]
 
-There is no pass / fail time.  usage: decode_bench.py [--repeats 5] [--window-ms 100] [--pv fp16,fp8] [--shapes 0,1,2,3] [--out F]"""
+``--pv fp4`` measures ``sageattn_decode_paged_v4`` on a ``SagePagedKVCacheV4`` instead: the yardstick is
+``sageattn_splitkv_paged_v4(causal=True)`` on the same cache, and a second one, "decode, FP8 cache", is ``sageattn_decode_paged``
+on a ``SagePagedKVCache(pv="fp8")`` over the same pools (profiles/decode_fp4.md).
+
+There is no pass / fail time.  usage: decode_bench.py [--repeats 5] [--window-ms 100] [--pv fp16,fp8,fp4] [--shapes 0,1,2,3] [--out F]"""
 import argparse
 import os
 import statistics
@@ -116,9 +120,10 @@ def setup(B, Hq, T, N, D, pv):
     v = torch.randn(P, Hk, PAGE, D, generator=gen, device="cuda", dtype=torch.float16)
     table = torch.randperm(P, generator=gen, device="cuda").to(torch.int32).view(B, N // PAGE)
     lens = torch.full((B,), N, dtype=torch.int32, device="cuda")
-    cache = sa.SagePagedKVCache.prepare(k, v, table, lens, pv=pv)
+    cache = sa.SagePagedKVCacheV4.prepare(k, v, table, lens) if pv == "fp4" else sa.SagePagedKVCache.prepare(k, v, table, lens, pv=pv)
+    cache8 = sa.SagePagedKVCache.prepare(k, v, table, lens, pv="fp8") if pv == "fp4" else None  # the second yardstick's cache
     q = torch.randn(B, Hk, T * G, D, generator=gen, device="cuda", dtype=torch.float16)
-    return cache, table, lens, q
+    return cache, cache8, table, lens, q
 
 
 def main():
@@ -127,16 +132,22 @@ def main():
     for si in (int(s) for s in a.shapes.split(",")):
         B, Hq, T, N, D = SHAPES[si]
         for pv in a.pv.split(","):
-            cache, table, lens, q = setup(B, Hq, T, N, D, pv)
+            cache, cache8, table, lens, q = setup(B, Hq, T, N, D, pv)
             Hk = Hq // G
-            kv_bytes = B * Hk * N * D * (1 + (1 if pv == "fp8" else 2))
+            fp4 = pv == "fp4"
+            # (FP4: half a byte per element of V and 2 * D scale bytes per 64 keys)
+            kv_bytes = B * Hk * N * (D * 3 // 2 + D // 32) if fp4 else B * Hk * N * D * (1 + (1 if pv == "fp8" else 2))
+            f_dec = sa.sageattn_decode_paged_v4 if fp4 else sa.sageattn_decode_paged
+            f_yard = sa.sageattn_splitkv_paged_v4 if fp4 else sa.sageattn_splitkv_paged
+            k_dec = "attn_i8_decode_paged_v4_kernel" if fp4 else "attn_i8_decode_paged_kernel"
+            k_yard = "attn_i8_splitkv_causal_paged_v4_kernel" if fp4 else "attn_i8_splitkv_causal_paged_kernel"
             s_dec, s_yard = sa.decode_num_splits(B, Hk, N), core.splitkv_num_splits(B, Hk, T * G, N)
 
             def dec(S):
-                return lambda: sa.sageattn_decode_paged(q, cache, table, lens, num_splits=S, q_fold=G, return_lse=True)
+                return lambda: f_dec(q, cache, table, lens, num_splits=S, q_fold=G, return_lse=True)
 
             def yard(S):
-                return lambda: sa.sageattn_splitkv_paged(q, cache, table, lens, num_splits=S, causal=True, q_fold=G, return_lse=True)
+                return lambda: f_yard(q, cache, table, lens, num_splits=S, causal=True, q_fold=G, return_lse=True)
 
             def step(attn):
                 def run():
@@ -150,18 +161,23 @@ def main():
                  f"yardstick S = {s_yard}; bits equal at S = {s_dec}: {same}")
             variants = {"decode": step(dec(s_dec)), "yardstick": step(yard(s_yard)), "yardstick again": step(yard(s_yard)),
                         "yardstick, equal S": step(yard(s_dec))}
+            if fp4:  # the FP8 cache's own append and its one-wave kernel, over the same pools
+                def step8():
+                    cache8.append(table, lens, lens, 1)
+                    sa.sageattn_decode_paged(q, cache8, table, lens, num_splits=s_dec, q_fold=G, return_lse=True)
+                variants["decode, FP8 cache"] = graph_of(step8)
             ts = rounds(variants, a.repeats)
             emit("| variant | step us (median) | / yardstick | attention us (least .. greatest of 3 traces) | merge us | K + V TB/s |")
             emit("|---|---|---|---|---|---|")
             for name, t in ts.items():  # every variant's kernels out of its OWN graph's replays
-                at, lo, hi, mg = kernel_us(variants[name], "attn_i8_decode_paged_kernel" if name == "decode"
-                                           else "attn_i8_splitkv_causal_paged_kernel")
+                at, lo, hi, mg = kernel_us(variants[name], k_dec if name == "decode" else "attn_i8_decode_paged_kernel"
+                                           if name == "decode, FP8 cache" else k_yard)
                 emit(f"| {name} | {statistics.median(t):.1f} | {fmt_ratio(t, ts['yardstick'])} | {at:.1f} ({lo:.1f} .. {hi:.1f}) | "
                      f"{mg:.1f} | {kv_bytes / at / 1e6:.2f} |")
             sweep = {f"S={S}": step(dec(S)) for S in range(1, 17)}
             st = rounds(sweep, max(2, a.repeats // 2))
             emit("decode step us over S = 1..16: " + " ".join(f"{statistics.median(st[f'S={S}']):.1f}" for S in range(1, 17)))
-            del cache, table, lens, q
+            del cache, cache8, table, lens, q
             torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f:
