@@ -38,8 +38,10 @@
  *
  * The paged MXFP4 V cache has its own entry: sageattn_hip_decode_fp4.h.
  *
- * NOT BUILT: the contiguous caches; the ragged, window, sink and shared-prefix forms; more than 16 splits; more than 32 rows;
- * a merge inside the attention launch.
+ * The window and sink forms, and with one split the merge inside the attention launch: sageattn_hip_decode_window.h.
+ *
+ * NOT BUILT: the contiguous caches; the ragged and shared-prefix forms; more than 16 splits; more than 32 rows; a merge inside
+ * the attention launch of the two entries here.
  */
 #ifndef SAGEATTN_HIP_DECODE_H
 #define SAGEATTN_HIP_DECODE_H

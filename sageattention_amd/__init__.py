@@ -21,6 +21,7 @@ from .ragged import RaggedQPlan, ragged_q_plan, sageattn_splitkv_paged_ragged  #
 from .window import sageattn_splitkv_paged_window, sageattn_splitkv_paged_ragged_window  # ... with a sliding window and sink logits
 from .decode import sageattn_decode_paged, sageattn_decode_paged_compilable, decode_num_splits  # decode steps: one wave per split
 from .decode_fp4 import sageattn_decode_paged_v4, sageattn_decode_paged_v4_compilable  # ... on the paged MXFP4 V cache
+from .decode_window import sageattn_decode_paged_window, sageattn_decode_paged_window_compilable  # ... with a window and sinks
 
 __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp16_triton",
            "sageattn_qk_int8_pv_fp8_cuda", "sageattn_qk_int8_pv_fp8_cuda_sm90", "sageattn_varlen", "ring_sageattn",
@@ -33,5 +34,6 @@ __all__ = ["sageattn", "sageattn_qk_int8_pv_fp16_cuda", "sageattn_qk_int8_pv_fp1
            "RaggedQPlan", "ragged_q_plan", "sageattn_splitkv_paged_ragged",
            "sageattn_splitkv_paged_window", "sageattn_splitkv_paged_ragged_window",
            "sageattn_decode_paged", "sageattn_decode_paged_compilable", "decode_num_splits",
-           "sageattn_decode_paged_v4", "sageattn_decode_paged_v4_compilable"]
+           "sageattn_decode_paged_v4", "sageattn_decode_paged_v4_compilable",
+           "sageattn_decode_paged_window", "sageattn_decode_paged_window_compilable"]
 __version__ = "0.2.0"

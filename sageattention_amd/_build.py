@@ -50,6 +50,8 @@ SOURCES = [
     # decode attention on the paged cache: one wave per split, a kernel text of its own (contraction off: it has the bits of
     # the causal paged split-KV kernel), and in the same text its twin on the paged MXFP4 V cache
     ("sage_attn_decode.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
+    # ... with a sliding window and sink logits, and with one split the merge's arithmetic in its epilogue: the same text and flags
+    ("sage_attn_decode_window.hip", ["-fno-slp-vectorize", "-ffp-contract=off"] + NO_PK_F32),
     ("sage_fp8.hip", []),
     ("sage_misc.hip", []),
     ("sage_op.hip", []),
@@ -189,6 +191,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_window.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode_fp4.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "sageattn_hip_decode_window.h"))
     hdr_key = _digest(*[_read(h) for h in hdrs])
     keys = {src: _digest(HIPCC, ARCH, " ".join(COMMON + extra), _read(os.path.join(CSRC, src)), hdr_key)
             for src, extra in SOURCES}
@@ -237,6 +240,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_ragged.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_splitkv_window.o"))
     _check_m0_private(os.path.join(CSRC, "sage_attn_decode.o"))
+    _check_m0_private(os.path.join(CSRC, "sage_attn_decode_window.o"))
     cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:

@@ -211,16 +211,20 @@ DECODE_FP4_SIGNATURES = {
     for name, (res, args) in PAGED_FP4_SIGNATURES.items() if name.startswith("sage_attn_")
 }
 
+# include/sageattn_hip_decode_window.h: the decode entries, each followed by window and sinks
+DECODE_WINDOW_SIGNATURES = {f"{name}_window": (res, args + [_I, _V]) for name, (res, args) in DECODE_SIGNATURES.items()}
+
 
 def bind(cdll, missing_ok=True):
     """Set restype / argtypes on every SIGNATURES, KVCACHE_SIGNATURES, PAGED_SIGNATURES, PAGED_ROWS_SIGNATURES,
-    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES, RAGGED_SIGNATURES, WINDOW_SIGNATURES, DECODE_SIGNATURES and
-    DECODE_FP4_SIGNATURES symbol ``cdll`` has and return it.  An older library
+    PREFIX_SIGNATURES, FP4_SIGNATURES, PAGED_FP4_SIGNATURES, RAGGED_SIGNATURES, WINDOW_SIGNATURES, DECODE_SIGNATURES,
+    DECODE_FP4_SIGNATURES and DECODE_WINDOW_SIGNATURES symbol ``cdll`` has and return it.  An older library
     loaded for an A/B run may lack some; with ``missing_ok=False`` (the package's own library) a missing symbol raises
     AttributeError."""
     for name, (res, args) in {**SIGNATURES, **KVCACHE_SIGNATURES, **PAGED_SIGNATURES, **PAGED_ROWS_SIGNATURES,
                               **PREFIX_SIGNATURES, **FP4_SIGNATURES, **PAGED_FP4_SIGNATURES, **RAGGED_SIGNATURES,
-                              **WINDOW_SIGNATURES, **DECODE_SIGNATURES, **DECODE_FP4_SIGNATURES}.items():
+                              **WINDOW_SIGNATURES, **DECODE_SIGNATURES, **DECODE_FP4_SIGNATURES,
+                              **DECODE_WINDOW_SIGNATURES}.items():
         fn = getattr(cdll, name, None) if missing_ok else getattr(cdll, name)
         if fn is not None:
             fn.restype, fn.argtypes = res, args

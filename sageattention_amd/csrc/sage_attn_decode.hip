@@ -37,20 +37,6 @@
 
 namespace sage {
 
-constexpr int kDecodeRing = 2;       // K slots and V slots of a wave's ring
-constexpr int kDecodeMaxRows = 32;   // one wave: one 32-row MFMA block of query rows
-constexpr size_t decode_lds_bytes(int D, bool pv_fp8, bool pv_fp4 = false) {
-  return (size_t)kDecodeRing * (64 * D + (pv_fp4 ? 0 : pv_fp8 ? 64 * D : 128 * D));
-}
-
-// every LDS read the wave has issued has returned (the scalar loads in flight share the counter and land as well): in front of
-// the copies that re-fill a slot the wave has read
-__device__ __forceinline__ void lds_reads_done() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-}
-
 // The wave is one text for both kernels (sage_attn_decode_body.h), included INTO each as the shared attention body is: as a
 // __forceinline__ device template hipcc allocated every register of the existing twelve instantiations anew.
 template <int D, bool KTHREAD, bool V_BF16, bool PV_FP8>

@@ -1,9 +1,11 @@
 // The body of the decode kernels: included INTO attn_i8_decode_paged_kernel and attn_i8_decode_paged_v4_kernel
-// (sage_attn_decode.hip, which says what it does), not a header in the usual sense.
+// (sage_attn_decode.hip, which says what it does) and attn_i8_decode_paged_window_kernel (sage_attn_decode_window.hip), not a
+// header in the usual sense.
 // Expects in scope: the kernel parameter block `p` and the compile-time constants D, KTHREAD, V_BF16, PV_FP8, PV_FP4
-// (PV_FP4, with PV_FP8, whose P it shares: V is the paged MXFP4 image, held in registers).
+// (PV_FP4, with PV_FP8, whose P it shares: V is the paged MXFP4 image, held in registers).  What the windowed kernel adds stands
+// under SAGE_ATTN_DECODE_BODY_WINDOW, which its file defines: the other kernels keep their text.
 #ifndef SAGE_ATTN_DECODE_BODY_OF_KERNEL
-#error "sage_attn_decode_body.h is the body of the decode kernels (sage_attn_decode.hip): included nowhere else"
+#error "sage_attn_decode_body.h is the body of the decode kernels (sage_attn_decode*.hip): included nowhere else"
 #endif
   static_assert(!(PV_FP8 && V_BF16), "fp8 V has no bf16 flavour");
   static_assert(!PV_FP4 || PV_FP8, "the FP4 image is multiplied by the FP8 mode's P");
@@ -38,9 +40,37 @@
 
   // ---- the split's range of logical tiles and the diagonal in its coordinates (wave uniform; an empty split returns at once)
   const int len_b = min(max(uniform_load_i32(p.kv_lens + b), 0), p.N);
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+  // WINDOW (attn_i8_decode_paged_window_kernel, sage_attn_decode_window.hip, which defines the macro, the int `dw_window` >= 1,
+  // `dw_sinks` and `dw_fused`; the rule: include/sageattn_hip_decode_window.h).  The call is one q-block: its keys lie between
+  // the lower limit of row 0 and the upper limit of the last row < M, the tiles [dw_tlo, dw_tlo + dw_nt), cut into the splits'
+  // ranges like the batch's tiles otherwise.  No tile below dw_tlo is named from here on, so no table entry below
+  // max(off_b - window + 1, 0) / page_size is read.  (window <= p.N: the host clamps it.)  dw_fused -- the host sets it iff
+  // num_splits == 1 -- finishes the rows in this launch (the epilogue below); a sequence without keys then gets its zeros and
+  // -inf here, from the lanes that own its rows.
+  auto dw_store_empty = [&]() __attribute__((always_inline)) {
+    const int row = threadIdx.x & 31, hh = threadIdx.x >> 5;
+    if (row >= M_) return;
+    uint16_t* const op = p.o + b * p.osb + h * p.osh + (int64_t)row * p.osn + 4 * hh;
+#pragma unroll
+    for (int d0 = 0; d0 < D; d0 += 8) *reinterpret_cast<uint2*>(op + d0) = make_uint2(0u, 0u);
+    if (hh == 0 && p.lse) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = -INFINITY;
+  };
+  const int dw_off = len_b - M_ / p.q_fold;
+  const int dw_lo = max(dw_off - dw_window + 1, 0);
+  const int dw_hi = min((M_ - 1) / p.q_fold + dw_off, len_b - 1);
+  if (dw_hi < 0) {
+    if (dw_fused) dw_store_empty();
+    return;
+  }
+  const int dw_tlo = dw_lo >> 6, dw_nt = (dw_hi >> 6) - dw_tlo + 1, tps_b = (dw_nt + p.num_splits - 1) / p.num_splits;
+  const int sk_t0 = dw_tlo + split * tps_b;
+  const int t1 = min(sk_t0 + tps_b, dw_tlo + dw_nt);
+#else
   const int ntk_b = (len_b + 63) >> 6, tps_b = (ntk_b + p.num_splits - 1) / p.num_splits;
   const int sk_t0 = split * tps_b;
   const int t1 = min(sk_t0 + tps_b, ntk_b);
+#endif
   if (sk_t0 >= t1) return;
   const int N_ = min(len_b, t1 << 6) - (sk_t0 << 6);         // keys from the split's first one to its end
   const int sk_off = (len_b - (sk_t0 << 6)) - M_ / p.q_fold;  // off_b in the split's coordinates
@@ -59,11 +89,24 @@
   const int rowc = min(row, M_ - 1);
   // the last key (of the split's coordinates) the lane's row may attend; every negative limit is held at -1
   const int lim_l = max(row / p.q_fold + sk_off, -1);
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+  // The FIRST key the lane's row may attend is lim_l - window + 1: no register of its own, mask_limit forms it from lim_l where
+  // a tile needs it (a row whose lim_l is held at -1 has no key whatever its lower limit is; rows >= M keep the limits of their
+  // row index on both sides).  dw_nlm, the tiles that need the lower mask, counted once: tile j does iff 64 * j < the lower limit
+  // of the last row < M -- the first one or two tiles of the first split that runs.
+  const int dw_nlm = (max((M_ - 1) / p.q_fold + sk_off - dw_window + 1, 0) + 63) >> 6;
+#define SAGE_DECODE_TILE_MASKED(t) ((t) >= n_plain || (t) < dw_nlm)
+#else
+#define SAGE_DECODE_TILE_MASKED(t) ((t) >= n_plain)
+#endif
 
   // ---- Q^T fragments (B operand) and the row's scale: the fused Q quantizer of the shared body on the wave's 32 rows.  Lane
   //      (r, hh) owns the 16-column chunks [32 * ks + 16 * hh, +16) of its row; rows >= M load the last row's bytes and are zeros.
   v4i qf[KS];
   float qsc;
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+  float dw_corr = 0.f;  // q . km of the lane's row, held for the finish inside the launch
+#endif
   auto prepare_q = [&]() __attribute__((always_inline)) {
     const bool valid = row < M_;
     const uint16_t* qp = p.q_f16 + b * p.qsb + h * p.qsh + (int64_t)rowc * p.qsn + 16 * hh;
@@ -100,7 +143,12 @@
         }
       amax = swap_max(amax);  // the other half of the row
       const float lse_corr = swap_sum(dot);
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+      dw_corr = lse_corr;  // (dw_fused: the epilogue adds it itself, nothing is parked)
+      if (!dw_fused && split == 0 && p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
+#else
       if (split == 0 && p.lse && hh == 0 && valid) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = lse_corr;
+#endif
       if constexpr (KTHREAD) {  // per thread: rows with equal r % 8 of the 32-row block share a scale
         amax = fmaxf(amax, __shfl_xor(amax, 8));
         amax = fmaxf(amax, __shfl_xor(amax, 16));
@@ -350,6 +398,17 @@
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) <= lim) ? s[mt][e] : kMaskedI;
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+    // two-sided, lo <= key <= lim, in a second pass of the same select so that only one limit is live at a time; the lower one
+    // where the tile needs it (wave uniform)
+    if (j < dw_nlm) {
+      const int lo = lim_l - (dw_window - 1) - (j << 6) - 4 * hh;
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[mt][e] = (32 * mt + (e & 3) + 8 * (e >> 2) >= lo) ? s[mt][e] : kMaskedI;
+    }
+#endif
   };
   // row max of a tile's logits from the raw integers (the scales are positive)
   auto row_max = [&](const v16i (&s)[2], const float sc0, const float sc1) __attribute__((always_inline)) -> float {
@@ -470,7 +529,7 @@
   float a0, a1, b0 = 0.f, b1 = 0.f, mx_cur;
   qk(0, s_a);
   scales_from(load_kscales(0, pg0), a0, a1);
-  if (n_plain <= 0) mask_limit(0, s_a);
+  if (SAGE_DECODE_TILE_MASKED(0)) mask_limit(0, s_a);
   mx_cur = row_max(s_a, a0, a1);
   float4 kk_nxt = load_kscales(min(1, last_tile), pg1);
 
@@ -507,7 +566,7 @@
       scales_from(kk_nxt, n0, n1);
       kk_nxt = load_kscales(min(j + 2, last_tile), pg2);
       qk(SLOT ^ 1, sb);
-      if (j + 1 >= n_plain) mask_limit(j + 1, sb);
+      if (SAGE_DECODE_TILE_MASKED(j + 1)) mask_limit(j + 1, sb);
     }
     if constexpr (PV_FP4) {  // V(j) has landed: only K(j + 2) is younger
       if (j + 2 < ntiles) dma_wait_keep<NK>();
@@ -531,6 +590,77 @@
   // ---- epilogue: the normalised fp32 partial of the split and its raw base-2 LSE into the workspace slot of (split, b, h, row)
   const float l_tot = MROW ? ((row & 16) ? l4[1] : l4[0]) : swap_sum(l_run);
   const float inv = 1.0f / l_tot;
+#ifdef SAGE_ATTN_DECODE_BODY_WINDOW
+  // The finish inside the launch (one split): no partial is written.  The lane does what window_merge_row
+  // (sage_attn_splitkv_window.hip) does for count == 1 with the values it would have stored -- that function's operations in its
+  // order, its library calls, ONE rounding of the output -- so the row has the bits of the two-launch path.
+  // Lane (row, hh) holds 4 neighbouring channels per (dt, g4): one 8-byte store each, as a thread of the merge.
+  if (dw_fused) {
+    if (row >= M_) return;
+    const float l0 = m_run + log2f(l_tot) - kPOff;  // the raw base-2 LSE of the split
+    const float mx = fmaxf(-INFINITY, l0);
+    const bool use = l0 != -INFINITY;               // (a row without a key: o = 0, lse = -inf)
+    const float w = exp2f(l0 - mx);
+    float sum = 0.f;
+    sum = use ? sum + w : sum;
+    const float minv = sum > 0.f ? 1.0f / sum : 0.f;
+    float v, keep = 1.0f;
+    {
+#pragma clang fp contract(off)
+      v = (sum > 0.f ? mx + log2f(sum) : -INFINITY) / 1.44269504f;
+      v += (p.lse ? dw_corr : 0.f) * p.sm_scale;
+      if (dw_sinks && sum > 0.f) {
+        const float sk = dw_sinks[h * p.q_fold + row % p.q_fold];
+        const float top = fmaxf(v, sk);
+        const float v2 = top + logf(expf(v - top) + expf(sk - top));
+        keep = expf(v - v2);
+        v = v2;
+      }
+    }
+    const float kf = dw_sinks ? minv * keep : minv;
+    uint16_t* const op = p.o + b * p.osb + h * p.osh + (int64_t)row * p.osn + 4 * hh;
+    auto finish = [&](auto bf16_tag) __attribute__((always_inline)) {
+      constexpr bool BF16 = decltype(bf16_tag)::value;
+      // a * kf rounded ONCE to fp16, as the merge's statement comes out of hipcc there (v_fma_mixlo_f16: product and convert
+      // in one instruction).  Here the same statement came out as that instruction for some elements of the unrolled store
+      // and as a multiply and a convert -- two roundings, an ulp apart in one element of a few thousand -- for others, so the
+      // instruction is named.  bf16 has no such instruction: product, then convert, in both kernels.
+      auto rounded = [&](const float a) __attribute__((always_inline)) -> uint32_t {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (!BF16) {
+          uint32_t bits;
+          asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(bits) : "v"(a), "v"(kf));
+          return bits & 0xffffu;
+        }
+#endif
+        return (uint32_t)f32_to_elem_bits<BF16>(a * kf);
+      };
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int d0 = 32 * dt + 8 * g4;
+          float x[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) x[e] = acc_o[dt][4 * g4 + e] * inv;
+          if constexpr (PV_FP8 && !PV_FP4) {
+            const float4 vs = *reinterpret_cast<const float4*>(p.v_scale + ((int64_t)b * p.Hk + hk) * D + d0 + 4 * hh);
+            x[0] *= vs.x; x[1] *= vs.y; x[2] *= vs.z; x[3] *= vs.w;
+          }
+          float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = use ? acc[e] + x[e] * w : acc[e];
+          uint2 w2;
+          w2.x = rounded(acc[0]) | (rounded(acc[1]) << 16);
+          w2.y = rounded(acc[2]) | (rounded(acc[3]) << 16);
+          *reinterpret_cast<uint2*>(op + d0) = w2;
+        }
+    };
+    if (p.out_bf16) finish(std::true_type{}); else finish(std::false_type{});
+    if (hh == 0 && p.lse) p.lse[((int64_t)b * p.Hq + h) * M_ + row] = v;
+    return;
+  }
+#endif
   if (row < M_) {
     const int64_t srow = ((((int64_t)split * p.B + b) * p.Hq + h) * M_ + row);
     float* const wp = p.sk_o + srow * D + 4 * hh;
@@ -550,3 +680,4 @@
       }
     if (hh == 0) p.sk_lse[srow] = m_run + log2f(l_tot) - kPOff;
   }
+#undef SAGE_DECODE_TILE_MASKED

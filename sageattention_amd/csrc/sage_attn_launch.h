@@ -38,4 +38,23 @@ static void by_slots(int count, F&& f) {
   else f(std::integral_constant<int, 16>{});
 }
 
+// ---- the one-wave decode kernels (sage_attn_decode.hip, sage_attn_decode_window.hip; their text: sage_attn_decode_body.h)
+constexpr int kDecodeRing = 2;       // K slots and V slots of a wave's ring
+constexpr int kDecodeMaxRows = 32;   // one wave: one 32-row MFMA block of query rows
+constexpr size_t decode_lds_bytes(int D, bool pv_fp8, bool pv_fp4 = false) {
+  return (size_t)kDecodeRing * (64 * D + (pv_fp4 ? 0 : pv_fp8 ? 64 * D : 128 * D));
+}
+
+// every LDS read the wave has issued has returned (the scalar loads in flight share the counter and land as well): in front of
+// the copies that re-fill a slot the wave has read
+__device__ __forceinline__ void lds_reads_done() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+}
+
+// the merge launch of a windowed call on [B, Hq, M] rows (window_merge_kernel, sage_attn_splitkv_window.hip), for the entries of
+// that file and of sage_attn_decode_window.hip: `window` already clamped to the capacity, sinks fp32 [query heads] or null
+int launch_window_merge(const AttnCall& c, int window, const float* sinks, hipStream_t st);
+
 }  // namespace sage

@@ -278,12 +278,20 @@ static int window_entry(const sage_tensor* q, int q_dtype, const sage_tensor* k8
     return attn_i8_splitkv_causal_paged_window_kernel<decltype(d)::value, decltype(k)::value, decltype(vb)::value,
                                                       decltype(fp8)::value>;
   });
-  if (s) return s;
-  const int64_t threads = (int64_t)B * Hq * M * (D / 4);
+  return s ? s : launch_window_merge(c, wp.window, sinks, st);
+}
+
+// (declared in sage_attn_launch.h: sage_attn_decode_window.hip merges its splits with it as well)
+int launch_window_merge(const AttnCall& c, int window, const float* sinks, hipStream_t st) {
+  WindowParams wp;
+  wp.a = c.p;
+  wp.sinks = sinks;
+  wp.window = window;
+  const int64_t threads = (int64_t)c.p.B * c.p.Hq * c.p.M * (c.D / 4);
   by_flag(c.p.out_bf16 != 0, [&](auto bf) {
-    by_slots(num_splits, [&](auto slots) {
+    by_slots(c.p.num_splits, [&](auto slots) {
       hipLaunchKernelGGL((window_merge_kernel<decltype(bf)::value, decltype(slots)::value>),
-                         dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, wp, D);
+                         dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, wp, c.D);
     });
   });
   return launch_status();

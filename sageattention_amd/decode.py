@@ -16,8 +16,11 @@ capture into a HIP graph whose replay follows a table and lengths rewritten in p
 
 The paged MXFP4 V cache has an operator of its own, ``sageattn_decode_paged_v4`` (decode_fp4.py).
 
-Not built: the contiguous caches, the ragged, window, sink and shared-prefix forms, more than 16 splits, more than 32 rows, and
-a merge inside the attention launch."""
+A sliding window, sink logits and -- with one split -- the merge inside the attention launch: ``sageattn_decode_paged_window``
+(decode_window.py).
+
+Not built: the contiguous caches, the ragged and shared-prefix forms, more than 16 splits, more than 32 rows, and a merge inside
+the attention launch of this operator."""
 from typing import Any, Optional
 
 import torch
